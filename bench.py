@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native detect -> SORT hot path (contract: see the driver's bench.py rules).
 
-    python bench.py --gpus N --steps K --warmup W [--stage e2e|detect|track|ensemble]
+    python bench.py --gpus N --steps K --warmup W [--stage e2e|detect|track|ensemble] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM.
   e2e      (default, BASELINE.json metric): detector on `--frames-per-step` synthetic 1920x1280x3 frames of one
@@ -12,8 +12,12 @@ One "step" = one pass of the hot path over one batch of synthetic input that is 
   train    one training step fwd+bwd+SGD (config 5), DDP over RCCL for N > 1.
 Multi-GPU: one process per GPU (torchrun), camera sequences / frames sharded with no data-path collective in
 the timed region (weak scaling); the only exchange is the ID-offset all_gather + result gather done by the CLIs.
-Rank 0 prints ONE JSON line with `roofline` (dominant hand-written kernel, HIP-event timed) and `cpu_baseline`
-(the C oracle timed on the host, bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it (`ms_per_step` = one timed step);
+`--full` adds what takes work of its own: `verified` (oracle replay of the timed output), `cpu_baseline` (the C oracle timed on the
+host, bounded sample), the e2e `roofline` (dominant hand-written kernel, HIP-event timed on an instrumented frame of the timed steps,
+offset-spread sweep) and the secondary e2e lines (`extra.exact_f32`, `extra.one_frame_in_flight`).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -58,7 +62,19 @@ def parse_args():
                     'behind the bottom-up pathway of the next frame (A/B of the overlap placement)')
     ap.add_argument('--no-graph', action='store_true', help='e2e/detect: launch every frame eagerly instead of replaying the captured hipGraph')
     ap.add_argument('--no-verify', action='store_true', help='skip the oracle replay of the timed output (after the timed region)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline figure: oracle replay (`verified`), `cpu_baseline`, HIP-event roofline of an '
+                         'instrumented frame, offset-spread sweep, the exact-f32 / one-frame-in-flight lines.  Off: set up, warm up, '
+                         'time the steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         '<= 64 MB in all; a fixed seeded row sample of larger outputs)')
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:
+        args.no_verify = args.no_cpu_baseline = True          # both only with --full
+    return args
 
 
 def check_flags(args):
@@ -176,6 +192,67 @@ def timed_steps(world, run_step, steps, warmup):
     return dt, ev_ms
 
 
+DUMP_BYTES = 60 * 2 ** 20     # --dump-outputs: at most 64 MB in all (sample row numbers included; .npy headers fit in the rest)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (uint8 / float32 data) or float64 (everything else: the int ids,
+    frames and categories are exact in it).  When the total exceeds DUMP_BYTES, every array above 1 MB keeps a fixed seeded sample
+    of its rows - the same rows for all arrays of the same length n, whose row numbers are written once as DIR/sample_rows_<n>.npy -
+    sized so that the samples and their row numbers together stay within the budget."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype in (np.uint8, np.float16, np.float32) else np.float64)
+    if sum(a.nbytes for a in out.values()) > DUMP_BYTES:
+        big = [name for name, a in out.items() if a.nbytes > 2 ** 20]
+        small = sum(a.nbytes for name, a in out.items() if name not in big)
+        row_bytes = {}                                   # length n -> bytes of one sampled row over all arrays of that length + its row number
+        for name in big:
+            a = out[name]
+            row_bytes[a.shape[0]] = row_bytes.get(a.shape[0], 8) + a.nbytes // a.shape[0]
+        frac = (DUMP_BYTES - small) / float(sum(n * b for n, b in row_bytes.items()))
+        rows = {n: np.unique(np.random.default_rng(n).integers(0, n, max(1, int(n * frac)))) for n in row_bytes}
+        for name in big:
+            out[name] = np.ascontiguousarray(out[name][rows[out[name].shape[0]]])
+        for n, r in rows.items():
+            out['sample_rows_%d' % n] = r.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return sorted(out)
+
+
+def e2e_outputs(pipe, track):
+    """What the last timed e2e / detect step handed on: the wire-format detections of its chunk (camera-major frames x 100 slots:
+    x, y, w, h, score and category, 0 = empty slot) and, with tracking, the tracker rows that chunk produced, in a canonical order
+    (frame, category, id) and with the chunk's (rows, births)."""
+    import torch
+    torch.cuda.synchronize()
+    c = pipe.chunk - 1                                   # the chunk the last step filled (a step leaves pipe.chunk >= 1)
+    out = dict(det_xywhs=pipe.xywhs[c].t().cpu().numpy(), det_category=pipe.category[c].cpu().numpy())
+    if track:
+        counts = pipe.chunk_counts[c].cpu().numpy()
+        if counts[0] < 0:
+            raise SystemExit('bench.py: SORT kernel status %d' % -int(counts[0]))
+        rows = {n: v[:int(counts[0])].cpu().numpy() for n, v in pipe.rows.columns(c).items()}
+        order = np.lexsort((rows['local_id'], rows['category'], rows['frame']))
+        out.update(('track_' + n, v[order]) for n, v in rows.items())
+        out['track_counts'] = counts
+    return out
+
+
+def train_outputs(det, loss):
+    """What the last timed training step left: its loss and a fixed seeded sample of 2^20 trainable parameters after its SGD update
+    (positions into the concatenation of the trainable parameters in module order: train_param_index)."""
+    import torch
+    ps = [p for p in det.model.parameters() if p.requires_grad]
+    idx = np.unique(np.random.default_rng(0).integers(0, sum(p.numel() for p in ps), 1 << 20))
+    flat = torch.cat([p.detach().reshape(-1) for p in ps])
+    return dict(train_loss=np.asarray([loss]), train_param_sample=flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy(),
+                train_param_index=idx)
+
+
 def build_predictions(seed, n_segments, n_frames=198, n_objects=100):
     from waymo_2d_tracking_amd import synthetic as syn
     rng = np.random.default_rng(seed)
@@ -242,6 +319,8 @@ def stage_track(args, world, rank):
                extra=dict(n_dets=n_dets, n_rows=rows, n_births=births, n_frames=n_frames,
                           births_by_rank=all_counts.view(-1, 2)[:, 1].cpu().tolist() if _dist_on() else None))
     res['roofline']['frac'] = res['roofline']['achieved'] / F64_VALU_PEAK_GFLOPS
+    if rank == 0 and args.dump_outputs:
+        res['outputs'] = dict({'track_' + k: v for k, v in out.items()}, track_births=np.asarray([births]))
     if rank == 0 and not args.no_verify:
         # checker, outside the timed region: the rows of the timed call replayed through the CPU oracle
         from oracle import oracle as O
@@ -378,6 +457,13 @@ def stage_ensemble(args, world, rank):
                                   'average: latency / division-throughput bound; 17 flops per ordered pair counted'),
                extra=dict(n_rows=int(len(d)), n_groups=int(len(off) - 1)))
     res['roofline']['frac'] = res['roofline']['achieved'] / F64_VALU_PEAK_GFLOPS
+    if rank == 0 and args.dump_outputs:
+        # the surviving rows of every group (the first counts[g] rows of its block), groups in order
+        import torch
+        torch.cuda.synchronize()
+        got, counts = ens.out5[:len(d)].cpu().numpy(), ens.counts[:len(off) - 1].cpu().numpy()
+        res['outputs'] = dict(ensemble_rows=np.concatenate([got[int(off[g]):int(off[g]) + int(counts[g])] for g in range(len(off) - 1)]),
+                              ensemble_counts=counts)
     if rank == 0 and not args.no_verify:
         import torch
         from oracle import oracle as O
@@ -532,12 +618,15 @@ def stage_decode(args, world, rank):
         with torch.cuda.stream(st):
             return ops.jpeg_decode(data)
 
+    last = {}
+
     def step():
-        return list(pool.map(one, batch))
+        last['outs'] = list(pool.map(one, batch))
     steps = args.steps or 20
     warmup = args.warmup if args.warmup is not None else 3
     dt, ev_ms = timed_steps(world, step, steps, warmup)
-    outs = step()
+    torch.cuda.synchronize()
+    outs = last['outs']
     in_bytes = float(sum(len(b) for b in batch))
     out_bytes = float(sum(o.numel() for o in outs))
     alg = in_bytes + out_bytes                          # compressed bytes in, RGB bytes out (intermediate coefficients are the decoder's own)
@@ -551,6 +640,8 @@ def stage_decode(args, world, rank):
                                   'launches + the write pass; one wave per SIMD, ~1500 cycles per symbol) set the time, not HBM; '
                                   'algorithmic bytes = compressed bytes in + RGB bytes out'),
                extra=dict(compressed_mb_per_step=in_bytes / 1e6, rgb_mb_per_step=out_bytes / 1e6, loader_threads=4))
+    if rank == 0 and args.dump_outputs:
+        res['outputs'] = {'decoded_%02d' % i: o.cpu().numpy() for i, o in enumerate(outs)}
     if rank == 0 and not args.no_verify:
         from PIL import Image
         ok = all(np.array_equal(o.cpu().numpy(), np.asarray(Image.open(io.BytesIO(b)).convert('RGB'))) for o, b in zip(outs[:5], batch[:5]))
@@ -601,6 +692,8 @@ def main():
         from waymo_2d_tracking_amd import bench_e2e
         res, steps, warmup = bench_e2e.run_train(args, world, rank, timed_steps)
         det = res.pop('model')
+        if rank == 0 and args.dump_outputs:
+            res['outputs'] = train_outputs(det, res['extra']['loss'])
         if rank == 0 and world == 1 and not args.no_cpu_baseline:       # the CPU baseline is timed at N = 1 only
             res['cpu_baseline'] = cpu_baseline_train(det)
         metric = 'training images/sec (fwd+bwd+step), Cascade R-CNN X152 dconv, 886x1280 crops'
@@ -608,6 +701,8 @@ def main():
         from waymo_2d_tracking_amd import bench_e2e
         res, steps, warmup = bench_e2e.run(args, world, rank, timed_steps)
         pipe = res.pop('pipeline')
+        if rank == 0 and args.dump_outputs:
+            res['outputs'] = e2e_outputs(pipe, args.stage == 'e2e')
         if rank == 0 and args.stage == 'e2e' and not args.no_verify:
             # checker, outside the timed region: every detection the resident trackers consumed during this segment
             # (warm-up and timed steps) replayed through the CPU oracle, rows / ids / boxes compared
@@ -619,6 +714,9 @@ def main():
             res['cpu_baseline'] = cpu_baseline_e2e(pipe, args.stage == 'e2e')
         metric = 'end-to-end frames/sec (detect+SORT) on 1920x1280 Waymo frames' if args.stage == 'e2e' else \
             'detector frames/sec on 1920x1280 Waymo frames'
+    outputs = res.pop('outputs', None)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     ranks_seen = rccl_ranks()
     if _dist_on():
         import torch.distributed as dist

@@ -60,18 +60,10 @@ def medium_cases():
 
 
 def real_world_files(limit=16):
-    """JPEG files that ship with Python packages of this image (matplotlib, scikit-learn, scikit-image, ... sample data): written by
-    other encoders than PIL's - optimised Huffman tables, other quantisation tables, restart intervals, progressive ones.  The GPU box
-    runs the same image, so the same files exist there.  [] if none is found."""
+    """JPEG files written by other encoders than PIL's - optimised Huffman tables, other quantisation tables, a restart interval of 32,
+    an Adobe marker, 2x2 up to 1411x1411 - kept as fixtures under tests/golden/jpeg_other_encoders/ (sources and licences in its
+    SOURCES.txt), so the tests see the same files on every machine."""
     import glob
-    pats = ['/usr/local/lib/python3*/dist-packages/*/datasets/images/*.jpg', '/usr/local/lib/python3*/dist-packages/matplotlib/mpl-data/sample_data/*.jpg',
-            '/opt/conda/lib/python3*/site-packages/skimage/data/*.jpg', '/opt/conda/lib/python3*/site-packages/*/static/images/*.jpg',
-            '/opt/conda/lib/python3*/site-packages/*/static/images/logos/*.jpg', '/opt/conda/lib/python3*/site-packages/nbconvert/tests/files/*.jpeg',
-            '/opt/conda/lib/python3*/site-packages/IPython/core/tests/*.jpg', '/opt/conda/doc/global/template/images/*.jpg',
-            '/usr/share/javascript/highlight.js/styles/*.jpg']
-    out = []
-    for p in pats:
-        for f in sorted(glob.glob(p)):
-            if f not in out:
-                out.append(f)
-    return out[:limit]
+    import os
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'jpeg_other_encoders')
+    return sorted(glob.glob(os.path.join(d, '*.jp*g')))[:limit]

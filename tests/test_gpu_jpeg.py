@@ -98,8 +98,8 @@ def test_image_loader_decodes_jpeg_on_the_gpu(tmp_path):
 
 
 def test_decode_files_written_by_other_encoders():
-    """sample images that ship with the Python packages of the image (matplotlib, scikit-learn, scikit-image ...): other encoders,
-    optimised Huffman tables, a restart interval of 32, sizes up to 1411 x 1411 - bit-exact with PIL; progressive ones are refused"""
+    """sample images of other encoders (matplotlib, scikit-image, nbconvert ... sample data, tests/golden/jpeg_other_encoders/):
+    optimised Huffman tables, a restart interval of 32, sizes up to 1411 x 1411 - bit-exact with PIL; unsupported ones are refused"""
     from waymo_2d_tracking_amd.detnet.nn import ops
     from waymo_2d_tracking_amd._lib import WaymoTrackError
     files = JC.real_world_files()

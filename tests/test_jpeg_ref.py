@@ -121,7 +121,7 @@ def test_header_parse_needs_no_gpu():
 
 
 def test_restatement_on_files_written_by_other_encoders():
-    """sample images shipped with the Python packages of this image (not PIL-encoded): the restatement equals PIL on every
+    """sample images of other encoders (not PIL-encoded, tests/golden/jpeg_other_encoders/): the restatement equals PIL on every
     baseline file (only the smaller ones: the Huffman stage of the restatement is a Python loop)"""
     files = JC.real_world_files()
     if not files:

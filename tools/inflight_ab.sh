@@ -6,7 +6,7 @@ O=gpurun_out/r06_inflight
 mkdir -p $O
 run() {
   name=$1; shift
-  timeout 500 python bench.py "$@" --no-cpu-baseline > $O/$name.json 2> $O/$name.err
+  timeout 500 python bench.py --full "$@" --no-cpu-baseline > $O/$name.json 2> $O/$name.err
   echo "$name rc=$?"
   python - "$O/$name.json" <<'PY'
 import json, sys

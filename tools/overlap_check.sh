@@ -3,7 +3,7 @@
 # sort_streams_kernel interval: how much detector kernel time ran inside it.
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_ov -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-verify > /tmp/ov.json 2>/tmp/ov.log
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_ov -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-verify > /tmp/ov.json 2>/tmp/ov.log
 python3 - "$(find /tmp/prof_ov -name '*kernel_trace.csv' | head -1)" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_sot
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_sot -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline "$@" > /tmp/sot.json 2>/tmp/sot.log
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_sot -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline "$@" > /tmp/sot.json 2>/tmp/sot.log
 python3 - "$(find /tmp/prof_sot -name '*kernel_trace.csv' | head -1)" > $R/gpurun_out/sort_overlap_trace.txt <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))

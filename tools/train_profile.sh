@@ -2,7 +2,7 @@
 # steady-state kernel breakdown of one training step: kernel trace of bench.py --stage train, last steps only
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_tr -- python3 $R/bench.py --stage train --steps 6 --warmup 4 --no-cpu-baseline > /tmp/tr.json 2>/tmp/tr.log
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_tr -- python3 $R/bench.py --full --stage train --steps 6 --warmup 4 --no-cpu-baseline > /tmp/tr.json 2>/tmp/tr.log
 python3 - "$(find /tmp/prof_tr -name '*kernel_trace.csv' | head -1)" > $R/gpurun_out/train_steady.txt <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R"
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
-line() { python3 bench.py --steps "$1" --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | cut -c1-120; }
+line() { python3 bench.py --full --steps "$1" --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | cut -c1-120; }
 mkdir -p gpurun_out
 line 6 > gpurun_out/tune_ab.txt                                                           # packaged selections
 WT_TUNABLEOP_IN= WT_GEMM_TUNING_ONLINE=1 WT_TUNE_MS=${WT_TUNE_MS:-60} WT_TUNE_ITERS=${WT_TUNE_ITERS:-100} WT_TUNABLEOP_OUT=$T/wt_long.csv line 2 >> gpurun_out/tune_ab.txt

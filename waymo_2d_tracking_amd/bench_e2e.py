@@ -556,16 +556,18 @@ def run(args, world, rank, timed_steps):
                                defer_tracking=track and not getattr(args, 'no_defer_track', False), auto_contrast=getattr(args, 'auto_contrast', False))
     steps = args.steps or 3
     warmup = args.warmup if args.warmup is not None else 1
+    full = getattr(args, 'full', False)      # bench.py --full: instrumented frames, roofline, offset sweep, secondary lines
     state = {'n': 0}
-    # Timed steps whose LAST frame is instrumented (launched eagerly with HIP events around every launch).  With two frames in flight that frame runs alone on
+    # --full: timed steps whose LAST frame is instrumented (launched eagerly with HIP events around every launch).  With two frames in flight that frame runs alone on
     # the chip - the other lane drains before it and waits behind it - which costs the step ~3 % (same box: 41.96 / 42.09 frames/s with every step
     # instrumented, 43.20 / 43.22 with two of ten, 43.51 / 43.38 with none): a SAMPLE of the timed region carries the events - one step, two from 8 steps on
     # (71 launches of the roofline shape per frame; the kernel's time does not move by 1 % between frames).  WT_BENCH_INSTRUMENT_STEPS overrides.
-    n_instr = int(os.environ.get('WT_BENCH_INSTRUMENT_STEPS', '2' if steps >= 8 else '1'))
+    # A plain run instruments nothing: every frame replays the captured hipGraph.
+    n_instr = int(os.environ.get('WT_BENCH_INSTRUMENT_STEPS', '2' if steps >= 8 else '1')) if full else 0
 
     def step():
         # HIP-event instrumentation of the dominant hand-written kernel only inside the timed region
-        if state['n'] == warmup:
+        if state['n'] == warmup and full:
             ops.EVENT_LOG = []
         state['n'] += 1
         # the LAST frame of every timed step runs eagerly so that its deform-conv launches carry HIP events (the first frames of a
@@ -615,7 +617,7 @@ def run(args, world, rank, timed_steps):
         deform_roof['all_deformable_launches'] = dict(launches=sum(v[0] for v in deform.values()), tflops=tot_f / tot_s / 1e12,
                                                      frac=tot_f / tot_s / 1e12 / 157.3)
         deform_roof['offset_spread_of_bench_model'] = 'std 0.10 - 0.21 px per layer (random-init offset convs, tools/offset_stats.py)'
-        if rank == 0:
+        if rank == 0 and full:
             deform_roof['by_offset_spread'] = deform_offset_sweep()
     split_roof = None
     if split:
@@ -662,14 +664,15 @@ def run(args, world, rank, timed_steps):
         res['workload'] += ('; 1x1 and dense 3x3 convolutions: f32 operands as exact 3 x bf16 splits, six cross terms on the bf16 matrix cores, f32 accumulate '
                             '(csrc/det_gemm_split.hip; error vs float64 below the f32 library GEMM\'s, profiles/r05_split_gemm_error.txt), everything else fp32')
         res['extra']['split_gemm'] = True
-        if world == 1 and os.environ.get('WT_BENCH_NO_EXACT') != '1':
+        if full and world == 1 and os.environ.get('WT_BENCH_NO_EXACT') != '1':
             res['extra']['exact_f32'] = exact_f32_line(args, rank, track, fps, min(steps, 3))
             if pipe.n_inflight > 1:
                 res['extra']['one_frame_in_flight'] = exact_f32_line(args, rank, track, fps, min(steps, 3), exact=False)
     res['extra']['frames_in_flight'] = pipe.n_inflight
     if pipe.n_inflight > 1:
-        res['workload'] += ('; %d frames in flight (hipGraph lanes on separate streams; the instrumented frame of a step runs alone)' % pipe.n_inflight)
-    if pipe.jpeg is not None:
+        res['workload'] += ('; %d frames in flight (hipGraph lanes on separate streams%s)'
+                            % (pipe.n_inflight, '; the instrumented frame of a step runs alone' if n_instr else ''))
+    if pipe.jpeg is not None and full:
         import io
         from PIL import Image
         pipe._await_decoded(range(pipe.n_times))
@@ -734,8 +737,10 @@ def run_train(args, world, rank, timed_steps):
     from .detnet.nn import ops
     state = {'n': 0}
 
+    full = getattr(args, 'full', False)
+
     def timed():
-        if state['n'] == warmup:
+        if state['n'] == warmup and full:                        # bench.py --full: the roofline below
             ops.EVENT_LOG = []                                   # HIP events around the col2im launches of the timed steps only
         state['n'] += 1
         step()

@@ -236,7 +236,7 @@ class Bottleneck(nn.Module):
             self._packed_v = v
         return self._packed
 
-    def offset_conv(self, x, deform_table=False):
+    def offset_conv(self, x, deform_table=False, stride=1):
         w = self.conv2_offset.weight
         if getattr(self, '_off_w2', None) is None or self._off_w2.device != w.device or self._off_v != w._version:
             self._off_w2 = ops.tap_gemm_weight(w)
@@ -247,7 +247,7 @@ class Bottleneck(nn.Module):
                 w32 = ops.tap_gemm_weight(w, align=32)              # 162 -> 192 rows (zero rows): N % 32 == 0 for the split kernel
                 self._off_split, self._off_split_key = (ops.split_pack_weight(w32), w32.shape[0]), (w.device, w._version)
             split = self._off_split
-        return ops.conv3x3_few(x, self._off_w2, self.conv2_offset.bias, 18, 1, deform_table, split=split)
+        return ops.conv3x3_few(x, self._off_w2, self.conv2_offset.bias, 18, stride, deform_table, split=split)
 
     def forward(self, x, emit_planes=False):
         if isinstance(x, PlanesAct) or emit_planes:
@@ -276,7 +276,9 @@ class Bottleneck(nn.Module):
                 # per-tile fallback kernel, so the round-2 per-layer calibration + host sync is gone)
                 offset, table = self.offset_conv(out, deform_table=True)
             else:
-                offset = self.offset_conv(out) if self.stride == 1 else self.conv2_offset(out)
+                # stride 2 too: MIOpen's solvers for this 18-channel conv accumulate in a run-dependent order (two calls on the same input
+                # differ in the last bits, enough to reorder near-tied detections downstream); the GEMM + gather is deterministic
+                offset = self.offset_conv(out, stride=self.stride)
             out = ops.deform_conv3x3(out, offset, self.packed_weight(), GROUPS, self.stride, 1, self.conv2_scale,
                                      self.conv2_bias, relu=True, table=table)
         else:
@@ -309,7 +311,7 @@ def _bottleneck_forward_planes(self, x, emit_planes):
     if self.stride == 1 and self.conv2_weight.shape[1] in (16, 32):
         offset, table = self.offset_conv(out, deform_table=True)
     else:
-        offset = self.offset_conv(out) if self.stride == 1 else self.conv2_offset(out)
+        offset = self.offset_conv(out, stride=self.stride)
     out = ops.deform_conv3x3(out, offset, self.packed_weight(), GROUPS, self.stride, 1, self.conv2_scale, self.conv2_bias, relu=True, table=table)
     n, c, h, w = out.shape
     m = n * h * w
