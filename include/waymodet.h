@@ -102,6 +102,8 @@ int wd_gemm_split_f32(const float* a, long lda, const void* packed_w, const floa
 int wd_conv_split_f32(const float* x, int batch, int H, int W, int C, const void* packed_w, int ksize, int stride, int pad, const float* bias,
                       const float* residual, float* out, int N, int relu, void* workspace, size_t workspace_bytes, void* stream);
 int wd_gemm_split_supported(const float* a, long lda, const float* bias, const float* residual, const float* out, long ldc, long M, int N, int K);
+/* 1 if wd_conv_split_f32 runs this convolution on position-major tiles (K = 9 C minus the taps in the zero padding), else 0 */
+int wd_conv_split_position_major(int batch, int H, int W, int ksize, int stride, int pad);
 /* Round 6 - activation planes: the A operand of a split-operand GEMM stored PRE-SPLIT by the kernel that produced it, so that the consumer pulls it
  * into LDS with LDS-DMA (global_load_lds_dwordx4) instead of loading f32, splitting on the vector units and writing LDS once per N tile.
  * Layout of an (M, K) activation matrix, K % 32 == 0: [ceil(M / 32) row blocks][K / 32][3 planes: hi, mid, lo][2048 bytes], the 2048 bytes being the

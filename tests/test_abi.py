@@ -104,3 +104,25 @@ def test_product_library_exports_no_laboratory_entry_points(lib):
     from waymo_2d_tracking_amd import build
     dbg = ctypes.CDLL(build.build_debug(verbose=False))
     assert all(hasattr(dbg, n) for n in ('wd_debug_mfma_burn', 'wd_gemm_split_debug_stamps', 'wd_gemm_split_f32'))
+
+
+# Every environment variable the package reads.  A new switch is added here on purpose; a laboratory switch belongs behind
+# experiment_knob() (honoured only with WT_EXPERIMENT=1), and one whose variant lost is deleted together with its code.
+ENV_SWITCHES = sorted([
+    'FVCORE_CACHE', 'HIPCC', 'LOCAL_RANK', 'RANK', 'WAYMO_DETECTRON2_WEIGHTS', 'WORLD_SIZE',
+    'WD_CANARY_BIG', 'WD_DEBUG_BUILD', 'WD_DEBUG_FILL', 'WD_DEFORM_PATCH', 'WD_FUSED_DEFORM_BWD', 'WD_FUSED_DEFORM_DXOFF',
+    'WD_FUSED_DEFORM_EPILOGUE', 'WD_FUSED_DEFORM_S2', 'WD_HIPCC_FLAGS', 'WD_SPLIT_GEMM', 'WD_SPLIT_MT', 'WD_SPLIT_NO_POSMAJOR',
+    'WD_SPLIT_PLANES', 'WD_SPLIT_PLANES_MIN_CH', 'WD_SPLIT_SPLITK', 'WD_SPLIT_TRAIN',
+    'WT_BENCH_INSTRUMENT_STEPS', 'WT_BENCH_NO_EXACT', 'WT_DIST_BACKEND', 'WT_EXPERIMENT', 'WT_GEMM_TUNING_ONLINE', 'WT_LIB_PATH',
+    'WT_SGD_FUSED', 'WT_TUNABLEOP_IN', 'WT_TUNABLEOP_OUT', 'WT_TUNE_ITERS', 'WT_TUNE_MS',
+])
+
+
+def test_environment_switches_are_the_listed_ones():
+    pat = re.compile(r'''\b(?:getenv|experiment_knob)\("([A-Za-z0-9_]+)"\)|\bos\.environ\.get\(['"]([A-Za-z0-9_]+)['"]''')
+    found = set()
+    for d, _, files in os.walk(os.path.join(ROOT, 'waymo_2d_tracking_amd')):
+        for f in files:
+            if f.endswith(('.py', '.hip', '.h', '.cpp')):
+                found.update(a or b for a, b in pat.findall(open(os.path.join(d, f), errors='replace').read()))
+    assert sorted(found) == ENV_SWITCHES

@@ -1,4 +1,5 @@
-"""EXPLORATORY: the res4 deformable conv as three bf16 MFMAs per tile and tap (2-way bfloat16 split of weights and
+"""ARCHIVED (round 7): WD_DEFORM_BF16X3 and the bf16x3 kernel left the library; this script works at commit 2acf2f1.
+EXPLORATORY: the res4 deformable conv as three bf16 MFMAs per tile and tap (2-way bfloat16 split of weights and
 samples, f32 accumulation) instead of sixteen f32 MFMAs.  NOT fp32 (about 16 mantissa bits per operand): never the benchmarked value.
 Reports (a) kernel time and output error against the fp32 kernel, (b) the drift of the detector's end boxes / scores on synthetic
 frames when all 35 res4 layers run in that mode.  Each mode runs in its own process (the switch is read once per process).

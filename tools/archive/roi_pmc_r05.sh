@@ -1,4 +1,5 @@
 #!/bin/bash
+# ARCHIVED (round 7): WD_ROI_KERNEL / WD_ROI_ORDER left the library with the kernels they selected; this script works at commit 2acf2f1.
 # memory-side counters of the ROIAlign kernels on the cold roofline set (tools only).  usage: roi_pmc.sh "name|lib-or-empty|KERNEL|ORDER" ...
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}

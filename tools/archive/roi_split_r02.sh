@@ -1,4 +1,5 @@
 #!/bin/bash
+# ARCHIVED (round 7): WD_ROI_ORDER and the row kernel left the library with the kernels they selected; this script works at commit 2acf2f1.
 # per-kernel split of one wd_roi_pool_fpn_f32 call (row kernel / ordering / fallback), both processing orders -> stdout
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}

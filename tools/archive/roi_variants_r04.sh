@@ -1,4 +1,5 @@
 #!/bin/bash
+# ARCHIVED (round 7): WD_ROI_KERNEL / WD_ROI_ORDER left the library with the kernels they selected; this script works at commit 2acf2f1.
 # ROIAlign kernels side by side (tools only).  usage: roi_variants.sh "name|lib-or-empty|KERNEL|ORDER" ...
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/roi_variants.txt

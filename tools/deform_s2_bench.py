@@ -1,5 +1,5 @@
 """Stride-2 deformable layers (first blocks of res3 / res4 / res5) through wd_deform_conv3x3_f32: time, fraction of the f32 MFMA peak,
-agreement with the round-1 gather kernel.   WD_PP_S2=narrow python tools/deform_s2_bench.py  = the round-3 routing (14 x 14 patches)"""
+agreement with the round-1 gather kernel."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

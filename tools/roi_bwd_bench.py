@@ -1,5 +1,4 @@
-"""ROIAlign backward at the training shape (512 sampled ROIs, 256 channels, 4 FPN levels of an 886 x 1280 crop), HIP-event timed (tools only).
-WD_ROI_BWD=sample selects the per-sample kernel."""
+"""ROIAlign backward at the training shape (512 sampled ROIs, 256 channels, 4 FPN levels of an 886 x 1280 crop), HIP-event timed (tools only)."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

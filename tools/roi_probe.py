@@ -1,4 +1,4 @@
-"""What bounds roi_pool_row_kernel?  (tools only)  Same 1000-ROI call with (a) the benchmark's random ROIs, (b) 1000 copies of ONE ROI
+"""What bounds the ROIAlign forward (round 2: roi_pool_row_kernel)?  (tools only)  Same 1000-ROI call with (a) the benchmark's random ROIs, (b) 1000 copies of ONE ROI
 (every feature byte after the first touch is a cache hit), (c) random positions but all on one level / one size."""
 import os
 import sys

@@ -8,7 +8,6 @@
 // Forward-speed kernels stay in det_deform.hip / det_roialign.hip; these favour simplicity and exactness.
 #include "common.h"
 #include <cstdlib>
-#include <cstring>
 #include "../../include/waymodet.h"
 
 namespace {
@@ -33,7 +32,7 @@ __device__ __forceinline__ bool roi_axis_sample(float y, int size, int& lo, int&
     return true;
 }
 
-// The per-sample form (4 atomics per sample and channel): ROIs whose footprint exceeds the separable kernel's tables, and WD_ROI_BWD=sample.
+// The per-sample form (4 atomics per sample and channel): ROIs whose footprint exceeds the separable kernel's tables, and pooled sizes other than 7.
 __device__ void roi_bwd_samples(float* __restrict__ grad, int H, int W, int C, const float* __restrict__ g0, int P, float rsh, float rsw,
                                 float bin_h, float bin_w, int gh, int gw, float count, int lane, int wave) {
     for (int cb = wave * 64; cb < C; cb += 256) {
@@ -434,11 +433,8 @@ int wd_roi_pool_fpn_bwd_f32(float* const* grad_feats, const int32_t* heights, co
     if (n_rois <= 0) return WT_OK;
     LevelsW lv;
     for (int i = 0; i < n_levels; ++i) { lv.grad[i] = grad_feats[i]; lv.h[i] = heights[i]; lv.w[i] = widths[i]; lv.scale[i] = scales[i]; }
-    const char* mode = getenv("WD_ROI_BWD");                 // experiments: "sample" = 4 atomics per sample (the round-1 kernel)
-    int split = 4;
-    if (const char* e = getenv("WD_ROI_BWD_SPLIT")) split = atoi(e);
-    if (split < 1) split = 1;
-    if (pooled == 7 && !(mode && strcmp(mode, "sample") == 0))
+    constexpr int split = 4;
+    if (pooled == 7)
         hipLaunchKernelGGL(roi_pool_fpn_bwd_kernel<7>, dim3((unsigned)(n_rois * split)), dim3(256), 0, (hipStream_t)stream, lv, n_levels, channels,
                            batch, rois, pooled, min_level, canonical_level, canonical_size, grad_out, split);
     else
@@ -478,8 +474,7 @@ int wd_deform_col2im_f32(const float* dcol, const float* x, const float* offset,
     const long npix = (long)batch * ho * wo;
     const long total = npix * 9 * (c / 4);
     const long blocks = (total + 255) / 256;
-    const char* mode = getenv("WD_COL2IM");                 // experiments: "atomic" = one global atomic per corner value
-    if ((stride == 1 || stride == 2) && pad == 1 && !(mode && strcmp(mode, "atomic") == 0)) {
+    if ((stride == 1 || stride == 2) && pad == 1) {
         // doffset (gather + channel reduction) and dx (inverted sampling table, gather) as two kernels
         hipLaunchKernelGGL(deform_col2im_kernel<false>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
                            (hipStream_t)stream, dcol, x, offset, npix, ho, wo, h, w, c, c / groups, stride, pad, dx, doffset);

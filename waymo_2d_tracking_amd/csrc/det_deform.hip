@@ -842,12 +842,9 @@ int wd_deform_conv3x3_tab_f32(const float* x, const float* offset, const float* 
     // (16 / 32 channels per group: register-fragment kernel, 64: shared-slab patch kernel); stride 2, plain grouped
     // convolution and 8 channels per group -> L1-gather kernel.  WD_DEFORM_PATCH=lds|all|none overrides (experiments).
     const char* mode = getenv("WD_DEFORM_PATCH");
-    // res2: plain grouped conv with 8 channels per group -> vector-unit kernel (det_gconv.hip); WD_GCONV=mfma keeps the MFMA path
-    if (!offset && !mask && cg == 8 && stride == 1 && pad == 1 && (c_in % 128) == 0 && ((uintptr_t)y & 7) == 0) {
-        const char* gm = getenv("WD_GCONV");
-        if (!(gm && strcmp(gm, "mfma") == 0))
-            return wd_grouped_conv3x3_c8_launch(x, packed_weight, scale, bias, relu, batch, h, w, c_in, stream, y);
-    }
+    // res2: plain grouped conv with 8 channels per group -> vector-unit kernel (det_gconv.hip)
+    if (!offset && !mask && cg == 8 && stride == 1 && pad == 1 && (c_in % 128) == 0 && ((uintptr_t)y & 7) == 0)
+        return wd_grouped_conv3x3_c8_launch(x, packed_weight, scale, bias, relu, batch, h, w, c_in, stream, y);
     int variant = deform_variant(cg, stride, pad, offset != nullptr, mode);
     if (variant == 3 && stride != 1 && mask) variant = 0;    // stride 2 + modulation mask: the gather kernel
     if (variant == 3 && stride == 1 && (mask || far_offsets)) variant = 2;  // the ping-pong kernel has no modulation mask; with many samples leaving

@@ -813,7 +813,6 @@ int geo_tiles(const Geo& g, int batch) { return batch * ((g.Ho + 7) / 8) * ((g.W
 int fused_dw_slices(int ntiles, int groups, int cg) {
     const int target = (cg == 32 ? 4 : 6) * 256;
     int per_wg = (int)(((long)ntiles * groups + target - 1) / target);
-    if (const char* e = getenv("WD_DW_TILES_PER_WG")) per_wg = atoi(e);
     if (per_wg < 1) per_wg = 1;
     return (ntiles + per_wg - 1) / per_wg;
 }
@@ -875,13 +874,10 @@ int wd_deform_dxoff_f32(const float* x, const float* offset, const float* dy, co
     const int dev = wt::device_index();
     if (cus <= 0) { wt::set_error("wd_deform_dxoff_f32: cannot read the device properties"); return WT_ERR_HIP; }
     int nwg = 2 * cus;                                       // two workgroups (77 KB of LDS, 6 waves each) per CU, all resident
-    if (const char* e = getenv("WD_DXOFF_WGS")) nwg = atoi(e);
     if (nwg > items) nwg = items;
     if (nwg < 1) nwg = 1;
-    int far_chunks = 32;                                     // group chunks of the far-sample kernel (workgroups of tiles without such samples exit at once)
-    if (const char* e = getenv("WD_FAR_CHUNKS")) far_chunks = atoi(e);
-    if (far_chunks < 1) far_chunks = 1;
-    if (far_chunks > groups) far_chunks = groups;
+    constexpr int kFarChunks = 32;                           // group chunks of the far-sample kernel (workgroups of tiles without such samples exit at once)
+    const int far_chunks = kFarChunks < groups ? kFarChunks : groups;
     const int naux = 4 * cus;                                // blocks that zero dX and pack the weights, in the launch that builds the tables
     if (cg == 32) {
         if (attr32.needed(dev)) {

@@ -39,7 +39,6 @@ namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 #ifndef PP_SPLIT32
 #define PP_SPLIT32 0
@@ -58,10 +57,8 @@ constexpr unsigned FAR_Y = 0xFFFFFFFFu;    // entry.y of a sample whose corners 
 #endif
 constexpr int RW = PP_RES_TAPS;
 template <int CG> constexpr int tap_floats() { return (CG == 32 ? 4 : 2) * 64 * 4; }     // weights of one tap of an item
-constexpr int PS_WIDE = 21;            // stride 2: 17 x 17 footprint of the undeformed taps of an 8 x 8 output tile + the same 2-pixel halo
-template <int CG, int PSIDE = PS, int NT = 2> constexpr size_t smem_bytes() {
-    return (size_t)(9 - RW) * tap_floats<CG>() * 4 + 2 * NT * (size_t)((PSIDE * PSIDE + 1) * CH * 4) + 2 * NT * (size_t)TAB_B;
-}
+constexpr int NT = 2;                  // teams (4 waves, one tile each) per workgroup
+template <int CG> constexpr size_t smem_bytes() { return (size_t)(9 - RW) * tap_floats<CG>() * 4 + 2 * NT * (size_t)PATCH_B + 2 * NT * (size_t)TAB_B; }
 }  // namespace pp
 
 // Workgroup barrier without the fence of __syncthreads() (the fence would make every wave wait for its outstanding LDS reads)
@@ -73,15 +70,6 @@ template <int CG, int PSIDE = PS, int NT = 2> constexpr size_t smem_bytes() {
 // slot boundary: the "memory" clobber keeps LLVM's IR passes from sinking the LDS loads to their uses behind the MFMA burst, the
 // sched_barrier keeps the machine scheduler from moving anything across
 #define PP_SLOT() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-
-// EXPLORATORY (bf16x3 mode, never the benchmarked path): v = hi + lo + O(2^-16 |v|) with hi, lo in bfloat16
-__device__ __forceinline__ void pp_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        hi[i] = (__bf16)v[i];
-        lo[i] = (__bf16)(v[i] - (float)hi[i]);
-    }
-}
 
 // fragment row r (0..15) of M tile m -> pixel (y, x) of the 8x8 tile (see header: even columns on rows {0-3, 12-15})
 __device__ __forceinline__ int pp_row_pixel(int r, int m) {
@@ -103,13 +91,13 @@ __device__ __forceinline__ int pp_slot(int p, int q) { return (p << 3) + (q ^ ((
 // Stride S (1 or 2): the patch origin is image pixel (S * 8 ty - org, S * 8 tx - org) with org = 3 for stride 1 (2-pixel halo around the
 // 10 x 10 footprint of undeformed taps) and org = -1 for stride 2: there the undeformed footprint is 17 x 17, the 14 x 14 patch holds its
 // middle rows / columns 1 .. 14 and the rest (about a third of the samples) takes the far path - still 2 - 3 x faster than the gather kernel.
-// round 4: stride 2 gets its own instantiation with 21 x 21 patches (one team, one wave per SIMD: the patches take the LDS of the second team):
-// origin 3 like stride 1, no sample of an undeformed tap leaves the patch.
-__device__ __forceinline__ int pp_origin(int stride, int ps) { return (stride == 1 || ps == pp::PS_WIDE) ? 3 : -1; }
+// (21 x 21 stride-2 patches with one team per workgroup were measured no faster in round 4: profiles/r04_deform_stride2.txt.)
+__device__ __forceinline__ int pp_origin(int stride) { return stride == 1 ? 3 : -1; }
 
 __device__ __forceinline__ uint4 pp_make_entry(bool pixel_in_image, int yy, int xx, int kh, int kw, float2 ov, int ty, int tx, int H, int W,
-                                               int stride, int ps) {
-    const int org = pp_origin(stride, ps);
+                                               int stride) {
+    constexpr int ps = pp::PS;
+    const int org = pp_origin(stride);
     const float t_fy = (float)(stride * yy + kh - 1 + org), t_fx = (float)(stride * xx + kw - 1 + org);   // undeformed sample, patch coordinates
     const float py0 = (float)(ty * 8 * stride - org), px0 = (float)(tx * 8 * stride - org);
     const float fH = (float)H, fW = (float)W;
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(576) void deform_offsets_table_kernel(const float* 
             ov = make_float2(a0, a1);
             *reinterpret_cast<float2*>(offsets + (((size_t)tn * H + oy) * W + ox) * 18 + 2 * k) = ov;
         }
-        const uint4 ent = pp_make_entry(in, yy, xx, kh, kw, ov, ty, tx, H, W, 1, pp::PS);
+        const uint4 ent = pp_make_entry(in, yy, xx, kh, kw, ov, ty, tx, H, W, 1);
         table[(size_t)t * pp::NE + e] = ent;
         pp_tile_flag(ent.y == pp::FAR_Y, t, ntiles, table);
     }
@@ -193,7 +181,7 @@ __global__ __launch_bounds__(576) void deform_offsets_table_kernel(const float* 
 // The same table from an offsets tensor (N, H, W, 18) that already exists (callers without the fused pre-pass).
 // H, W: the OUTPUT grid (tiles, offsets); Hin, Win: the sampled image (== H, W at stride 1).
 __global__ __launch_bounds__(576) void deform_table_kernel(const float* __restrict__ offsets, int batch, int Hin, int Win, int H, int W,
-                                                          int stride, int ps, uint4* __restrict__ table) {
+                                                          int stride, uint4* __restrict__ table) {
     const int tiles_x = (W + 7) >> 3, tiles_y = (H + 7) >> 3;
     const int ntiles = batch * tiles_y * tiles_x;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -208,27 +196,23 @@ __global__ __launch_bounds__(576) void deform_table_kernel(const float* __restri
         const bool in = oy < H && ox < W;
         float2 ov = make_float2(0.f, 0.f);
         if (in) ov = *reinterpret_cast<const float2*>(offsets + (((size_t)tn * H + oy) * W + ox) * 18 + 2 * k);
-        const uint4 ent = pp_make_entry(in, yy, xx, kh, kw, ov, ty, tx, Hin, Win, stride, ps);
+        const uint4 ent = pp_make_entry(in, yy, xx, kh, kw, ov, ty, tx, Hin, Win, stride);
         table[(size_t)t * pp::NE + e] = ent;
         pp_tile_flag(ent.y == pp::FAR_Y, t, ntiles, table);
     }
 }
 
-// BF3 (exploratory, 32 channels per group only): the implicit GEMM as three bf16 MFMAs per 16-channel tile and tap (hi.hi + hi.lo + lo.hi of a
-// 2-way bfloat16 split of weights and samples, f32 accumulation) on the bf16 matrix pipe - 6 x ~17 cycles instead of 16 x 32, and that pipe
-// overlaps with VALU.  About 16 mantissa bits per operand: NOT fp32; measured and reported as an `extra` only (tools/bf16x3_experiment.py).
-template <int CG, bool BF3 = false, int PSIDE = pp::PS, int NT = 2>
-__global__ __launch_bounds__(256 * NT, NT) __attribute__((amdgpu_waves_per_eu(NT, NT))) void deform_conv3x3_pp_kernel(
+template <int CG>
+__global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_per_eu(pp::NT, pp::NT))) void deform_conv3x3_pp_kernel(
     const float* __restrict__ x, const float* __restrict__ wfrag, const float* __restrict__ scale, const float* __restrict__ bias,
     int relu, int batch, int H, int W, int Ho, int Wo, int stride, int C, int Cout, int nsplit, float* __restrict__ y,
     const uint4* __restrict__ table) {
     // H, W: the sampled image; Ho, Wo: the output grid (== H, W at stride 1); stride 1 or 2 (pp_origin)
     static_assert(CG == 32 || CG == 16, "32 channels per group, or two groups of 16 per item");
-    static_assert(!BF3 || CG == 32, "the bf16x3 experiment exists for 32 channels per group only");
     constexpr int NQ = CG == 32 ? 4 : 2;                     // float4 weight fragments per lane and tap
-    constexpr int RW = pp::RW;
-    constexpr int PS = PSIDE, NPIX = PS * PS;                // patch side / pixels (+ pixel NPIX = zeros)
-    constexpr int PATCH_F = (NPIX + 1) * pp::CH, PATCH_B = PATCH_F * 4;
+    constexpr int RW = pp::RW, NT = pp::NT;
+    constexpr int PS = pp::PS, NPIX = pp::NPIX;              // patch side / pixels (+ pixel NPIX = zeros)
+    constexpr int PATCH_F = pp::PATCH_F, PATCH_B = pp::PATCH_B;
     constexpr int NPC = (NPIX * 8 + 255) / 256;              // LDS-DMA pieces (64 slots of 16 bytes) per wave and patch
     static_assert((NPIX + 1) * 8 * 16 <= 65536, "corner byte offsets are 16 bits");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -241,7 +225,7 @@ __global__ __launch_bounds__(256 * NT, NT) __attribute__((amdgpu_waves_per_eu(NT
     const int r16 = lane & 15, kq = lane >> 4;
     const int tiles_x = (Wo + 7) >> 3, tiles_y = (Ho + 7) >> 3;
     const int ntiles = batch * tiles_y * tiles_x;
-    const int org = pp_origin(stride, PS), tstep = 8 * stride;                                 // patch origin = tile * tstep - org
+    const int org = pp_origin(stride), tstep = 8 * stride;                                 // patch origin = tile * tstep - org
     const int g = blockIdx.x / nsplit, sidx = blockIdx.x - g * nsplit;                     // g = item (32 channels)
     // contiguous tile range of this workgroup
     const int tq = ntiles / nsplit, trm = ntiles - tq * nsplit;
@@ -345,28 +329,7 @@ __global__ __launch_bounds__(256 * NT, NT) __attribute__((amdgpu_waves_per_eu(NT
     {
         // wfrag (pack_weight_kernel's fragment copy): CG 32: [group][tap][lane][16]; CG 16: [group][tap][lane][4], an item = groups 2g, 2g+1
         // -> bw[tap - RW][q][lane][4]
-        if constexpr (CG == 32 && BF3) {
-            // per (tap, lane): the 16 weights [tile][k] -> 4 x 16 bytes [tile 0 hi | tile 0 lo | tile 1 hi | tile 1 lo] (8 bf16 each)
-            const float* src = wfrag + (size_t)g * 9 * 64 * 16;
-            auto split_tap = [&](int k, int ln, f32x4 (&dst)[4]) {
-                float v0[8], v1[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { v0[i] = src[(k * 64 + ln) * 16 + i]; v1[i] = src[(k * 64 + ln) * 16 + 8 + i]; }
-                bf16x8 h0, l0, h1, l1;
-                pp_split8(v0, h0, l0); pp_split8(v1, h1, l1);
-                dst[0] = __builtin_bit_cast(f32x4, h0); dst[1] = __builtin_bit_cast(f32x4, l0);
-                dst[2] = __builtin_bit_cast(f32x4, h1); dst[3] = __builtin_bit_cast(f32x4, l1);
-            };
-            for (int e = tid; e < (9 - RW) * 64; e += 256 * NT) {
-                const int ln = e & 63, k = e >> 6;
-                f32x4 d[4];
-                split_tap(k + RW, ln, d);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(bw + ((k * 4 + j) * 64 + ln) * 4) = d[j];
-            }
-#pragma unroll
-            for (int k = 0; k < RW; ++k) split_tap(k, lane, wres[k]);
-        } else if constexpr (CG == 32) {
+        if constexpr (CG == 32) {
             const f32x4* src = reinterpret_cast<const f32x4*>(wfrag + (size_t)g * 9 * 64 * 16);
             for (int e = tid; e < (9 - RW) * 64 * 4; e += 256 * NT) {
                 const int j = e & 3, ln = (e >> 2) & 63, k = e >> 8;
@@ -516,18 +479,7 @@ __global__ __launch_bounds__(256 * NT, NT) __attribute__((amdgpu_waves_per_eu(NT
         return;
 #endif
 #define PP_MM(ch, t, wa, av) acc[2 * (ch) + (t)] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa, av, acc[2 * (ch) + (t)], 0, 0, 0);
-        if constexpr (CG == 32 && BF3) {
-            bf16x8 xh, xl;
-            pp_split8(a, xh, xl);
-            const bf16x8 w0h = __builtin_bit_cast(bf16x8, bb[0]), w0l = __builtin_bit_cast(bf16x8, bb[1]);
-            const bf16x8 w1h = __builtin_bit_cast(bf16x8, bb[2]), w1l = __builtin_bit_cast(bf16x8, bb[3]);
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0h, xh, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1h, xh, acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0h, xl, acc[2], 0, 0, 0);
-            acc[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1h, xl, acc[3], 0, 0, 0);
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0l, xh, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1l, xh, acc[1], 0, 0, 0);
-        } else if constexpr (CG == 32) {
+        if constexpr (CG == 32) {
             // k-step kk: channels 8 kq + kk of the lane's pixel; output tiles 0 / 1 = channels 0-15 / 16-31 of the group
             PP_MM(0, 0, bb[0].x, a[0]) PP_MM(0, 1, bb[2].x, a[0]) PP_MM(1, 0, bb[0].y, a[1]) PP_MM(1, 1, bb[2].y, a[1])
             PP_MM(0, 0, bb[0].z, a[2]) PP_MM(0, 1, bb[2].z, a[2]) PP_MM(1, 0, bb[0].w, a[3]) PP_MM(1, 1, bb[2].w, a[3])
@@ -692,64 +644,27 @@ int wd_deform_pp_launch(const float* x, const float* offset, const float* packed
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::smem_bytes<32>()));
         WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deform_conv3x3_pp_kernel<16>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::smem_bytes<16>()));
-        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deform_conv3x3_pp_kernel<32, false, pp::PS_WIDE, 1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::smem_bytes<32, pp::PS_WIDE, 1>()));
-        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deform_conv3x3_pp_kernel<16, false, pp::PS_WIDE, 1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::smem_bytes<16, pp::PS_WIDE, 1>()));
         attr.mark(dev);
     }
     const int ho = (h + 2 - 3) / stride + 1, wo = (w + 2 - 3) / stride + 1;
     const int items = c / pp::CH;
     const int ntiles = batch * ((ho + 7) / 8) * ((wo + 7) / 8);
-    // stride 2, WD_PP_S2=wide: 21 x 21 patches (no sample of an undeformed tap leaves the patch), one team per workgroup - the patches take
-    // the LDS of the second team.  Measured on MI355X (tools/deform_s2_bench.py, profiles/r04_deform_stride2.txt): res3 205 vs 229 us at
-    // 0.2 px but 261 vs 230 us at 2 px, res4 109 vs 108 / 132 vs 112 us: one wave per SIMD costs what the far path costs -> the default
-    // stays the two-team kernel with 14 x 14 patches placed over the middle of the footprint (pp_origin)
-    static const bool s2_wide = getenv("WD_PP_S2") && getenv("WD_PP_S2")[0] == 'w';
-    const bool wide = stride == 2 && s2_wide;
-    const int teams = wide ? 1 : 2;
     if (!table || stride != 1) {
         void* scratch = nullptr;
         WT_TRY(scratch_table(wd_deform_table_bytes(batch, ho, wo), stream, &scratch));
         hipLaunchKernelGGL(deform_table_kernel, dim3((unsigned)(ntiles < 65535 ? ntiles : 65535)), dim3(pp::NE), 0, stream, offset, batch, h, w,
-                           ho, wo, stride, wide ? pp::PS_WIDE : pp::PS, (uint4*)scratch);
+                           ho, wo, stride, (uint4*)scratch);
         WT_HIP(hipGetLastError());
         table = scratch;
     }
     const int n_cu = wt::device_cus() > 0 ? wt::device_cus() : 256;  // cached per device (the first call is not inside a stream capture)
     int nsplit = n_cu / items;
-    static const int nsplit_env = getenv("WD_PP_NSPLIT") ? atoi(getenv("WD_PP_NSPLIT")) : 0;    // experiments: fewer workgroups per item
-    if (nsplit_env > 0 && nsplit_env < nsplit) nsplit = nsplit_env;
     if (nsplit < 1) nsplit = 1;
-    if (nsplit > (ntiles + teams - 1) / teams) nsplit = (ntiles + teams - 1) / teams;       // at least one tile per team
+    if (nsplit > (ntiles + pp::NT - 1) / pp::NT) nsplit = (ntiles + pp::NT - 1) / pp::NT;   // at least one tile per team
     if (nsplit < 1) nsplit = 1;
     const float* wfrag = packed_weight + (size_t)c * cg * 9;       // lane-major fragment copy (pack_weight_kernel)
-    // EXPERIMENT: not fp32 (see the kernel's header), and as an instruction stream (v_mfma_f32_16x16x32_bf16 with a repeated weight operand) the strongest
-    // co-residency aggressor measured (profiles/r06_costream_victim_side.txt, burner kind 9): honoured only together with WT_EXPERIMENT=1
-    static const bool bf3 = []() {
-        const char *e = getenv("WD_DEFORM_BF16X3"), *x = getenv("WT_EXPERIMENT");
-        if (!(e && e[0] == '1')) return false;
-        if (x && x[0] == '1') return true;
-        fprintf(stderr, "libwaymotrack: WD_DEFORM_BF16X3=1 ignored (laboratory switch; set WT_EXPERIMENT=1 to use it)\n");
-        return false;
-    }();
     const dim3 grid((unsigned)(items * nsplit));
-    if (wide && cg == 32)
-        hipLaunchKernelGGL((deform_conv3x3_pp_kernel<32, false, pp::PS_WIDE, 1>), grid, dim3(256), (pp::smem_bytes<32, pp::PS_WIDE, 1>()), stream, x,
-                           wfrag, scale, bias, relu, batch, h, w, ho, wo, stride, c, c, nsplit, y, (const uint4*)table);
-    else if (wide)
-        hipLaunchKernelGGL((deform_conv3x3_pp_kernel<16, false, pp::PS_WIDE, 1>), grid, dim3(256), (pp::smem_bytes<16, pp::PS_WIDE, 1>()), stream, x,
-                           wfrag, scale, bias, relu, batch, h, w, ho, wo, stride, c, c, nsplit, y, (const uint4*)table);
-    else if (cg == 32 && bf3) {
-        static bool attr3 = false;
-        if (!attr3) {
-            WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deform_conv3x3_pp_kernel<32, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::smem_bytes<32>()));
-            attr3 = true;
-        }
-        hipLaunchKernelGGL((deform_conv3x3_pp_kernel<32, true>), grid, dim3(512), pp::smem_bytes<32>(), stream, x, wfrag, scale, bias, relu,
-                           batch, h, w, ho, wo, stride, c, c, nsplit, y, (const uint4*)table);
-    } else if (cg == 32)
+    if (cg == 32)
         hipLaunchKernelGGL(deform_conv3x3_pp_kernel<32>, grid, dim3(512), pp::smem_bytes<32>(), stream, x, wfrag, scale, bias, relu, batch,
                            h, w, ho, wo, stride, c, c, nsplit, y, (const uint4*)table);
     else

@@ -354,12 +354,11 @@ extern "C" int wd_gemm_nt_f32(const float* A, const float* Bt, const float* bias
         // few tiles and a long K (the box-head FC: 256 tiles, K = 12544): split K so that >= 2 workgroups share a CU and
         // hide each other's LDS latency; partial sums meet in C through f32 atomics, the epilogue runs as a second pass
         // Run-to-run determinism: with TWO slices the result 0 + a + b is the same in either arrival order (f32 addition is
-        // commutative), with more slices the atomic order would matter - so the split is capped at 2 unless
-        // WD_GEMM_SPLITK_MAX (experiments) raises it.
-        static const int splitk_max = []() { const char* e = getenv("WD_GEMM_SPLITK_MAX"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
+        // commutative), with more slices the atomic order would matter - so the split is capped at 2.
+        constexpr int kSplitKMax = 2;
         int splitk = 1;
         if (!residual && (N % 4) == 0 && K >= 2048) {
-            while (tiles * splitk < 512 && splitk * 2 <= splitk_max && K / (splitk * 2) >= 1024) splitk *= 2;
+            while (tiles * splitk < 512 && splitk * 2 <= kSplitKMax && K / (splitk * 2) >= 1024) splitk *= 2;
         }
         if (splitk > 1) WT_HIP(hipMemsetAsync(C, 0, sizeof(float) * (size_t)M * N, stream));
         hipLaunchKernelGGL((gemm_nt_kernel<2, 2>), dim3((unsigned)(tiles * splitk)), dim3(256), 0, stream, A, Bt, bias, residual,
@@ -377,9 +376,9 @@ extern "C" int wd_gemm_nt_f32(const float* A, const float* Bt, const float* bias
 extern "C" size_t wd_gemm_nt_workspace(int M, int N, int K) {
     if (M < 256 || N < 256 || K < 1024 || (N & 3) || (K & 31) || (long)M * K >= (1l << 31) || (long)N * K >= (1l << 31)) return 0;
     const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-    static const int target = []() { const char* e = getenv("WD_GEMM_V2_WGS"); return e ? atoi(e) : 448; }();     // experiments
+    constexpr int kTargetWgs = 448;                  // workgroups the K slices aim for
     int splitk = 1;
-    while (tiles * splitk < target && K / (splitk * 2) >= 512) splitk *= 2;
+    while (tiles * splitk < kTargetWgs && K / (splitk * 2) >= 512) splitk *= 2;
     return (size_t)splitk * M * N * sizeof(float);
 }
 

@@ -62,7 +62,7 @@ struct SplitArgs {
     unsigned char* outp;          // output as activation planes of an (M, N) matrix (the next GEMM's A), or nullptr
     long lda, ldc;                // row strides (floats) of a (plain mode) and of out / residual
     int M, N, K, relu;
-    int tiles_m, tiles_n, xmap;
+    int tiles_m, tiles_n;
     int splitk;                   // K slices per output tile; > 1: raw partial tiles go to part[slice][M][N]
     float* part;
     long long* stamps;            // WD_DEBUG builds: per-workgroup s_memtime stamps (start, main loop, epilogue, end) or nullptr
@@ -292,8 +292,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_split_kernel(const SplitArgs
     // split-K: the slices of one tile are neighbours (same XCD); slice kz covers K steps [k0, k0 + nk)
     const int kz = PM ? 0 : id % p.splitk;
     if (!PM) id /= p.splitk;
-    int tm, tn;
-    if (p.xmap == 0 || PM) { tm = id / p.tiles_n; tn = id - tm * p.tiles_n; } else { tn = id / p.tiles_m; tm = id - tn * p.tiles_m; }
+    const int tm = id / p.tiles_n, tn = id - tm * p.tiles_n;
     int m0 = tm * BM;
     const int n0 = tn * BN;
     const int kc = CONV ? p.C / 32 : 1;           // K steps per tap
@@ -583,8 +582,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_split_planes_kernel(const Sp
 #endif
     const int kz = id % p.splitk;
     id /= p.splitk;
-    int tm, tn;
-    if (p.xmap == 0) { tm = id / p.tiles_n; tn = id - tm * p.tiles_n; } else { tn = id / p.tiles_m; tm = id - tn * p.tiles_m; }
+    const int tm = id / p.tiles_n, tn = id - tm * p.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int nk_all = p.K / 32;
     const int per = (nk_all + p.splitk - 1) / p.splitk;
@@ -849,7 +847,7 @@ __global__ __launch_bounds__(256) void gemm_split_reduce_kernel(const float4* __
     }
 }
 
-// Laboratory switches of this unit (tile height, K slices, tile order) are honoured only when WT_EXPERIMENT=1 is set as well: a product
+// Laboratory switches of this unit (tile height, K slices, position-major tiles) are honoured only when WT_EXPERIMENT=1 is set as well: a product
 // process ignores them - with a warning, because WD_SPLIT_MT=2|3 re-enables a known wrong-answer mode of OTHER kernels (see pick_plan).
 bool experiment_mode() {
     static const bool on = []() { const char* e = getenv("WT_EXPERIMENT"); return e && e[0] == '1'; }();
@@ -969,8 +967,6 @@ int dispatch(SplitArgs& a, void* workspace, size_t workspace_bytes, hipStream_t 
     a.part = pl.splitk > 1 ? (float*)workspace : nullptr;
     a.tiles_m = (a.M + 32 * mt - 1) / (32 * mt);
     a.tiles_n = (a.N + BN - 1) / BN;
-    static const int xmap = experiment_knob("WD_SPLIT_XMAP");
-    a.xmap = xmap;
     int rc;
     switch (mt) {
         case 2: rc = launch<2, MODE>(a, stream); break;
@@ -1008,7 +1004,7 @@ int dispatch_position_major(SplitArgs& a, hipStream_t stream) {
         const double t = work > tile(9) ? work : tile(9);
         if (t < best_t * 0.97) { best_t = t; best = mt; }
     }
-    a.splitk = 1; a.part = nullptr; a.xmap = 0;
+    a.splitk = 1; a.part = nullptr;
     a.tiles_m = a.H * a.W * ((maps + 32 * best - 1) / (32 * best));
     a.tiles_n = (int)tn;
     switch (best) {
@@ -1145,6 +1141,12 @@ int wd_gemm_split_io(const WdSplitIO* io, const void* packed_w, const float* bia
     return io->a ? dispatch<0>(s, workspace, workspace_bytes, (hipStream_t)stream_) : dispatch<2>(s, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
+// many small maps (the box heads: 1000 ROIs x 7 x 7): position-major tiles skip the taps that fall into the zero padding (MODE 3)
+int wd_conv_split_position_major(int batch, int H, int W, int ksize, int stride, int pad) {
+    static const int no_pm = experiment_knob("WD_SPLIT_NO_POSMAJOR");
+    return !no_pm && ksize == 3 && stride == 1 && pad == 1 && H >= 3 && W >= 3 && H * W <= 81 && batch >= 256;
+}
+
 int wd_conv_split_f32(const float* x, int batch, int H, int W, int C, const void* packed_w, int ksize, int stride, int pad, const float* bias,
                       const float* residual, float* out, int N, int relu, void* workspace, size_t workspace_bytes, void* stream_) {
     WT_TRY(wt::ensure_device());
@@ -1160,10 +1162,7 @@ int wd_conv_split_f32(const float* x, int batch, int H, int W, int C, const void
     s.a = x; s.w = (const uint4*)packed_w; s.bias = bias; s.residual = residual; s.out = out;
     s.lda = C; s.ldc = N; s.M = (int)M; s.N = N; s.K = ksize * ksize * C; s.relu = relu;
     s.H = H; s.W = W; s.C = C; s.Ho = Ho; s.Wo = Wo; s.stride = stride; s.pad = pad; s.ksize = ksize;
-    // many small maps (the box heads: 1000 ROIs x 7 x 7): position-major tiles skip the taps that fall into the zero padding (MODE 3)
-    static const int no_pm = experiment_knob("WD_SPLIT_NO_POSMAJOR");
-    if (!no_pm && ksize == 3 && stride == 1 && pad == 1 && H >= 3 && W >= 3 && H * W <= 81 && batch >= 256)
-        return dispatch_position_major(s, (hipStream_t)stream_);
+    if (wd_conv_split_position_major(batch, H, W, ksize, stride, pad)) return dispatch_position_major(s, (hipStream_t)stream_);
     return dispatch<1>(s, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 

@@ -7,7 +7,6 @@
 // Boxes arrive sorted by descending score; groups (FPN level / class) never suppress each other.
 #include "common.h"
 #include <cstdlib>
-#include <cstring>
 #include "../../include/waymodet.h"
 
 namespace {
@@ -280,8 +279,7 @@ int wd_nms_sorted_f32(const float* boxes, const int32_t* idxs, int n, float iou_
     unsigned long long* removed = cv.take<unsigned long long>((size_t)nb + 1);
     unsigned long long* diag_pred = cv.take<unsigned long long>((size_t)n);
     constexpr int kMaxR = 24;                               // column sweep: up to 6144 boxes
-    const char* mode = getenv("WD_NMS_SWEEP");              // experiments: "row" forces the row sweep
-    if (n <= 256 * kMaxR && !(mode && strcmp(mode, "row") == 0)) {
+    if (n <= 256 * kMaxR) {
         hipLaunchKernelGGL(nms_mask_kernel<true>, dim3(nb, nb), dim3(64), 0, stream, (const float4*)boxes, idxs, n, nb,
                            iou_threshold, mask, diag_pred, NmsSegs{});
         hipLaunchKernelGGL(nms_sweep_col_kernel<kMaxR>, dim3(1), dim3(256), (size_t)(nb + 1) * 8, stream, mask, diag_pred, n, nb,

@@ -500,10 +500,8 @@ int run_tracking(int64_t n_dets, const double* x, const double* y, const double*
     WT_HIP(hipMemsetAsync(ws.rcnt, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
     WT_HIP(hipMemsetAsync(ws.rbirths, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
     const unsigned n_trackers = (unsigned)n_streams * (unsigned)C;
-    // helper waves (three more waves per tracker for the data-parallel phases) when every tracker can have a CU to itself anyway;
-    // WT_SORT_HELPERS=0 switches them off (A/B)
-    static const bool helpers_off = getenv("WT_SORT_HELPERS") && getenv("WT_SORT_HELPERS")[0] == '0';
-    const bool helpers = !helpers_off && n_trackers <= 256 && (lds + 15) / 16 * 16 + wtdev::help_lds_bytes() <= (size_t)160 * 1024 - 256;
+    // helper waves (three more waves per tracker for the data-parallel phases) when every tracker can have a CU to itself anyway
+    const bool helpers = n_trackers <= 256 && (lds + 15) / 16 * 16 + wtdev::help_lds_bytes() <= (size_t)160 * 1024 - 256;
     if (helpers) lds = (lds + 15) / 16 * 16 + wtdev::help_lds_bytes();
     if (lds > 48 * 1024)
         WT_HIP(hipFuncSetAttribute(helpers ? reinterpret_cast<const void*>(sort_streams_kernel<true>) : reinterpret_cast<const void*>(sort_streams_kernel<false>),

@@ -10,8 +10,8 @@ init, or a detectron2 / reference checkpoint through weights.load_state_dict_det
 MI355X-first layout: every activation is NHWC (torch.channels_last storage); FrozenBatchNorm is folded into the
 producing op; the hot per-frame ops run in hand-written HIP kernels (detnet/nn/ops.py):
   * the box-head FC 12544 -> 1024 = the hand-written f32-MFMA GEMM (wd_gemm_nt_f32, split-K x2); the 1x1 convolutions
-    (2/3 of the backbone FLOPs) are GEMMs on the NHWC matrix view through hipBLASLt (Conv1x1.USE_LIBRARY_GEMM: the library
-    sustains 100-135 TFLOP/s on these shapes, ahead of the hand-written kernel), residual on the beta term,
+    (2/3 of the backbone FLOPs) are GEMMs on the NHWC matrix view through hipBLASLt (the library sustains 100-135 TFLOP/s on
+    these shapes, ahead of the hand-written kernel), residual on the beta term,
   * the 47 deformable 3x3 convolutions = implicit GEMM with fused FrozenBN + ReLU (wd_deform_conv3x3_f32),
   * ROIPooler over the 4 FPN levels (wd_roi_pool_fpn_f32), RPN / box NMS (wd_nms_sorted_f32).
 Dense 3x3 / 7x7 convolutions and GroupNorm stay on PyTorch-ROCm (MIOpen) - the "Python host carries the graph".
@@ -44,11 +44,8 @@ FUSED_TRAINING_EPILOGUES = True
 SPLIT_GEMM = os.environ.get('WD_SPLIT_GEMM', '1') != '0'
 
 
-_SKIP = set(os.environ.get('WD_SPLIT_SKIP', '').split(','))      # experiments: 'cin-cout-stride-hasresidual' 1x1 shapes kept on the library
-_INPLACE = os.environ.get('WD_SPLIT_INPLACE', '1') != '0'      # experiments: 0 = block outputs in fresh buffers instead of the residual's
-SPLIT_PARTS = set(os.environ.get('WD_SPLIT_PARTS', 'conv1x1,conv3x3,head,fc,offset').split(','))     # experiments: which layer families use the kernel
 # the N-thin GEMM of the 18-channel offset convolution goes to the split kernel from this many rows (res3 at full size; below, the library is as fast)
-OFFSET_SPLIT_MIN_ROWS = int(os.environ.get('WD_OFFSET_SPLIT_MIN_ROWS', '30000'))
+OFFSET_SPLIT_MIN_ROWS = 30000
 
 
 # Round 6, measured and OFF by default (profiles/r06_split_presplit.txt): inside a stage of >= SPLIT_PLANES_MIN_CH channels the block output travels as
@@ -70,8 +67,8 @@ class PlanesAct:
 DECISION_LOG = None
 
 
-def _split_ok(cin, cout, part='conv1x1'):
-    return SPLIT_GEMM and part in SPLIT_PARTS and cin % 64 == 0 and cout % 32 == 0
+def _split_ok(cin, cout):
+    return SPLIT_GEMM and cin % 64 == 0 and cout % 32 == 0
 
 
 class _PackedSplit:
@@ -101,8 +98,6 @@ class Conv1x1(nn.Module):
     Plain library GEMM (hipBLASLt through torch): on MI355X it sustains 100-135 TFLOP/s fp32 on these shapes
     (tools/gemm_bench.py), ahead of the hand-written wd_gemm_nt_f32 which is kept for the box-head FC.  The residual
     rides on the GEMM's beta term (addmm), bias+ReLU on the library epilogue where there is no residual."""
-    USE_LIBRARY_GEMM = True
-    FUSED_RESIDUAL = True
 
     def __init__(self, cin, cout, gen, bn_scale=1.0, bias=False):
         super().__init__()
@@ -114,8 +109,7 @@ class Conv1x1(nn.Module):
         self._split = _PackedSplit()
 
     def forward(self, x, relu=False, residual=None, stride=1):
-        skip = '%d-%d-%d-%d' % (self.weight.shape[1], self.weight.shape[0], stride, 0 if residual is None else 1) in _SKIP
-        if not skip and not torch.is_grad_enabled() and x.is_cuda and _split_ok(self.weight.shape[1], self.weight.shape[0]):
+        if not torch.is_grad_enabled() and x.is_cuda and _split_ok(self.weight.shape[1], self.weight.shape[0]):
             # split-operand kernel: the strided shortcut reads its pixels in place (no gathered copy), the residual is added in the epilogue
             # and the block output lands in the residual's buffer (dead after this block), as on the library path
             pw = self._split.get(self.weight)
@@ -129,7 +123,7 @@ class Conv1x1(nn.Module):
                 r = residual if residual.is_contiguous(memory_format=torch.channels_last) else residual.contiguous(memory_format=torch.channels_last)
                 r = r.permute(0, 2, 3, 1).reshape(n * h * w, cout)
             if ops.gemm_split_ok(a, cout, self.bias, r):           # (alignment / size preconditions: otherwise the library path below)
-                y = ops.gemm_split(a, pw, cout, self.bias, r, relu, out=r if _INPLACE else None)
+                y = ops.gemm_split(a, pw, cout, self.bias, r, relu, out=r)
                 return y.view(n, h, w, cout).permute(0, 3, 1, 2)
         if stride != 1:
             x = x[:, :, ::stride, ::stride].contiguous(memory_format=torch.channels_last)
@@ -147,9 +141,7 @@ class Conv1x1(nn.Module):
                 if relu:
                     y = F.relu(y)
             return y.view(n, h, w, -1).permute(0, 3, 1, 2)
-        if not self.USE_LIBRARY_GEMM:
-            y = ops.gemm_nt(a, self.weight, self.bias, r, relu)
-        elif r is None:
+        if r is None:
             if relu:
                 y = torch._addmm_activation(self.bias, a, self.weight.t(), use_gelu=False)
             else:
@@ -157,7 +149,7 @@ class Conv1x1(nn.Module):
         else:
             # inference: the residual buffer is dead after this block (block input or a fresh shortcut output), so the
             # GEMM accumulates into it in place (beta = 1, C == D) - no copy of the residual into a new output
-            if self.FUSED_RESIDUAL and a.is_contiguous():
+            if a.is_contiguous():
                 # residual on the beta term, folded-BN shift + ReLU on the library epilogue: one launch (wd_gemm_lt_f32)
                 y = ops.gemm_lt(a, self.weight, self.bias, r if r.is_contiguous() else r.contiguous(), relu,
                                 out=r if r.is_contiguous() else None)
@@ -181,7 +173,7 @@ class ConvBN(nn.Module):
 
     def forward(self, x, relu=False):
         if (not torch.is_grad_enabled() and x.is_cuda and self.groups == 1 and self.weight.shape[2] in (1, 3)
-                and _split_ok(self.weight.shape[1], self.weight.shape[0], 'conv3x3')):
+                and _split_ok(self.weight.shape[1], self.weight.shape[0])):
             # dense 3x3 (FPN output convs, RPN conv): implicit GEMM over (tap, channel) on the split-operand kernel, bias + ReLU fused
             return ops.conv_split(x, self._split.get(self.weight), self.weight.shape[0], self.weight.shape[2], self.stride, self.pad,
                                   self.bias, None, relu)
@@ -242,7 +234,7 @@ class Bottleneck(nn.Module):
             self._off_w2 = ops.tap_gemm_weight(w)
             self._off_v = w._version
         split = None
-        if x.shape[0] * x.shape[2] * x.shape[3] >= OFFSET_SPLIT_MIN_ROWS and x.is_cuda and _split_ok(w.shape[1], 32, 'offset'):
+        if x.shape[0] * x.shape[2] * x.shape[3] >= OFFSET_SPLIT_MIN_ROWS and x.is_cuda and _split_ok(w.shape[1], 32):
             if getattr(self, '_off_split', None) is None or self._off_split_key != (w.device, w._version):
                 w32 = ops.tap_gemm_weight(w, align=32)              # 162 -> 192 rows (zero rows): N % 32 == 0 for the split kernel
                 self._off_split, self._off_split_key = (ops.split_pack_weight(w32), w32.shape[0]), (w.device, w._version)
@@ -337,7 +329,7 @@ def _run_stage(stage, x):
     """One res stage; with SPLIT_PLANES (inference, split kernel on, wide stage) the block outputs inside the stage travel as activation planes."""
     blocks = list(stage)
     use = (SPLIT_PLANES and SPLIT_GEMM and not torch.is_grad_enabled() and x.is_cuda and DECISION_LOG is None and len(blocks) > 1
-           and blocks[0].conv3.weight.shape[0] >= SPLIT_PLANES_MIN_CH and blocks[0].deform and 'conv1x1' in SPLIT_PARTS)
+           and blocks[0].conv3.weight.shape[0] >= SPLIT_PLANES_MIN_CH and blocks[0].deform)
     if not use:
         return stage(x)
     for i, blk in enumerate(blocks):
@@ -505,7 +497,7 @@ class BoxHead(nn.Module):
     def forward(self, x):
         train = torch.is_grad_enabled()
         for li, (conv, norm) in enumerate(zip(self.convs, self.norms)):
-            if not train and x.is_cuda and _split_ok(256, 256, 'head'):
+            if not train and x.is_cuda and _split_ok(256, 256):
                 x = ops.conv_split(x, self._split[li].get(conv.weight), 256, 3, 1, 1)
             elif train and ops.SPLIT_TRAIN and x.is_cuda and _split_ok(256, 256) and x.shape[0] > 0:
                 x = ops.ConvSplitFn.apply(x, conv.weight, None, 1, 1, False)
@@ -524,14 +516,14 @@ class BoxHead(nn.Module):
         flat = x.permute(0, 2, 3, 1).reshape(r, -1)           # NHWC flatten, a view
         if train:
             h = F.relu(F.linear(flat, self.fc1_weight, self.fc1_bias))
-        elif x.is_cuda and _split_ok(self.fc1_weight.shape[1], self.fc1_weight.shape[0], 'fc'):
+        elif x.is_cuda and _split_ok(self.fc1_weight.shape[1], self.fc1_weight.shape[0]):
             # 12544 -> 1024 on the split-operand kernel, K cut into slices (32 output tiles would leave 7/8 of the chip idle)
             h = ops.gemm_split(flat if flat.is_contiguous() else flat.contiguous(), self._split_fc.get(self.fc1_weight), self.fc1_weight.shape[0],
                                self.fc1_bias, None, True)
         else:
             h = ops.gemm_nt(flat, self.fc1_weight, self.fc1_bias, None, True)
         nc1 = self.cls_weight.shape[0]
-        if not train and x.is_cuda and nc1 + 4 <= 32 and _split_ok(1024, 32, 'fc'):
+        if not train and x.is_cuda and nc1 + 4 <= 32 and _split_ok(1024, 32):
             # class scores and box deltas as ONE split-operand GEMM on the concatenated (zero-padded to 32 rows) predictor weights: one launch
             # (+ the K-slice sum) instead of two skinny library GEMMs whose split-K kernels accumulate with float atomics - run-to-run
             # identical scores also with other kernels in flight (tests/test_gpu_e2e.py: two pipelines on two streams)

@@ -197,7 +197,7 @@ def gemm_nt(a, bt, bias=None, residual=None, relu=False, out=None):
         residual = residual.contiguous()
     lib = _lib.lib()
     need = int(lib.wd_gemm_nt_workspace(C.c_int(m), C.c_int(n), C.c_int(k)))
-    if need and os.environ.get('WD_GEMM_V1') != '1':       # large shapes (box-head FC): 128x128 tiles, two-pass split-K
+    if need:       # large shapes (box-head FC): 128x128 tiles, two-pass split-K
         ws = torch.empty(need, dtype=torch.uint8, device=a.device)
         _lib.check(lib.wd_gemm_nt_ws_f32(_p(a), _p(bt), _p(bias), _p(residual), C.c_int(1 if relu else 0), C.c_int(m), C.c_int(n),
                                          C.c_int(k), _p(out), _p(ws), C.c_size_t(need), _stream()), 'wd_gemm_nt_ws_f32')
@@ -629,13 +629,14 @@ def conv_split(x, packed, n_out, ksize, stride=1, pad=0, bias=None, residual=Non
                                             C.c_int(pad), _p(bias), _p(residual), _p(out), C.c_int(n_out), C.c_int(1 if relu else 0), _p(ws), C.c_size_t(ws_bytes),
                                             _stream()),
                'wd_conv_split_f32')
-    k_eff = ksize * ksize * c
-    if ksize == 3 and stride == 1 and pad == 1 and h >= 3 and w >= 3 and h * w <= 81 and b >= 256 and os.environ.get('WD_SPLIT_NO_POSMAJOR') != '1':
-        # position-major tiles (csrc/det_gemm_split.hip MODE 3) SKIP the taps in the zero padding: only the walked taps are matrix work that was issued
-        walked = (h - 2) * (w - 2) * 9 + (2 * (h - 2) + 2 * (w - 2)) * 6 + 4 * 4
-        k_eff = k_eff * walked / float(9 * h * w)
-    _split_log_end(ev, 'gemm_split_kernel: %dx%d conv s%d M=%d N=%d K=%d' % (ksize, ksize, stride, b * ho * wo, n_out, ksize * ksize * c), b * ho * wo, n_out,
-                   k_eff)
+    if ev is not None:
+        k_eff = ksize * ksize * c
+        if _lib.lib().wd_conv_split_position_major(C.c_int(b), C.c_int(h), C.c_int(w), C.c_int(ksize), C.c_int(stride), C.c_int(pad)):
+            # position-major tiles (csrc/det_gemm_split.hip MODE 3) SKIP the taps in the zero padding: only the walked taps are matrix work that was issued
+            walked = (h - 2) * (w - 2) * 9 + (2 * (h - 2) + 2 * (w - 2)) * 6 + 4 * 4
+            k_eff = k_eff * walked / float(9 * h * w)
+        _split_log_end(ev, 'gemm_split_kernel: %dx%d conv s%d M=%d N=%d K=%d' % (ksize, ksize, stride, b * ho * wo, n_out, ksize * ksize * c), b * ho * wo,
+                       n_out, k_eff)
     return out
 
 
