@@ -255,6 +255,24 @@ int wt_ensemble_groups_dev(const double* dets5, const int64_t* group_offsets, co
                            double iou_thresh, double soft_nms_cut, double* out5, int64_t* out_counts,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Ensemble of K test-time views of the same frames, slot to slot: the device form of exporting each view
+ * (--tta V --export), detnet/ensemble.py over the K files and reading the result back as tracker slots.
+ *   xywhs        : (K, 5, n_frames * slots) float64 wire rows [x, y, w, h, score] (integer boxes, 5-decimal scores)
+ *   category     : (K, n_frames * slots) int32, 1..n_categories; 0 (or anything outside) = empty slot
+ *   weights      : (K) float64 per-view weights (device)
+ *   method       : 0 weighted fusion, 1 nms, 2 soft_nms
+ * One (frame, category) group equals detnet/ensemble.py step for step: rows view by view in slot order, dropped unless
+ * w > 0, h > 0 and score * weight >= min_score (:31-47); merged as wt_ensemble_groups_dev does with input_sizes = kept rows
+ * per view (:50-58); kept if score > min_score, boxes truncated toward zero, score = numpy round(score, 5) (:59-63).
+ *   out_xywhs    : (5, n_frames * K * slots), out_category (n_frames * K * slots): per frame the groups in ascending
+ *                  category order, then empty slots (category 0, zero rows); out_counts (n_frames) int64 rows per frame.
+ * Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.  1 <= K <= 16. */
+size_t wt_ensemble_slots_workspace(int64_t n_frames, int64_t slots, int k_views, int n_categories, int method);
+int wt_ensemble_slots_dev(const double* xywhs, const int32_t* category, int64_t n_frames, int64_t slots, int k_views,
+                          const double* weights, int n_categories, int method, double iou_thresh, double soft_nms_cut,
+                          double min_score, double* out_xywhs, int32_t* out_category, int64_t* out_counts,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* --- Waymo Open Dataset protobuf emit (csrc/waymo_proto.hip; host code) -----------------------------------
  * metrics.Objects - and with submission != 0 the Submission envelope around it - written straight from columns: replaces
  * the per-object message building of /root/reference/coco_to_waymo.py:16-82 (create_pd_object / create_pb_submission) and

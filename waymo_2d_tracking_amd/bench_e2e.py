@@ -17,7 +17,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from .detnet.ensemble import normalise_weights as normalise_view_weights
 from .detnet.nn import ops
+from .detnet.nn.tta import parse_view
 from .detnet.nn.detectron2_det import Detectron2Det
 from .devpath import StreamingTracker
 from .tuning import enable_gemm_tuning
@@ -41,17 +43,22 @@ def moving_frames(n_cameras, n_times, height, width, seed, device):
 class DetectTrackPipeline(object):
     def __init__(self, n_cameras=5, frames_per_camera=2, height=1280, width=1920, seed=0, device='cuda',
                  iou_threshold=(0.01, 0.01, 1.0, 0.0), score_threshold=(0.0, 0.0, 0.0, 0.0), max_age=2, min_hits=0, tta='',
-                 segment_frames=SEGMENT_FRAMES, distinct_times=16, model=None, use_graph=True, n_inflight=1, deterministic=False, defer_tracking=False, auto_contrast=False):
+                 segment_frames=SEGMENT_FRAMES, distinct_times=16, model=None, use_graph=True, n_inflight=1, deterministic=False, defer_tracking=False, auto_contrast=False,
+                 views=None, view_ensemble=None):
         self.dev = torch.device(device)
         # --tta x1.5,hflip (nn/tta.py:228-267): one pass on the enlarged, flipped image, folded into the pre-processing kernel
-        self.tta_scale, self.tta_hflip = 1.0, False
-        for aug in [a for a in tta.split(',') if a]:
-            if aug.startswith('x'):
-                self.tta_scale *= float(aug[1:])
-            elif aug == 'hflip':
-                self.tta_hflip = True
-            elif aug != 'orig':
-                raise ValueError('bench supports --tta orig / xS / hflip, got %r' % aug)
+        self.tta_scale, self.tta_hflip = parse_view(tta)
+        # views=('orig', 'x1.5,hflip'): every frame goes through one captured detector graph per view and the views' wire slots are
+        # merged on the device (SlotEnsemble: detnet/ensemble.py per (frame, category)) before SORT consumes them
+        self.views = None
+        if views is not None:
+            if tta:
+                raise ValueError('views and tta are exclusive: give the single view as views=(%r,)' % tta)
+            self.views = [parse_view(v) for v in views]
+            if not self.views:
+                raise ValueError('views must name at least one view')
+        self.k_views = len(self.views) if self.views else 1
+        self.slots = SLOTS * self.k_views           # slots per frame the tracker reads (merged: K * 100)
         if deterministic:
             # run-to-run bit-identical library kernels (tests: graph replay == eager launches): MIOpen's deterministic solvers,
             # no find-mode search (its winner may accumulate split-K partial sums with atomics), library-default GEMM picks
@@ -67,14 +74,31 @@ class DetectTrackPipeline(object):
         self.n_times = max(frames_per_camera, (distinct_times // frames_per_camera) * frames_per_camera)
         self.frames = moving_frames(n_cameras, self.n_times, height, width, seed, self.dev)
         self.max_chunks = max(1, segment_frames // frames_per_camera)
-        n = self.n_frames * SLOTS
+        n = self.n_frames * self.slots
         self.chunk_dets = n
         R = self.max_chunks
         f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.dev)
-        # per-chunk detection slots (chunk-major; inside a chunk camera-major frames x 100 slots, category 0 = empty)
+        # per-chunk detection slots (chunk-major; inside a chunk camera-major frames x self.slots slots, category 0 = empty)
         self.xywhs = f64(R, 5, n)                    # x, y, w, h, score rows of every chunk (one strided copy per frame)
         self.x, self.y, self.wd, self.ht, self.score = (self.xywhs[:, q] for q in range(5))
         self.category = torch.zeros((R, n), dtype=torch.int32, device=self.dev)
+        self.ensemble, self.merge_events = None, None
+        if self.views:
+            # each view's 100 slots per frame land in their own (K, 5, frames x 100) block of the chunk; the merge writes self.xywhs
+            from .devpath import SlotEnsemble
+            nv = self.n_frames * SLOTS
+            self.view_xywhs = f64(R, self.k_views, 5, nv)
+            self.view_category = torch.zeros((R, self.k_views, nv), dtype=torch.int32, device=self.dev)
+            self.merge_counts = torch.zeros((R, self.n_frames), dtype=torch.int64, device=self.dev)
+            ve = dict(method='weighted_fusion', iou_thresh=0.5, soft_nms_cut=1.0, min_score=0.0, weights=None)
+            unknown = set(view_ensemble or {}) - set(ve)
+            if unknown:
+                raise ValueError('view_ensemble: unknown keys %s' % sorted(unknown))
+            ve.update(view_ensemble or {})
+            weights = normalise_view_weights(ve['weights'], self.k_views)
+            self.view_ensemble = dict(ve, weights=weights)
+            self.ensemble = SlotEnsemble(self.n_frames, SLOTS, weights, len(iou_threshold), ve['method'], ve['iou_thresh'],
+                                         ve['soft_nms_cut'], ve['min_score'], device=self.dev)
         self.n_dets_dev = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.use_graph, self._graph = use_graph, None
         self.n_inflight, self._lanes, self._frame_no = max(1, n_inflight), [], 0
@@ -91,13 +115,13 @@ class DetectTrackPipeline(object):
         self.out_id = [v['local_id'] for v in views]
         self.chunk_counts = self.rows.counts
         self.collate = False           # exchange birth counts + gather the chunk's rows to rank 0 behind every track() call
-        self.frame_off = (torch.arange(self.n_frames + 1, dtype=torch.int64) * SLOTS).to(self.dev)
+        self.frame_off = (torch.arange(self.n_frames + 1, dtype=torch.int64) * self.slots).to(self.dev)
         self.stream_off = (torch.arange(n_cameras + 1, dtype=torch.int64) * frames_per_camera).to(self.dev)
         self.clip_w = torch.full((n_cameras,), float(width), dtype=torch.float64, device=self.dev)
         self.clip_h = torch.full((n_cameras,), float(height), dtype=torch.float64, device=self.dev)
         self.track_params = dict(iou_threshold=list(iou_threshold), score_threshold=list(score_threshold),
                                  max_age=max_age, min_hits=min_hits)
-        self.tracker = StreamingTracker(n_cameras, SLOTS, self.n_frames, n, list(iou_threshold), max_age, min_hits,
+        self.tracker = StreamingTracker(n_cameras, self.slots, self.n_frames, n, list(iou_threshold), max_age, min_hits,
                                         list(score_threshold), device=self.dev)
         self.track_stream = torch.cuda.Stream(device=self.dev)
         self._slot_done = [None] * R      # per ring slot: event of the track() that last read it
@@ -114,22 +138,53 @@ class DetectTrackPipeline(object):
         """(rows, births) of the most recent chunk (device int64[2])."""
         return self.chunk_counts[max(self.chunk - 1, 0)]
 
-    def _detect_core(self, img):
+    def _detect_core(self, img, view=None):
         """uint8 (1, H, W, 3) frame -> wire-format detections in 100 static slots: (xywhs (5, 100) float64, category (100) int32
-        with 0 = empty slot).  Static shapes, no host synchronisation: capturable as ONE hipGraph."""
+        with 0 = empty slot).  Static shapes, no host synchronisation: capturable as ONE hipGraph.  view: (scale, hflip), default
+        the pipeline's tta."""
+        scale, hflip = view if view is not None else (self.tta_scale, self.tta_hflip)
         if self.auto_contrast:
             img = ops.autocontrast_(img[0].clone()).unsqueeze(0)
-        boxes, scores, classes, cnt = self.model.predict_padded(img, self.tta_scale, self.tta_hflip)
+        boxes, scores, classes, cnt = self.model.predict_padded(img, scale, hflip)
         ho, wo = self.model.last_input_size
         # HFlipTTA.post_process + Detectron2Det.predict + load_prediction in one launch; unused slots: category 0 = ignored
-        xywhs, cat = ops.detections_to_wire(boxes, scores, classes, cnt, wo, ho, self.w, self.h, self.tta_hflip)
+        xywhs, cat = ops.detections_to_wire(boxes, scores, classes, cnt, wo, ho, self.w, self.h, hflip)
         return xywhs, cat, cnt
 
-    def _detect_heads(self, feats):
+    def _detect_heads(self, feats, hflip=None):
         boxes, scores, classes, cnt = self.model.predict_padded_heads(feats)
         ho, wo = self.model.last_input_size
-        xywhs, cat = ops.detections_to_wire(boxes, scores, classes, cnt, wo, ho, self.w, self.h, self.tta_hflip)
+        xywhs, cat = ops.detections_to_wire(boxes, scores, classes, cnt, wo, ho, self.w, self.h,
+                                            self.tta_hflip if hflip is None else hflip)
         return xywhs, cat, cnt
+
+    def _capture_views(self, lane):
+        """views: one captured detector graph per view (two with defer_tracking), scale and flips baked in.  A lane's graphs share
+        one memory pool: they replay one after the other on the lane's stream, in the order they were captured."""
+        with torch.cuda.stream(lane['stream']), torch.no_grad():
+            for t in range(3):
+                lane['gin'].copy_(self.frames[t % self.n_times, 0].unsqueeze(0))
+                for v in self.views:
+                    self._detect_core(lane['gin'], v)
+        lane['stream'].synchronize()
+        lane['vgraphs'], lane['vgraphs_b'], lane['vfeats'], lane['vgout'] = [], [], [], []
+        pool = None
+        for scale, hflip in self.views:
+            g = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(g, stream=lane['stream'], pool=pool, capture_error_mode='thread_local'):
+                if self.defer_tracking:
+                    gin = ops.autocontrast_(lane['gin'][0].clone()).unsqueeze(0) if self.auto_contrast else lane['gin']
+                    lane['vfeats'].append(self.model.predict_padded_bottom_up(gin, scale, hflip))
+                else:
+                    lane['vgout'].append(self._detect_core(lane['gin'], (scale, hflip)))
+            pool = g.pool() if pool is None else pool
+            lane['vgraphs'].append(g)
+            if self.defer_tracking:
+                gb = torch.cuda.CUDAGraph()
+                with torch.no_grad(), torch.cuda.graph(gb, stream=lane['stream'], pool=pool, capture_error_mode='thread_local'):
+                    lane['vgout'].append(self._detect_heads(lane['vfeats'][-1], hflip))
+                lane['vgraphs_b'].append(gb)
+        lane['graph'] = lane['vgraphs'][0]
 
     def _capture(self):
         """Per lane: warm up eagerly on the lane's stream (MIOpen / TunableOp / hipBLASLt pick their kernels, per-stream scratch
@@ -149,11 +204,13 @@ class DetectTrackPipeline(object):
             lane = dict(stream=torch.cuda.Stream(device=self.dev), n_dets=torch.zeros(1, dtype=torch.int64, device=self.dev),
                         gin=torch.zeros((1, self.h, self.w, 3), dtype=torch.uint8, device=self.dev))
             with torch.cuda.stream(lane['stream']), torch.no_grad():
-                for t in range(3):
+                for t in range(0 if self.views else 3):
                     lane['gin'].copy_(self.frames[t % self.n_times, 0].unsqueeze(0))
                     self._detect_core(lane['gin'])
             lane['stream'].synchronize()
-            if self.defer_tracking:
+            if self.views:
+                self._capture_views(lane)
+            elif self.defer_tracking:
                 # two graphs per frame - bottom-up pathway | FPN + RPN + heads + tail - so that an event between them can release the
                 # SORT kernel of the previous chunk (see step()); the second graph reads the first one's output tensors in place
                 lane['graph'] = torch.cuda.CUDAGraph()
@@ -230,6 +287,8 @@ class DetectTrackPipeline(object):
 
     def detect_frame(self, c, cam, j, eager=False):
         """Frame j of camera cam of chunk c -> wire-format detections in that frame's 100 slots."""
+        if self.views:
+            return self._detect_frame_views(c, cam, j, eager)
         # decoded uint8 HWC RGB frame -> fused pre-processing kernel (ToTensor(scaling=False) + BGR + normalise + pad)
         img = self.frames[(self.time + j) % self.n_times, cam].unsqueeze(0)
         a = (cam * self.fpc + j) * SLOTS
@@ -279,11 +338,69 @@ class DetectTrackPipeline(object):
             self.category[c, a:a + SLOTS] = cat
             lane['n_dets'] += cnt
 
+    def _detect_frame_views(self, c, cam, j, eager):
+        """views: the frame through every view's detector, each view's 100 wire slots into its own block of chunk c."""
+        img = self.frames[(self.time + j) % self.n_times, cam].unsqueeze(0)
+        a = (cam * self.fpc + j) * SLOTS
+        if not self.use_graph:
+            for k, v in enumerate(self.views):
+                xywhs, cat, cnt = self._detect_core(img, v)
+                self.view_xywhs[c, k, :, a:a + SLOTS] = xywhs
+                self.view_category[c, k, a:a + SLOTS] = cat
+                self.n_dets_dev += cnt
+            return
+        if self._graph is None:
+            self._capture()
+        lane = self._lanes[self._frame_no % self.n_inflight]
+        self._frame_no += 1
+        others = [l for l in self._lanes if l is not lane]
+        if eager and others:
+            for l in others:                                     # the instrumented frame runs alone (see detect_frame)
+                ev = torch.cuda.Event()
+                ev.record(l['stream'])
+                lane['stream'].wait_event(ev)
+        with torch.cuda.stream(lane['stream']):
+            if eager:
+                outs = [self._detect_core(img, v) for v in self.views]
+                if others:
+                    ev = torch.cuda.Event()
+                    ev.record(lane['stream'])
+                    for l in others:
+                        l['stream'].wait_event(ev)
+                if self._pending_track is not None:
+                    self.flush()
+            else:
+                lane['gin'].copy_(img)
+                for k in range(self.k_views):
+                    lane['vgraphs'][k].replay()
+                    if self.defer_tracking:
+                        if k == 0 and self._pending_track is not None:
+                            # the previous chunk's merge + SORT start behind the first view's bottom-up pathway (see detect_frame)
+                            ev = torch.cuda.Event()
+                            ev.record(lane['stream'])
+                            fn, self._pending_track = self._pending_track, None
+                            fn(ev)
+                        lane['vgraphs_b'][k].replay()
+                outs = lane['vgout']
+            for k, (xywhs, cat, cnt) in enumerate(outs):
+                self.view_xywhs[c, k, :, a:a + SLOTS] = xywhs
+                self.view_category[c, k, a:a + SLOTS] = cat
+                lane['n_dets'] += cnt
+
     @property
     def n_dets_total(self):
         return int(self.n_dets_dev.item()) + sum(int(l['n_dets'].item()) for l in getattr(self, '_lanes', []))
 
     def track(self, c):
+        if self.ensemble is not None:
+            # views: merge the K views' slots of chunk c into the slots SORT reads (same stream, in front of it)
+            if self.merge_events is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            self.ensemble.run(self.view_xywhs[c], self.view_category[c], out=(self.xywhs[c], self.category[c], self.merge_counts[c]))
+            if self.merge_events is not None:
+                e1.record()
+                self.merge_events.append((e0, e1))
         self.tracker.feed(self.x[c], self.y[c], self.wd[c], self.ht[c], self.score[c], self.category[c], self.frame_off,
                           self.stream_off, self.clip_w, self.clip_h, self.out_frame[c], self.out_cat[c], self.out_bbox[c],
                           self.out_score[c], self.out_id[c], self.chunk_counts[c])
@@ -369,9 +486,9 @@ class DetectTrackPipeline(object):
         in order, empty slots removed), `rows` the tracker output in the reference's order (stream-major) with the
         reference's global ids (wt_track_global_ids_dev), frame = index into packed's frames."""
         torch.cuda.synchronize()
-        nch, F, nc = self.chunk, self.fpc, self.nc
-        cat = self.category[:nch].cpu().numpy().reshape(nch, nc, F, SLOTS)
-        arr = {k: getattr(self, a)[:nch].cpu().numpy().reshape(nch, nc, F, SLOTS)
+        nch, F, nc, S = self.chunk, self.fpc, self.nc, self.slots
+        cat = self.category[:nch].cpu().numpy().reshape(nch, nc, F, S)
+        arr = {k: getattr(self, a)[:nch].cpu().numpy().reshape(nch, nc, F, S)
                for k, a in (('x', 'x'), ('y', 'y'), ('w', 'wd'), ('h', 'ht'), ('score', 'score'))}
         cols = {k: [] for k in ('x', 'y', 'w', 'h', 'score', 'category')}
         frame_off, stream_off = [0], [0]
@@ -407,6 +524,19 @@ class DetectTrackPipeline(object):
         rows = dict(frame=fr[order].cpu().numpy(), category=ct[order].cpu().numpy(), bbox=bb[order].cpu().numpy(),
                     score=sc[order].cpu().numpy(), object_id=gid[order].cpu().numpy())
         return packed, rows, int(counts[:, 1].sum())
+
+
+    def view_history(self):
+        """views: synchronise and return the chunks of the current segment as the merge saw them - per-view slots
+        xywhs (chunks, K, 5, frames x 100) / category (chunks, K, frames x 100) - and what it wrote: merged_xywhs
+        (chunks, 5, frames x K x 100), merged_category, merged_counts (chunks, frames)."""
+        if not self.views:
+            raise ValueError('view_history() needs a pipeline built with views')
+        torch.cuda.synchronize()
+        nch = self.chunk
+        return dict(xywhs=self.view_xywhs[:nch].cpu().numpy(), category=self.view_category[:nch].cpu().numpy(),
+                    merged_xywhs=self.xywhs[:nch].cpu().numpy(), merged_category=self.category[:nch].cpu().numpy(),
+                    merged_counts=self.merge_counts[:nch].cpu().numpy())
 
 
 def check_against(pipe, track_streams):

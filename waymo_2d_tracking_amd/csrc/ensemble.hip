@@ -474,6 +474,152 @@ __global__ __launch_bounds__(kWave) void nms_raw_kernel(const double* __restrict
     if (lane == 0) *n_keep = nk;
 }
 
+// ---- ensemble of K views' wire slots (the device form of: --export per view -> detnet.ensemble -> JSON) ---------------
+// Input slots are the layout DetectTrackPipeline fills: view-major xywhs (K, 5, n_frames * S) float64 [x, y, w, h, score]
+// and category (K, n_frames * S) int32, 0 = empty slot.  Pass 1 runs one wavefront per (frame, category) group: it gathers
+// the group's rows view by view in slot order (= merge_inputs + pack_groups of detnet/ensemble.py, with the filters of
+// convert_submission), merges them with ensemble_nms_group / ensemble_fusion_group and applies the output step of
+// ensemble.py:59-63 (score > min_score, boxes truncated, numpy's round(score, 5)).  Pass 2 (one wavefront per frame) writes
+// the groups of a frame in ascending category order into the frame's K * S output slots.
+constexpr int kMaxViews = 16;
+constexpr size_t kSlotsLdsBudget = kLdsBudget - 1024;      // room for the kernel's static LDS
+
+// round(np.float64(s), 5) = numpy around: multiply, rint (half to even), divide (not CPython's correctly rounded round)
+__device__ __forceinline__ double round5_numpy(double s) { return rint(s * 1e5) / 1e5; }
+
+__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct SlotsWs {
+    double* rows;      // per group K*S rows of 5: gathered input, later the group's final wire rows [x, y, w, h, score]
+    double* merged;    // per group K*S rows of 5: merge output [score, x, y, w, h]
+    int32_t* count;    // per group: final row count
+    char* scratch;     // per group `scratch_stride` bytes of group memory (global path only)
+    size_t scratch_stride;
+};
+
+__host__ __device__ inline size_t slots_group_mem(int method, size_t ks) {
+    return method == 0 ? fuse_mem_bytes(ks) : group_mem_bytes(ks);
+}
+
+__host__ inline SlotsWs slots_ws_layout(char* base, int64_t n_groups, size_t ks, int method, bool lds, size_t* total) {
+    SlotsWs w;
+    size_t off = 0;
+    const size_t rows_b = align256((size_t)n_groups * ks * 5 * sizeof(double));
+    w.rows = reinterpret_cast<double*>(base + off); off += rows_b;
+    w.merged = reinterpret_cast<double*>(base + off); off += rows_b;
+    w.count = reinterpret_cast<int32_t*>(base + off); off += align256((size_t)n_groups * sizeof(int32_t));
+    w.scratch_stride = lds ? 0 : align256(slots_group_mem(method, ks));
+    w.scratch = base + off; off += (size_t)n_groups * w.scratch_stride;
+    *total = off;
+    return w;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kWave) void slots_groups_kernel(
+    const double* __restrict__ xywhs, const int32_t* __restrict__ category, int64_t n_frames, int S, int K,
+    const double* __restrict__ weights, int C, int method, double thr, double cut, double min_score, SlotsWs ws) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int32_t sizes[kMaxViews];
+    __shared__ int64_t n_merged;
+    const int lane = threadIdx.x;
+    const int64_t N = n_frames * S;
+    const size_t ks = (size_t)K * S;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int64_t g = blockIdx.x; g < n_frames * C; g += gridDim.x) {
+        const int64_t f = g / C;
+        const int c = (int)(g - f * C) + 1;
+        double* rows = ws.rows + (size_t)g * ks * 5;
+        double* merged = ws.merged + (size_t)g * ks * 5;
+        // 1. gather: view by view, slot order; convert_submission's filters on the weighted score
+        int n = 0;
+        for (int k = 0; k < K; ++k) {
+            const double wk = weights[k];
+            const int n0 = n;
+            for (int base = 0; base < S; base += kWave) {
+                const int s = base + lane;
+                const int64_t i = (int64_t)k * N + f * S + s;
+                bool keep = false;
+                double x = 0., y = 0., w = 0., h = 0., sc = 0.;
+                if (s < S && category[i] == c) {
+                    const double* p = xywhs + (int64_t)k * 5 * N + f * S + s;
+                    x = p[0]; y = p[N]; w = p[2 * N]; h = p[3 * N];
+                    sc = p[4 * N] * wk;
+                    keep = (w > 0.) && (h > 0.) && (sc >= min_score);
+                }
+                const unsigned long long mask = __ballot(keep);
+                if (keep) {
+                    double* r = rows + 5 * (size_t)(n + __popcll(mask & below));
+                    r[0] = sc; r[1] = x; r[2] = y; r[3] = w; r[4] = h;
+                }
+                n += __popcll(mask);
+            }
+            if (lane == 0) sizes[k] = n - n0;
+        }
+        __syncthreads();
+        // 2. merge (the existing group functions, rows [score, x_left, y_top, w, h])
+        if (n > 0) {
+            char* mem = kLds ? smem : ws.scratch + (size_t)g * ws.scratch_stride;
+            if (method == 0)
+                ensemble_fusion_group(rows, n, sizes, K, mem, ks, false, thr, merged, &n_merged);
+            else
+                ensemble_nms_group<kLds>(rows, n, mem, ks, method == 2, false, thr, cut, merged, &n_merged);
+        } else if (lane == 0) {
+            n_merged = 0;
+        }
+        __syncthreads();
+        // 3. ensemble.py:59-63: score > min_score, astype(int), round(score, 5); wire order [x, y, w, h, score]
+        const int nm = (int)n_merged;
+        int nk = 0;
+        for (int base = 0; base < nm; base += kWave) {
+            const int r = base + lane;
+            bool keep = false;
+            double v[5] = {0., 0., 0., 0., 0.};
+            if (r < nm) {
+                for (int q = 0; q < 5; ++q) v[q] = merged[5 * (size_t)r + q];
+                keep = v[0] > min_score;
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (keep) {
+                double* o = rows + 5 * (size_t)(nk + __popcll(mask & below));
+                o[0] = trunc(v[1]); o[1] = trunc(v[2]); o[2] = trunc(v[3]); o[3] = trunc(v[4]);
+                o[4] = round5_numpy(v[0]);
+            }
+            nk += __popcll(mask);
+        }
+        if (lane == 0) ws.count[g] = nk;
+        __syncthreads();
+    }
+}
+
+// pass 2: frame f's groups in ascending category order -> output slots [f * K * S, (f + 1) * K * S); the rest empty
+__global__ __launch_bounds__(kWave) void slots_compact_kernel(int64_t n_frames, int S, int K, int C, SlotsWs ws,
+                                                             double* __restrict__ out_xywhs, int32_t* __restrict__ out_category,
+                                                             int64_t* __restrict__ out_counts) {
+    const int lane = threadIdx.x;
+    const int64_t ks = (int64_t)K * S;
+    const int64_t NO = n_frames * ks;
+    for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
+        int64_t o = f * ks;
+        for (int c = 0; c < C; ++c) {
+            const int64_t g = f * C + c;
+            const int cnt = ws.count[g];
+            const double* rows = ws.rows + (size_t)g * ks * 5;
+            for (int j = lane; j < cnt; j += kWave) {
+                for (int q = 0; q < 5; ++q) out_xywhs[q * NO + o + j] = rows[5 * (size_t)j + q];
+                out_category[o + j] = c + 1;
+            }
+            o += cnt;
+        }
+        for (int64_t j = o + lane; j < (f + 1) * ks; j += kWave) {
+            for (int q = 0; q < 5; ++q) out_xywhs[q * NO + j] = 0.;
+            out_category[j] = 0;
+        }
+        if (lane == 0) out_counts[f] = o - f * ks;
+    }
+}
+
+bool slots_use_lds(int method, int64_t ks) { return slots_group_mem(method, (size_t)ks) <= kSlotsLdsBudget; }
+
 size_t row_bytes(int method) { return method == 0 ? fuse_mem_bytes(1) + 16 : group_mem_bytes(1) + 16; }
 
 int launch_groups(const double* dets5, const int64_t* group_offsets, const int32_t* input_sizes, int64_t n_rows,
@@ -574,6 +720,55 @@ int wt_ensemble_groups_host(const double* dets5, const int64_t* group_offsets, c
     WT_HIP(hipDeviceSynchronize());
     WT_HIP(hipMemcpy(out5, d_out.p, sizeof(double) * 5 * (size_t)n_rows, hipMemcpyDeviceToHost));
     WT_HIP(hipMemcpy(out_counts, d_cnt.p, sizeof(int64_t) * (size_t)n_groups, hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+size_t wt_ensemble_slots_workspace(int64_t n_frames, int64_t slots, int k_views, int n_categories, int method) {
+    if (n_frames < 0 || slots < 0 || k_views < 1 || n_categories < 1 || method < 0 || method > 2) return 0;
+    const int64_t ks = (int64_t)k_views * slots;
+    size_t total = 0;
+    slots_ws_layout(nullptr, n_frames * n_categories, (size_t)(ks > 0 ? ks : 1), method, slots_use_lds(method, ks), &total);
+    return total;
+}
+
+int wt_ensemble_slots_dev(const double* xywhs, const int32_t* category, int64_t n_frames, int64_t slots, int k_views,
+                          const double* weights, int n_categories, int method, double iou_thresh, double soft_nms_cut,
+                          double min_score, double* out_xywhs, int32_t* out_category, int64_t* out_counts,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    WT_TRY(wt::ensure_device());
+    if (method < 0 || method > 2) { wt::set_error("method must be 0 (fusion), 1 (nms) or 2 (soft_nms)"); return WT_ERR_INVALID; }
+    if (k_views < 1 || k_views > kMaxViews) { wt::set_error("k_views must be in 1..%d", kMaxViews); return WT_ERR_INVALID; }
+    if (n_frames < 0 || slots < 0 || slots > (1 << 20) || n_categories < 1) {
+        wt::set_error("bad slot shape: n_frames %lld, slots %lld, n_categories %d", (long long)n_frames, (long long)slots, n_categories);
+        return WT_ERR_INVALID;
+    }
+    if (n_frames == 0 || slots == 0) return WT_OK;
+    if (!xywhs || !category || !weights || !out_xywhs || !out_category || !out_counts || !workspace) {
+        wt::set_error("null pointer argument"); return WT_ERR_INVALID;
+    }
+    const int64_t ks = (int64_t)k_views * slots;
+    const bool lds = slots_use_lds(method, ks);
+    const int64_t n_groups = n_frames * n_categories;
+    size_t need = 0;
+    const SlotsWs ws = slots_ws_layout((char*)workspace, n_groups, (size_t)ks, method, lds, &need);
+    if (workspace_bytes < need) {
+        wt::set_error("slot ensemble workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
+        return WT_ERR_CAPACITY;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)(n_groups < (1 << 20) ? n_groups : (1 << 20));
+    if (lds)
+        hipLaunchKernelGGL(slots_groups_kernel<true>, dim3(grid), dim3(kWave), slots_group_mem(method, (size_t)ks), st, xywhs,
+                           category, n_frames, (int)slots, k_views, weights, n_categories, method, iou_thresh, soft_nms_cut,
+                           min_score, ws);
+    else
+        hipLaunchKernelGGL(slots_groups_kernel<false>, dim3(grid), dim3(kWave), 0, st, xywhs, category, n_frames, (int)slots,
+                           k_views, weights, n_categories, method, iou_thresh, soft_nms_cut, min_score, ws);
+    WT_HIP(hipGetLastError());
+    const unsigned fgrid = (unsigned)(n_frames < (1 << 20) ? n_frames : (1 << 20));
+    hipLaunchKernelGGL(slots_compact_kernel, dim3(fgrid), dim3(kWave), 0, st, n_frames, (int)slots, k_views, n_categories, ws,
+                       out_xywhs, out_category, out_counts);
+    WT_HIP(hipGetLastError());
     return WT_OK;
 }
 

@@ -39,6 +39,17 @@ def convert_submission(det_list, weight, min_score=0):
     return grouped
 
 
+def normalise_weights(weights, k):
+    """Per-input weights divided by their maximum (main() below, for the weights of a .yml); None = all 1."""
+    w = [1.0] * k if weights is None else [float(v) for v in weights]
+    if len(w) != k:
+        raise ValueError('%d weights for %d inputs' % (len(w), k))
+    top = max(w)
+    if not top > 0:
+        raise ValueError('weights need a positive maximum, got %s' % w)
+    return [v / top for v in w]
+
+
 def load_yml_input_and_weight(tree, prefix=''):
     """ensemble.py:67-75: the nested {directory: {file: weight}} mapping of a weights .yml flattened to [(path, weight)] in
     written order."""

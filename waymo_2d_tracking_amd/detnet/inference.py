@@ -4,6 +4,8 @@
 
     python -m waymo_2d_tracking_amd.detnet.inference -m MODEL_FILE -i IMAGES_DIR --export submission.json \
         [--tta x1.5,hflip] [--auto-contrast=1] [-j 8] [-o OUT_DIR] [--resume OUT_DIR/detections.pkl] [--eval --annotations GT.json]
+    python -m waymo_2d_tracking_amd.detnet.inference -m MODEL_FILE -i IMAGES_DIR --export merged.json \
+        --views 'orig;x1.5,hflip' --views-method soft_nms [--views-weights 1,0.8] [--export-views VIEWS_DIR]
     torchrun --nproc-per-node 8 -m waymo_2d_tracking_amd.detnet.inference ...     # the same, started by torchrun
 
 MODEL_FILE is a `{args, kwargs, state_dict}` file of the reference or of this package (nn/__init__.py); the string
@@ -77,7 +79,157 @@ def build_parser():
     parser.add_argument('--data-root', type=str, default=None)
     parser.add_argument('--data-include-empty', action='store_true')
     parser.add_argument('--data-bgr', action='store_true')
+    # several TTA views of one model, merged per (image, category) on the GPU (= --tta V --export per view + detnet.ensemble)
+    parser.add_argument('--views', type=str, help="';'-separated --tta specs merged per image, e.g. 'orig;x1.2;x1.5,hflip' (needs --export)")
+    parser.add_argument('--views-method', choices=('weighted_fusion', 'nms', 'soft_nms'), default='weighted_fusion',
+                        help='how the views are merged (detnet.ensemble -m)')
+    parser.add_argument('--views-iou-thresh', type=float, default=0.5, help='IOU threshold for merging bboxes')
+    parser.add_argument('--views-soft-nms-cut', type=float, default=1.0, help='cutout IoU threshold for soft nms')
+    parser.add_argument('--views-min-score', type=float, default=0, help='minimal score to keep')
+    parser.add_argument('--views-weights', type=str, help="per-view weights, e.g. '1,0.8' (divided by their maximum)")
+    parser.add_argument('--export-views', type=str, help='directory: view<k>.json = what --tta <view k> --export writes')
     return parser
+
+
+VIEW_BATCH_FRAMES = 256         # images per SlotEnsemble launch
+
+
+def check_views(args):
+    """--views and its flags -> (specs, --tta token lists, normalised weights), or None without --views.  Conflicting or
+    unfoldable settings raise ValueError / NotImplementedError with the reason."""
+    from .ensemble import normalise_weights
+    from .nn.tta import foldable_view
+    if not args.views:
+        if args.export_views or args.views_weights:
+            raise ValueError('--export-views / --views-weights need --views')
+        return None
+    if not args.export:
+        raise ValueError('--views needs --export (the merged rows are written there)')
+    for flag, on in (('--tta', args.tta), ('-o/--output', args.output), ('--resume', args.resume), ('--eval', args.eval)):
+        if on:
+            raise ValueError('--views cannot be combined with %s: the merged rows are wire rows (integer boxes, 5-decimal scores), '
+                             'not the per-class prediction store' % flag)
+    if args.jobs > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise NotImplementedError('--views runs in one process on one GPU: -j N / torchrun are not supported with it')
+    specs = [v.strip() for v in args.views.split(';')]
+    views = [foldable_view(v) for v in specs]
+    weights = None
+    if args.views_weights:
+        try:
+            weights = [float(w) for w in args.views_weights.split(',')]
+        except ValueError:
+            raise ValueError('--views-weights: %r is not a comma-separated list of numbers' % args.views_weights)
+    return specs, views, normalise_weights(weights, len(views))
+
+
+def merge_view_rows(image_ids, view_rows, weights, method, iou_thresh, soft_nms_cut, min_score, batch_frames=VIEW_BATCH_FRAMES):
+    """The detection rows of K views (export.detection_rows columns: image index, category, int bbox, 5-decimal score, images in
+    data-set order) -> the rows `python -m detnet.ensemble view0.json ... view{K-1}.json` writes, merged on the GPU.
+
+    Every view's rows of an image fill that image's wire slots in file order (S = the most rows any view has for one image);
+    devpath.SlotEnsemble merges batch_frames images per launch.  Images come out in the ensemble CLI's order: first appearance
+    over the views' kept rows, view by view (merge_inputs); inside an image categories ascend."""
+    from ..devpath import SlotEnsemble
+    F, K = len(image_ids), len(view_rows)
+    empty = dict(image=np.zeros(0, np.int32), category=np.zeros(0, np.int32), bbox=np.zeros((0, 4), np.int64), score=np.zeros(0))
+    counts = [np.bincount(r['image'], minlength=F) if len(r['image']) else np.zeros(F, np.int64) for r in view_rows]
+    S = int(max([1] + [int(c.max()) for c in counts if len(c)]))
+    C = int(max([1] + [int(r['category'].max()) for r in view_rows if len(r['category'])]))
+    if any(len(r['category']) and int(r['category'].min()) < 1 for r in view_rows):
+        raise ValueError('view rows need category ids >= 1')
+    pos = []
+    for r, c in zip(view_rows, counts):
+        img = np.asarray(r['image'], np.int64)
+        if np.any(np.diff(img) < 0):
+            raise ValueError('view rows must be grouped by image in data-set order')
+        start = np.concatenate([[0], np.cumsum(c)[:-1]])
+        pos.append(img * S + (np.arange(len(img)) - start[img]))          # slot = file order inside the image
+    B = max(1, min(batch_frames, F))
+    ens = SlotEnsemble(B, S, weights, C, method, iou_thresh, soft_nms_cut, min_score)
+    out = ens.outputs()
+    parts = []
+    for b0 in range(0, F, B):
+        xywhs = np.zeros((K, 5, B * S))
+        cat = np.zeros((K, B * S), np.int32)
+        for k, r in enumerate(view_rows):
+            sel = (r['image'] >= b0) & (r['image'] < b0 + B)
+            p = pos[k][sel] - b0 * S
+            xywhs[k, 0:4, p] = r['bbox'][sel]
+            xywhs[k, 4, p] = r['score'][sel]
+            cat[k, p] = r['category'][sel]
+        ens.run(torch.from_numpy(xywhs).cuda(), torch.from_numpy(cat).cuda(), out=out)
+        ox, oc, on = (t.cpu().numpy() for t in out)
+        n = on[:min(B, F - b0)]
+        slot = np.concatenate([f * K * S + np.arange(c) for f, c in enumerate(n.tolist())]) if n.sum() else np.zeros(0, np.int64)
+        parts.append(dict(image=(b0 + slot // (K * S)).astype(np.int32), category=oc[slot].astype(np.int32),
+                          bbox=ox[0:4, slot].T.astype(np.int64), score=ox[4, slot].copy()))
+    rows = {k: np.concatenate([p[k] for p in parts]) if parts else empty[k] for k in empty}
+    # image order of merge_inputs: first appearance over the kept rows (w > 0, h > 0, score * weight >= min_score), view by view
+    seen = np.concatenate([np.asarray(r['image'], np.int64)[(r['bbox'][:, 2] > 0) & (r['bbox'][:, 3] > 0) & (r['score'] * w >= min_score)]
+                           for r, w in zip(view_rows, weights)] + [np.zeros(0, np.int64)])
+    present, first = np.unique(seen, return_index=True)
+    rank = np.full(F, F, np.int64)
+    rank[present[np.argsort(first, kind='stable')]] = np.arange(len(present))
+    order = np.argsort(rank[rows['image']], kind='stable')
+    return {k: v[order] for k, v in rows.items()}
+
+
+def run_views(args, views_spec):
+    """--views: every image is decoded once and goes through one captured detector graph lane per view (scale / flips folded into
+    the pre-processing kernel); each view's rows are the rows `--tta <view> --export` writes (optionally written to
+    --export-views); merge_view_rows merges them on the GPU and the native writer writes --export."""
+    from . import nn as detnn
+    from .export import detection_rows, write_detections_json
+    from .trainer import Predictions
+    specs, views, weights = views_spec
+    torch.backends.cudnn.benchmark = bool(args.cudnn_benchmark)
+    if args.cudnn_benchmark:
+        from ..tuning import enable_gemm_tuning
+        enable_gemm_tuning()
+    start = time.time()
+    model = detnn.load(args.model).cuda().eval()
+    predicts = [PredictModel(model, dict(tta=v, max_bbox=args.max_bbox)) for v in views]
+    images = list_images(args.input)
+    if args.exclusive:
+        images = [(i, p) for i, p in images if args.exclusive not in i]
+    image_ids = [i for i, _ in images]
+    index = {k: i for i, k in enumerate(image_ids)}
+    stores = [Predictions(model.classnames, image_ids) for _ in views]
+    sizes = np.zeros((len(image_ids), 2), np.int32)
+    K = len(views)
+    with torch.no_grad():
+        loader = ImageLoader(images, args.resize, args.max_image_size, auto_contrast=args.auto_contrast, decoder=args.decoder)
+        lanes = [p.stream(args.inflight) for p in predicts] if args.inflight > 0 else None
+        if lanes is not None and any(l is None for l in lanes):
+            lanes = None                                              # no static-shape pass: one eager call per view and image
+        pending = []
+        for image_id, img, (w, h) in loader:
+            if args.auto_contrast and not loader.auto_contrast_in_loader:
+                img = autocontrast_(img)
+            sizes[index[image_id]] = (w, h)
+            if lanes is None:
+                for k in range(K):
+                    stores[k][image_id] = predicts[k](img.unsqueeze(0))[0]
+                continue
+            if len(pending) >= args.inflight:
+                done, tickets = pending.pop(0)
+                for k in range(K):
+                    stores[k][done] = lanes[k][1](tickets[k])
+            pending.append((image_id, [lanes[k][0](img) for k in range(K)]))
+        for done, tickets in pending:
+            for k in range(K):
+                stores[k][done] = lanes[k][1](tickets[k])
+    image_sizes = {k: (int(sizes[i, 0]), int(sizes[i, 1])) for i, k in enumerate(image_ids)}
+    view_rows = [detection_rows(st, image_sizes) for st in stores]
+    if args.export_views:
+        for k, r in enumerate(view_rows):
+            write_detections_json(Path(args.export_views) / ('view%d.json' % k), image_ids, r)
+    rows = merge_view_rows(image_ids, view_rows, weights, args.views_method, args.views_iou_thresh, args.views_soft_nms_cut,
+                           args.views_min_score)
+    write_detections_json(Path(args.export).with_suffix('.json'), image_ids, rows)
+    print(f'inference done in {time.time() - start:.1f}s, {len(image_ids)} images, views {specs} weights {weights}, '
+          f'{sum(len(r["image"]) for r in view_rows)} view rows -> {len(rows["image"])} merged rows')
+    return rows
 
 
 class PredictModel(torch.nn.Module):
@@ -283,6 +435,7 @@ def check_supported(args):
         raise ValueError('--eval needs --annotations GT.json (COCO-format ground truth; the reference reads it from --data-root)')
     if args.export_format != 'json':
         raise NotImplementedError('--export-format json only')
+    return check_views(args)
 
 
 def run_rank(args, world, rank):
@@ -383,7 +536,7 @@ def _spawned(rank, world, port, argv):
 
 def inference(args, argv=None):
     """detnet/inference.py:151-199 for an image folder."""
-    check_supported(args)
+    views_spec = check_supported(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     if world == 1 and args.jobs > 1:                                  # -j N: one process per GPU (trainer/test.py:227-250)
@@ -400,6 +553,8 @@ def inference(args, argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError('the detector runs on the GPU only (HIP kernels, no CPU fallback)')
     torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
+    if views_spec is not None:
+        return run_views(args, views_spec)
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group('nccl', device_id=torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0'))))

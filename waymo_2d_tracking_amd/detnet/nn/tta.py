@@ -58,6 +58,35 @@ def parse_tta(data_aug):
     return plan
 
 
+def parse_view(spec):
+    """One view spec of DetectTrackPipeline ('orig', 'x1.5', 'x1.5,hflip', '') -> (scale, hflip): the augmentations the
+    pre-processing kernel folds in (resizes multiply)."""
+    scale, hflip = 1.0, False
+    for aug in [a for a in spec.split(',') if a]:
+        if aug.startswith('x'):
+            scale *= float(aug[1:])
+        elif aug == 'hflip':
+            hflip = True
+        elif aug != 'orig':
+            raise ValueError('bench supports --tta orig / xS / hflip, got %r' % aug)
+    return scale, hflip
+
+
+def foldable_view(spec):
+    """One --views spec ('orig', 'x1.5,hflip', ...) -> its --tta token list when the detector folds it into the pre-processing
+    kernel (TTA._fused_pre: at most one xS resize, then flips); ValueError otherwise."""
+    tokens = [t for t in spec.split(',') if t]
+    if not tokens:
+        raise ValueError('--views: empty view spec (use "orig" for the plain image)')
+    try:
+        fused = TTA(None, tokens)._fused_pre()
+    except (ValueError, NotImplementedError) as e:
+        raise ValueError('--views: %r is not a view the pre-processing kernel can fold: %s' % (spec, e))
+    if fused is None:
+        raise ValueError('--views: %r cannot be folded into the pre-processing kernel (at most one xS resize, then flips)' % spec)
+    return tokens
+
+
 def apply_plan(x, plan):
     """Image side of the plan on a (B, 3, H, W) tensor: bilinear resize (align_corners False) / flips (tta.py:147-190)."""
     for op in plan:

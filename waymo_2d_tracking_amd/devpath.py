@@ -103,6 +103,59 @@ class DeviceEnsemble(object):
         _lib.check(rc, 'wt_ensemble_groups_dev')
 
 
+class SlotEnsemble(object):
+    """wt_ensemble_slots_dev: K views' wire slots of the same frames -> merged wire slots, on the caller's stream.
+
+    Inputs are xywhs (K, 5, n_frames * slots) float64 and category (K, n_frames * slots) int32 device tensors (the layout
+    DetectTrackPipeline fills per view); outputs are (5, n_frames * K * slots), (n_frames * K * slots) and per-frame row
+    counts (n_frames) int64.  The workspace is owned here; run() neither allocates nor synchronises, so it can be captured.
+    Categories must lie in 1..n_categories: the kernel reads any other value as an empty slot, so callers size n_categories from
+    their data (inference.merge_view_rows: the largest category present) or from the detector (DetectTrackPipeline: one per
+    tracker class)."""
+
+    def __init__(self, n_frames, slots, weights, n_categories, method='weighted_fusion', iou_thresh=0.5, soft_nms_cut=1.0,
+                 min_score=0.0, device='cuda'):
+        from .detnet.ensemble import METHODS
+        self.lib = _lib.lib()
+        self.dev = torch.device(device)
+        self.n_frames, self.slots, self.k, self.n_categories = int(n_frames), int(slots), len(weights), int(n_categories)
+        self.method = METHODS[method] if isinstance(method, str) else int(method)
+        self.thr, self.cut, self.min_score = float(iou_thresh), float(soft_nms_cut), float(min_score)
+        self.weights = torch.tensor([float(w) for w in weights], dtype=torch.float64, device=self.dev)
+        ws = int(self.lib.wt_ensemble_slots_workspace(C.c_int64(self.n_frames), C.c_int64(self.slots), C.c_int(self.k),
+                                                      C.c_int(self.n_categories), C.c_int(self.method)))
+        if ws == 0:
+            raise ValueError('wt_ensemble_slots_workspace: bad shape (%d frames, %d slots, %d views, %d categories, method %d)'
+                             % (self.n_frames, self.slots, self.k, self.n_categories, self.method))
+        self.ws_bytes = ws
+        self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.dev)
+        self.out_slots = self.n_frames * self.k * self.slots
+
+    def outputs(self):
+        """Fresh output tensors: (xywhs (5, n_frames * K * slots), category, counts (n_frames))."""
+        return (torch.zeros((5, self.out_slots), dtype=torch.float64, device=self.dev),
+                torch.zeros(self.out_slots, dtype=torch.int32, device=self.dev),
+                torch.zeros(self.n_frames, dtype=torch.int64, device=self.dev))
+
+    def run(self, xywhs, category, out=None):
+        """Enqueue the merge on the current stream; returns (xywhs, category, counts) - `out` when given."""
+        n = self.n_frames * self.slots
+        if tuple(xywhs.shape) != (self.k, 5, n) or tuple(category.shape) != (self.k, n):
+            raise ValueError('expected xywhs (%d, 5, %d) and category (%d, %d), got %s and %s'
+                             % (self.k, n, self.k, n, tuple(xywhs.shape), tuple(category.shape)))
+        if xywhs.dtype != torch.float64 or category.dtype != torch.int32 or not xywhs.is_contiguous() or not category.is_contiguous():
+            raise ValueError('xywhs must be contiguous float64 and category contiguous int32')
+        ox, oc, on = out if out is not None else self.outputs()
+        if tuple(ox.shape) != (5, self.out_slots) or tuple(oc.shape) != (self.out_slots,) or on.numel() < self.n_frames:
+            raise ValueError('output tensors have the wrong shape')
+        rc = self.lib.wt_ensemble_slots_dev(
+            _dp(xywhs), _dp(category), C.c_int64(self.n_frames), C.c_int64(self.slots), C.c_int(self.k), _dp(self.weights),
+            C.c_int(self.n_categories), C.c_int(self.method), C.c_double(self.thr), C.c_double(self.cut),
+            C.c_double(self.min_score), _dp(ox), _dp(oc), _dp(on), _dp(self.workspace), C.c_size_t(self.ws_bytes), _stream())
+        _lib.check(rc, 'wt_ensemble_slots_dev')
+        return ox, oc, on
+
+
 class StreamingTracker(object):
     """wt_track_state_* / wt_track_chunk_dev: trackers that stay resident in HBM while the frames of their streams arrive
     chunk by chunk (online detect -> track; tracking/utils.py:29-36 keeps one MultiClassTrackerSort per stream alive).
