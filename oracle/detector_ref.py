@@ -164,8 +164,8 @@ def rpn(r, feats, img_h, img_w):
     return boxes[keep]
 
 
-def roi_pool_fpn(feats, boxes, scales, pooled=7, min_level=2, canonical_level=4, canonical_size=224.0):
-    """Vectorised ROIAlign (aligned=True, adaptive grid) over FPN levels; boxes (R,4) for batch 0 -> (R,C,P,P)."""
+def roi_pool_fpn(feats, boxes, scales, pooled=7, min_level=2, canonical_level=4, canonical_size=224.0, image=0):
+    """Vectorised ROIAlign (aligned=True, adaptive grid) over FPN levels; boxes (R,4) for image `image` of the batch -> (R,C,P,P)."""
     R = boxes.shape[0]
     C = feats[0].shape[1]
     dt = feats[0].dtype
@@ -178,7 +178,7 @@ def roi_pool_fpn(feats, boxes, scales, pooled=7, min_level=2, canonical_level=4,
         if not len(sel):
             continue
         H, W = feat.shape[2], feat.shape[3]
-        fl = feat[0].permute(1, 2, 0).reshape(H * W, C)
+        fl = feat[image].permute(1, 2, 0).reshape(H * W, C)
         b = boxes[sel].float() * scales[li] - 0.5
         rw, rh = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
         bw, bh = rw / P, rh / P
@@ -215,6 +215,19 @@ def roi_pool_fpn(feats, boxes, scales, pooled=7, min_level=2, canonical_level=4,
                     vals = fl[idx.reshape(-1)].view(n, P, gh * 2, P, gw * 2, C)
                     acc = (vals * wgt.reshape(n, P, gh * 2, P, gw * 2, 1).to(dt)).sum(dim=(2, 4))   # (n,P,P,C)
                     out[sel[mm]] = (acc / max(gh * gw, 1)).permute(0, 3, 1, 2)
+    return out
+
+
+def roi_pool_fpn_batched(feats, rois, scales, pooled=7, min_level=2, canonical_level=4, canonical_size=224.0):
+    """roi_pool_fpn for a batch: rois (R,5) = [image index, x1, y1, x2, y2] -> (R,C,P,P).  The index is truncated towards zero like the
+    kernel's (int) cast; a row whose index lies outside [0, N) gives zeros and sends no gradient (the kernels return early for it)."""
+    n = feats[0].shape[0]
+    out = torch.zeros((rois.shape[0], feats[0].shape[1], pooled, pooled), dtype=feats[0].dtype)
+    index = rois[:, 0].detach().to(torch.int64)
+    for b in range(n):
+        sel = torch.nonzero(index == b).flatten()
+        if len(sel):
+            out[sel] = roi_pool_fpn(feats, rois[sel, 1:], scales, pooled, min_level, canonical_level, canonical_size, image=b)
     return out
 
 
