@@ -273,6 +273,50 @@ int wt_ensemble_slots_dev(const double* xywhs, const int32_t* category, int64_t 
                           double min_score, double* out_xywhs, int32_t* out_category, int64_t* out_counts,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* =================================================================================================
+ * MOT evaluation  (CLEAR-MOT per class and Waymo difficulty level; the definition is in DESIGN.md, "Tracking metric")
+ * ================================================================================================= */
+
+/* Scores K >= 1 tracking results against one ground truth: one wavefront per (result set, stream, class) walks the stream's
+ * frames in order (carry last frame's pairs that still reach the class's IoU threshold, assign the rest with the
+ * linear_assignment of tracking/sort/sort.py:206 on the gated float32 IoU matrix, count).  IoU is float64 on [x, y, x+w, y+h]
+ * in the operation order of tracking/sort/sort.py:34-47.
+ *
+ * Ground truth: SoA rows sorted by (stream, frame, file order) - x, y, w, h float64, category int32 (rows outside
+ * 1..n_classes are skipped), level int32 (2 = LEVEL_2 only, anything else counts at both levels), gt_id int32 = object id
+ * interned per stream to 0..max_gt_ids-1 - with the CSR offsets frame_gt_offsets (n_frames + 1) and stream_frame_offsets
+ * (n_streams + 1); the frames of a stream ascend.  An id occurs at most once per frame.
+ * Results: the K sets concatenated; set k owns rows set_row_offsets[k] .. set_row_offsets[k + 1] and lists first the rows on
+ * the ground truth's frames, sorted like the ground truth, with frame_hyp_offsets[k * (n_frames + 1) + f] their offsets inside
+ * the set, then the rows that take no part (other frames, unknown streams).  h_id int32 >= 0 = object id interned per (set,
+ * stream); an id occurs at most once per frame and class.
+ * thr: n_classes <= 16 IoU thresholds, host pointer, read before the call returns.
+ * max_frame_boxes: upper bound of the boxes of ONE class in one frame on either side (<= 4096, more is WT_ERR_CAPACITY).
+ * Outputs: counts (K, n_streams, n_classes, 2, 5) int64 = gt, tp, fn, fp, idsw for LEVEL_1, LEVEL_2;
+ *          iou_sum (K, n_streams, n_classes, 2) float64, summed in frame order, then ground-truth row order;
+ *          hyp_match (per result row, may be NULL): matched ground-truth row, -1 false positive, -2 took no part;
+ *          hyp_switch (per result row, may be NULL): 1 where the match is an identity switch.
+ * The device form also reports in status_dev (device int32) 0 or the WT_ERR_* a wavefront met (capacity, assignment did
+ * not converge); it does not check the layout, the host form does (WT_ERR_INVALID names the frame). */
+size_t wt_mot_eval_workspace(int32_t k_sets, int32_t n_streams, int32_t n_classes, int64_t max_frame_boxes, int32_t max_gt_ids);
+int wt_mot_eval_dev(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                    const int32_t* g_category, const int32_t* g_level, const int32_t* g_id,
+                    int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                    int32_t k_sets, int64_t n_hyp, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                    const double* hx, const double* hy, const double* hw, const double* hh,
+                    const int32_t* h_category, const int32_t* h_id,
+                    int32_t n_classes, const double* thr, int64_t max_frame_boxes, int32_t max_gt_ids,
+                    int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch, int32_t* status_dev,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int wt_mot_eval_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                     const int32_t* g_category, const int32_t* g_level, const int32_t* g_id,
+                     int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                     int32_t k_sets, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                     const double* hx, const double* hy, const double* hw, const double* hh,
+                     const int32_t* h_category, const int32_t* h_id,
+                     int32_t n_classes, const double* thr,
+                     int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch);
+
 /* --- Waymo Open Dataset protobuf emit (csrc/waymo_proto.hip; host code) -----------------------------------
  * metrics.Objects - and with submission != 0 the Submission envelope around it - written straight from columns: replaces
  * the per-object message building of /root/reference/coco_to_waymo.py:16-82 (create_pd_object / create_pb_submission) and

@@ -1,0 +1,248 @@
+"""HIP tracking metric (csrc/mot_eval.hip through tracking/evaluate.py) against the plain-Python restatement tests/mot_ref.py:
+counts, per-row matches and switches, and the float64 IoU sums must be EQUAL - the summation order is part of the definition."""
+import json
+import math
+
+import numpy as np
+import pytest
+
+import mot_ref
+
+pytestmark = pytest.mark.gpu
+
+SETTINGS = [                       # (max_age, min_hits, score thresholds, tracker IoU thresholds): three different results
+    (2, 0, [0.3, 0.2, 1.0, 0.1], [0.01, 0.01, 1.0, 0.0]),
+    (1, 1, [0.6, 0.6, 1.0, 0.6], [0.3, 0.3, 1.0, 0.3]),
+    (3, 0, [0.0, 0.0, 0.0, 0.0], [0.1, 0.1, 0.1, 0.1]),
+]
+
+
+def _track(dets, max_age, min_hits, score_thr, iou_thr):
+    """Detections list -> the rows tracking/track.py would write, through a JSON round trip like a file."""
+    from waymo_2d_tracking_amd.tracking import utils as T
+    predictions = {}
+    for e in dets:
+        seg, fr, cam = e['image_id'].split('/')
+        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
+            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
+    packed = T.pack_streams(predictions)
+    out, _ = T.track_packed(packed, iou_thr, max_age, min_hits, score_thr)
+    return json.loads(json.dumps(T.format_tracks(packed, out)))
+
+
+@pytest.fixture(scope='module', params=[True, False], ids=['integer_boxes', 'fractional_boxes'])
+def sequence(request):
+    from waymo_2d_tracking_amd import synthetic as syn
+    dets, gt_json = syn.make_tracking_json(11 if request.param else 12, n_segments=1, n_frames=24, n_objects=40,
+                                           integer_boxes=request.param)
+    results = [_track(dets, *s) for s in SETTINGS]
+    return gt_json, results
+
+
+def same_number(a, b):
+    return (a == b) or (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b))
+
+
+def assert_equals_reference(got, ref, n_classes=4):
+    """MotResult (per_row=True) == mot_ref.evaluate() output: everything, exactly."""
+    assert got.stream_keys == ref['stream_keys']
+    for s, key in enumerate(got.stream_keys):
+        for c in range(1, n_classes + 1):
+            for li, lv in enumerate((1, 2)):
+                exp = ref['per_stream'][key][c][lv]
+                assert got.counts[s, c - 1, li].tolist() == [exp[f] for f in mot_ref.FIELDS], (key, c, lv)
+                assert got.iou_sum[s, c - 1, li] == exp['iou_sum'], (key, c, lv, got.iou_sum[s, c - 1, li], exp['iou_sum'])
+    assert got.hyp_match.tolist() == ref['hyp_match']
+    assert got.hyp_switch.tolist() == ref['hyp_switch']
+    assert got.ignored_rows == ref['ignored_rows']
+    for c, rows in ref['table'].items():
+        for lv, row in rows.items():
+            for name, v in row.items():
+                assert same_number(got.table[c][lv][name], v), (c, lv, name, got.table[c][lv][name], v)
+
+
+def test_device_equals_reference_on_tracked_sequences(sequence):
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results = sequence
+    gt = E.load_ground_truth(gt_json)
+    assert len(gt['stream_keys']) == 5
+    got = E.evaluate_tracks(gt, [E.load_tracks(r) for r in results], per_row=True)
+    assert len(got) == 3
+    refs = [mot_ref.evaluate(gt_json, r) for r in results]
+    # the three settings give three different results, with matches, misses, false positives and switches in them
+    assert len(set(json.dumps(r['table']['ALL'][2], sort_keys=True) for r in refs)) == 3
+    all2 = refs[0]['table']['ALL'][2]
+    assert all2['tp'] > 500 and all2['fn'] > 0 and all2['fp'] > 0 and sum(r['table']['ALL'][2]['idsw'] for r in refs) > 0
+    assert refs[0]['table']['ALL'][1]['gt'] < all2['gt']
+    for g, r in zip(got, refs):
+        assert_equals_reference(g, r)
+
+
+def test_k_sets_in_one_call_equal_k_calls_and_dev_equals_host(sequence):
+    import torch
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results = sequence
+    gt = E.load_ground_truth(gt_json)
+    tracks = [E.load_tracks(r) for r in results]
+    together = E.evaluate_tracks(gt, tracks, per_row=True)
+    dev = E.DeviceEvaluation(gt, tracks)
+    dev.launch()
+    from_dev = dev.results(per_row=True)
+    for k, tr in enumerate(tracks):
+        alone = E.evaluate_tracks(gt, [tr], per_row=True)[0]
+        for other in (together[k], from_dev[k]):
+            assert np.array_equal(alone.counts, other.counts) and np.array_equal(alone.iou_sum, other.iou_sum)
+            assert np.array_equal(alone.hyp_match, other.hyp_match) and np.array_equal(alone.hyp_switch, other.hyp_switch)
+            assert alone.ignored_rows == other.ignored_rows
+    # a second launch on the same buffers gives the same answer (the call initialises everything it reads)
+    dev.launch()
+    again = dev.results(per_row=True)
+    assert all(np.array_equal(a.counts, b.counts) and np.array_equal(a.iou_sum, b.iou_sum) and np.array_equal(a.hyp_match, b.hyp_match)
+               for a, b in zip(from_dev, again))
+    torch.cuda.synchronize()
+
+
+def _crowd(rng, frame, n_gt, n_hyp, first_id, cat=1):
+    """One crowded frame: n_gt objects on a grid, n_hyp hypotheses = jittered copies of some of them under fresh ids."""
+    anns, rows = [], []
+    for i in range(n_gt):
+        x, y = 20 + 90 * (i % 20), 20 + 90 * (i // 20)
+        anns.append({'image_id': 'seg/%d/FRONT' % frame, 'bbox': [x, y, 60 + (i % 7), 60 + (i % 5)], 'category_id': cat,
+                     'object_id': 'o%d' % i, 'tracking_difficulty_level': 2 if i % 6 == 0 else 1})
+    for j in range(n_hyp):
+        b = anns[j % n_gt]['bbox']
+        jit = rng.normal(0, 4.0, 4)
+        rows.append({'image_id': 'seg/%d/FRONT' % frame, 'bbox': [b[0] + jit[0], b[1] + jit[1], b[2] + jit[2], b[3] + jit[3]],
+                     'score': 0.9, 'category_id': cat, 'object_id': str(first_id + j)})
+    return anns, rows
+
+
+def test_wide_and_transposed_assignment_paths():
+    """More than 128 boxes a side (the bitmap form of the Munkres), more ground truth than hypotheses (the transposed
+    problem), and 128 x 300 (the wide register form).  Fresh hypothesis ids in every frame: nothing is carried over."""
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    rng = np.random.default_rng(3)
+    anns, rows = [], []
+    for frame, (n_gt, n_hyp) in enumerate([(150, 140), (30, 200), (135, 300), (60, 20)]):
+        a, r = _crowd(rng, frame, n_gt, n_hyp, 1000 * frame, cat=2)
+        anns += a
+        rows += r
+    rows = json.loads(json.dumps(rows))
+    got = E.evaluate_tracks(E.load_ground_truth(anns), [E.load_tracks(rows)], per_row=True)[0]
+    ref = mot_ref.evaluate(anns, rows)
+    assert ref['table'][2][2]['tp'] > 250 and ref['table'][2][2]['fp'] > 100 and ref['table'][2][2]['idsw'] > 100
+    assert_equals_reference(got, ref)
+
+
+def test_ground_truth_against_itself_is_mota_1_at_both_levels(sequence):
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, _ = sequence
+    rows = [{'image_id': a['image_id'], 'bbox': a['bbox'], 'score': 1.0, 'category_id': a['category_id'], 'object_id': a['object_id']}
+            for a in gt_json['annotations'] if a['bbox'][2] >= 1 and a['bbox'][3] >= 1]
+    got = E.evaluate_tracks(E.load_ground_truth(gt_json), [E.load_tracks(rows)])[0]
+    for lv in (1, 2):
+        row = got.table['ALL'][lv]
+        assert row['MOTA'] == 1.0 and row['MOTP'] == 1.0 and row['fn'] == row['fp'] == row['idsw'] == 0 and row['gt'] > 0
+    assert got.table['ALL'][1]['gt'] < got.table['ALL'][2]['gt']
+
+
+def test_capacity_and_duplicate_id_errors(monkeypatch):
+    from waymo_2d_tracking_amd import _lib
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    anns = [{'image_id': 'seg/7/FRONT', 'bbox': [i % 100 * 15, i // 100 * 15, 10, 10], 'category_id': 1, 'object_id': 'o%d' % i}
+            for i in range(4097)]
+    rows = [{'image_id': 'seg/7/FRONT', 'bbox': [0, 0, 10, 10], 'score': 1.0, 'category_id': 1, 'object_id': '1'}]
+    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
+        E.evaluate_tracks(E.load_ground_truth(anns), [E.load_tracks(rows)])
+    # 4096 is allowed (and all of them are missed)
+    got = E.evaluate_tracks(E.load_ground_truth(anns[:4096]), [E.load_tracks([dict(rows[0], bbox=[5000, 5000, 10, 10])])])[0]
+    assert got.table[1][2]['fn'] == 4096 and got.table[1][2]['fp'] == 1
+    dup = rows + [dict(rows[0], bbox=[50, 50, 10, 10])]
+    with pytest.raises(_lib.WaymoTrackError, match=r'WT_ERR_INVALID.*seg/7/FRONT'):
+        E.evaluate_tracks(E.load_ground_truth(anns[:10]), [E.load_tracks(dup)])
+    # the same id in two classes of one frame is two problems, not a duplicate
+    E.evaluate_tracks(E.load_ground_truth(anns[:10]), [E.load_tracks(rows + [dict(rows[0], category_id=2)])])
+    # the library checks it too (a caller of the C entry point gets the same status)
+    monkeypatch.setattr(E, '_check_unique', lambda *a: None)
+    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_INVALID'):
+        E.evaluate_tracks(E.load_ground_truth(anns[:10]), [E.load_tracks(dup)])
+
+
+def test_cli_table_equals_api_on_files_written_by_track(tmp_path, capsys):
+    from waymo_2d_tracking_amd import synthetic as syn
+    from waymo_2d_tracking_amd.tracking import evaluate as E, track
+    dets, gt_json = syn.make_tracking_json(21, n_segments=2, n_frames=12, n_objects=25, cameras=('FRONT', 'SIDE_LEFT'))
+    (tmp_path / 'det.json').write_text(json.dumps(dets))
+    gt_json = dict(gt_json, images=gt_json['images'][::2])           # ground truth for every other frame only
+    (tmp_path / 'gt.json').write_text(json.dumps(gt_json))
+    outs = []
+    for i, flags in enumerate((['--max-age=2', '--min-hits=0', '--score-threshold=0.5,0.5,1.0,0.5'], ['--max-age=1', '--python-io'])):
+        outs.append(str(tmp_path / ('tracks%d.json' % i)))
+        assert track.main(['--input', str(tmp_path / 'det.json'), '--output', outs[-1]] + flags) == 0
+    capsys.readouterr()
+    assert E.main(['--annotations', str(tmp_path / 'gt.json'), '--json', str(tmp_path / 'mota.json')] + outs) == 0
+    printed = capsys.readouterr().out
+    api = E.evaluate_tracks(E.load_ground_truth(str(tmp_path / 'gt.json')), [E.load_tracks(p) for p in outs])
+    assert printed == ''.join(E.format_table(r, p) + '\n' for p, r in zip(outs, api))
+    saved = json.loads((tmp_path / 'mota.json').read_text())
+    for p, r in zip(outs, api):
+        assert r.ignored_rows > 0 and saved[p]['ignored_rows'] == r.ignored_rows
+        ref = mot_ref.evaluate(gt_json, json.loads(open(p).read()))
+        assert ref['ignored_rows'] == r.ignored_rows
+        for c in (1, 2, 4, 'ALL'):
+            for lv in (1, 2):
+                for name, v in ref['table'][c][lv].items():
+                    assert same_number(r.table[c][lv][name], v) and same_number(saved[p]['table'][str(c)]['LEVEL_%d' % lv][name], v)
+
+
+def test_sweep_picks_the_setting_mot_ref_picks(tmp_path, capsys):
+    from waymo_2d_tracking_amd import synthetic as syn
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    dets, gt_json = syn.make_tracking_json(31, n_segments=1, n_frames=16, n_objects=30, cameras=('FRONT', 'FRONT_LEFT'), clutter=0.3)
+    (tmp_path / 'det.json').write_text(json.dumps(dets))
+    (tmp_path / 'gt.json').write_text(json.dumps(gt_json))
+    grid = {'score': [0.2, 0.7], 'iou': [0.01, 0.3], 'max_age': [1, 3], 'min_hits': [0]}
+    res = E.sweep(str(tmp_path / 'det.json'), E.load_ground_truth(gt_json), grid)
+    assert len(res['settings']) == 8 and len(res['results']) == 8
+    # every setting by itself with the reference, then the same rule: per (max_age, min_hits) the best grid point of each class
+    # (fewest errors, first wins), classes combined, highest ALL MOTA wins, first wins
+    refs = {}
+    for max_age in grid['max_age']:
+        for min_hits in grid['min_hits']:
+            for score in grid['score']:
+                for iou in grid['iou']:
+                    rows = _track(dets, max_age, min_hits, [score] * 4, [iou] * 4)
+                    refs[max_age, min_hits, score, iou] = mot_ref.evaluate(gt_json, rows)['table']
+    expected = {}
+    for lv in (1, 2):
+        best = None
+        for max_age in grid['max_age']:
+            for min_hits in grid['min_hits']:
+                total = {'gt': 0, 'err': 0}
+                pick = {}
+                for c in (1, 2, 4):
+                    top = None
+                    for score in grid['score']:
+                        for iou in grid['iou']:
+                            row = refs[max_age, min_hits, score, iou][c][lv]
+                            err = row['fn'] + row['fp'] + row['idsw']
+                            if top is None or err < top[0]:
+                                top = (err, score, iou, row['gt'])
+                    pick[c] = top
+                    total['gt'] += top[3]
+                    total['err'] += top[0]
+                mota = 1.0 - total['err'] / total['gt']
+                if best is None or mota > best[0]:
+                    best = (mota, max_age, min_hits, pick)
+        expected[lv] = best
+    for lv in (1, 2):
+        got, (mota, max_age, min_hits, pick) = res['best'][lv], expected[lv]
+        assert got['MOTA'] == mota and (got['max_age'], got['min_hits']) == (max_age, min_hits)
+        for c in (1, 2, 4):
+            assert (got['score_threshold'][c - 1], got['iou_threshold'][c - 1]) == (pick[c][1], pick[c][2])
+        assert got['score_threshold'][2] == 1.0 and got['iou_threshold'][2] == 1.0
+    # the CLI prints the flag line of the best LEVEL_2 setting last
+    capsys.readouterr()
+    assert E.main(['--annotations', str(tmp_path / 'gt.json'), '--sweep', str(tmp_path / 'det.json'), '--score-grid', '0.2,0.7',
+                   '--iou-grid', '0.01,0.3', '--max-age', '1,3', '--min-hits', '0']) == 0
+    assert capsys.readouterr().out.rstrip('\n').split('\n')[-1] == E.flag_line(res['best'][2])

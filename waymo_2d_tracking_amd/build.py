@@ -28,6 +28,7 @@ UNITS = {
     'ensemble.hip': ['-ffp-contract=off'],
     'sort_engine.hip': ['-ffp-contract=off'],
     'sort_single.hip': ['-ffp-contract=off'],
+    'mot_eval.hip': ['-ffp-contract=off'],             # CLEAR-MOT evaluation: float64 IoU in the reference's operation order
     'det_roialign.hip': [],
     'det_nms.hip': [],
     'det_deform.hip': [],

@@ -113,6 +113,95 @@ def make_sequence_json(seed, n_segments=1, n_frames=198, n_objects=100, cameras=
     return detections_json(streams, integer_boxes=kw.get('integer_boxes', True))
 
 
+def stream_with_ground_truth(rng, n_frames, n_objects, camera='FRONT', jitter=2.0, dropout=0.1, clutter=0.1,
+                             level2_share=0.2, score_lo=0.01, integer_boxes=True):
+    """One (segment, camera) stream together with the ground truth its detections were drawn from (tracking/evaluate.py).
+
+    Returns (det, gt): det as stream_detections(); gt = per-box arrays sorted by frame: frame, cat, x, y, w, h, object
+    (index of the object inside the stream) and level (1, or 2 for the level2_share of objects that are hard to track).
+    Objects have lifetimes; the ground-truth box is the object's true box in every frame it lives in, detected or not.
+    A generator of its own: stream_detections() keeps its random stream (committed fixtures were made from it)."""
+    width, height = IMAGE_SIZES[camera]
+    obj = make_objects(rng, n_objects, n_frames, width, height, lifetimes=True)
+    level = np.where(rng.uniform(size=n_objects) < level2_share, 2, 1)
+    det = {k: [] for k in ('frame', 'cat', 'x', 'y', 'w', 'h', 'score')}
+    gt = {k: [] for k in ('frame', 'cat', 'x', 'y', 'w', 'h', 'object', 'level')}
+    for f in range(n_frames):
+        alive = np.nonzero((obj['start'] <= f) & (f < obj['end']))[0]
+        tx = obj['cx'][alive] + obj['vx'][alive] * f - obj['w'][alive] / 2
+        ty = obj['cy'][alive] + obj['vy'][alive] * f - obj['h'][alive] / 2
+        tw, th = obj['w'][alive], obj['h'][alive]
+        if integer_boxes:                           # waymo_to_coco.py:66-69 int()
+            tx, ty, tw, th = np.trunc(tx), np.trunc(ty), np.trunc(tw), np.trunc(th)
+        gt['frame'].append(np.full(alive.size, f, dtype=np.int64)); gt['cat'].append(obj['cls'][alive].astype(np.int64))
+        gt['x'].append(tx); gt['y'].append(ty); gt['w'].append(tw); gt['h'].append(th)
+        gt['object'].append(alive.astype(np.int64)); gt['level'].append(level[alive].astype(np.int64))
+        idx = alive[rng.uniform(size=alive.size) >= dropout]
+        cx = obj['cx'][idx] + obj['vx'][idx] * f + rng.normal(0, jitter, idx.size)
+        cy = obj['cy'][idx] + obj['vy'][idx] * f + rng.normal(0, jitter, idx.size)
+        w = np.maximum(obj['w'][idx] + rng.normal(0, jitter, idx.size), 2)
+        h = np.maximum(obj['h'][idx] + rng.normal(0, jitter, idx.size), 2)
+        c = obj['cls'][idx]
+        n_clutter = rng.binomial(n_objects, clutter)
+        cw = rng.uniform(20, 300, n_clutter)
+        ch = rng.uniform(20, 300, n_clutter)
+        cx = np.concatenate([cx, rng.uniform(cw / 2, width - cw / 2)]); cy = np.concatenate([cy, rng.uniform(ch / 2, height - ch / 2)])
+        w = np.concatenate([w, cw]); h = np.concatenate([h, ch])
+        c = np.concatenate([c, CLASS_IDS[rng.choice(3, size=n_clutter, p=CLASS_P)]])
+        # true objects score high, clutter anywhere: a score threshold has something to separate
+        s = np.concatenate([rng.uniform(0.5, 1.0, idx.size), rng.uniform(score_lo, 1.0, n_clutter)])
+        perm = rng.permutation(cx.size)
+        cx, cy, w, h, c, s = cx[perm], cy[perm], w[perm], h[perm], c[perm], s[perm]
+        x, y = cx - w / 2, cy - h / 2
+        if integer_boxes:
+            x, y, w, h = np.trunc(x), np.trunc(y), np.trunc(w), np.trunc(h)
+            s = np.round(s, 5)
+        det['frame'].append(np.full(cx.size, f, dtype=np.int64)); det['cat'].append(c.astype(np.int64))
+        det['x'].append(x); det['y'].append(y); det['w'].append(w); det['h'].append(h); det['score'].append(s)
+    cat = lambda a: np.concatenate(a) if a else np.zeros(0)
+    det = {k: cat(v) for k, v in det.items()}
+    gt = {k: cat(v) for k, v in gt.items()}
+    for d in (det, gt):
+        d['frame'] = d['frame'].astype(np.int64); d['cat'] = d['cat'].astype(np.int64)
+    gt['object'] = gt['object'].astype(np.int64); gt['level'] = gt['level'].astype(np.int64)
+    return det, gt
+
+
+def ground_truth_json(streams, integer_boxes=True, n_frames=None):
+    """streams: list of (segment_id, camera, gt-dict from stream_with_ground_truth) -> the COCO dict waymo_to_coco.py
+    writes (the reference's waymo_to_coco.py:58,72-76): 'images' (every frame when n_frames is given) and 'annotations'."""
+    images, annotations = [], []
+    for segment, camera, g in streams:
+        width, height = IMAGE_SIZES[camera]
+        frames = range(n_frames) if n_frames is not None else sorted(set(g['frame'].tolist()))
+        for f in frames:
+            image_id = '%s/%i/%s' % (segment, frame_timestamp(f), camera)
+            images.append({'file_name': image_id + '.jpg', 'id': image_id, 'height': height, 'width': width})
+        for i in range(g['frame'].size):
+            if integer_boxes:
+                bbox = [int(g['x'][i]), int(g['y'][i]), int(g['w'][i]), int(g['h'][i])]
+            else:
+                bbox = [float(g['x'][i]), float(g['y'][i]), float(g['w'][i]), float(g['h'][i])]
+            annotations.append({'image_id': '%s/%i/%s' % (segment, frame_timestamp(g['frame'][i]), camera), 'bbox': bbox,
+                                'area': bbox[2] * bbox[3], 'category_id': int(g['cat'][i]),
+                                'object_id': '%s_%s_%d' % (segment[:13], camera, int(g['object'][i])),
+                                'tracking_difficulty_level': int(g['level'][i]), 'id': len(annotations)})
+    return {'images': images, 'annotations': annotations}
+
+
+def make_tracking_json(seed, n_segments=1, n_frames=198, n_objects=100, cameras=CAMERAS, **kw):
+    """Config-1 shaped detections AND their ground truth: (detections list, ground-truth COCO dict)."""
+    rng = np.random.default_rng(seed)
+    dets, gts = [], []
+    for s in range(n_segments):
+        seg = 'segment-%05d_with_camera_labels' % s
+        for cam in cameras:
+            d, g = stream_with_ground_truth(rng, n_frames, n_objects, cam, **kw)
+            dets.append((seg, cam, d)); gts.append((seg, cam, g))
+    integer = kw.get('integer_boxes', True)
+    return detections_json(dets, integer_boxes=integer), ground_truth_json(gts, integer_boxes=integer, n_frames=n_frames)
+
+
 def ensemble_group(rng, n_objects, k_inputs, jitter=3.0, width=1920, height=1280):
     """K jittered copies of the same objects of one class in one image ->
     list of K arrays (n_i, 5) [score, x_left, y_top, w, h] float64 (tie-free scores)."""

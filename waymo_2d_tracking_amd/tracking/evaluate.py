@@ -1,0 +1,526 @@
+"""MOTA / MOTP of tracking results against ground truth, and the threshold sweep that tunes the tracker's flags.
+
+    python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
+        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT]
+    python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1
+
+The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
+has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
+kernel behind ``wt_mot_eval_host`` (include/waymotrack.h): K results are scored in one launch, which is what makes a
+sweep over tracker settings cost seconds.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
+"""
+import argparse
+import ctypes as C
+import json
+import math
+
+import numpy as np
+
+from .. import _lib
+from . import utils as T
+
+DEFAULT_IOU_THRESHOLD = (0.7, 0.5, 0.5, 0.5)       # Waymo: 0.7 vehicles, 0.5 pedestrians and cyclists
+ALL_CLASSES = (1, 2, 4)                            # the three evaluated types (3 = sign is not tracked)
+FIELDS = ('gt', 'tp', 'fn', 'fp', 'idsw')
+LEVELS = (1, 2)
+
+
+def _floats(s):
+    return [float(item) for item in s.split(',')]
+
+
+def _split(image_id):
+    segment_id, frame_id, camera_id = image_id.split('/')
+    return segment_id, int(frame_id), camera_id
+
+
+def _columns(rows, stream_index, with_level):
+    n = len(rows)
+    stream = np.zeros(n, np.int64)
+    frame = np.zeros(n, np.int64)
+    box = np.zeros((n, 4), np.float64)
+    cat = np.zeros(n, np.int32)
+    level = np.ones(n, np.int32)
+    oid = np.empty(n, dtype=object)
+    for i, e in enumerate(rows):
+        segment_id, frame_id, camera_id = _split(e['image_id'])
+        key = (segment_id, camera_id)
+        s = stream_index.get(key)
+        if s is None:
+            s = stream_index[key] = len(stream_index)
+        stream[i] = s
+        frame[i] = frame_id
+        box[i] = e['bbox']
+        cat[i] = e['category_id']
+        oid[i] = str(e['object_id'])
+        if with_level and e.get('tracking_difficulty_level', 1) == 2:
+            level[i] = 2
+    return stream, frame, box, cat, level, oid
+
+
+def _dense_ids(stream, oid, per_stream):
+    """Object ids -> int32, equal ids inside a stream <-> equal numbers; per_stream: numbered from 0 in every stream."""
+    if oid.size == 0:
+        return np.zeros(0, np.int32), 0
+    _, inv = np.unique(oid.astype(str), return_inverse=True)
+    n_names = int(inv.max()) + 1
+    pair, ids = np.unique(stream * n_names + inv, return_inverse=True)
+    if not per_stream:
+        return ids.astype(np.int32), int(pair.size)
+    first = np.searchsorted(pair // n_names, np.arange(int(stream.max()) + 1))
+    ids = ids - first[stream]
+    return ids.astype(np.int32), int(ids.max()) + 1
+
+
+def load_ground_truth(path_or_json):
+    """Ground-truth COCO file (dict with 'annotations' and optionally 'images', or a bare list) -> packed columns.
+
+    Streams are numbered by first appearance; a stream's frames are those of 'images' when the file has that list,
+    otherwise those that carry at least one annotation.  Rows with w < 1 or h < 1 are dropped (tracking/utils.py:79)."""
+    data = path_or_json
+    if isinstance(path_or_json, str):
+        with open(path_or_json) as fp:
+            data = json.load(fp)
+    annotations = data['annotations'] if isinstance(data, dict) else data
+    images = data.get('images') if isinstance(data, dict) else None
+    stream_index = {}
+    if images is not None:
+        im_stream = np.zeros(len(images), np.int64)
+        im_frame = np.zeros(len(images), np.int64)
+        for i, im in enumerate(images):
+            segment_id, frame_id, camera_id = _split(im['id'])
+            im_stream[i] = stream_index.setdefault((segment_id, camera_id), len(stream_index))
+            im_frame[i] = frame_id
+    stream, frame, box, cat, level, oid = _columns(annotations, stream_index, True)
+    if images is None:
+        im_stream, im_frame = stream, frame
+    n_streams = len(stream_index)
+    # frames: unique (stream, frame id), streams in first-appearance order, frame ids ascending
+    frame_values = np.unique(np.concatenate([im_frame, frame]))
+    nv = max(1, frame_values.size)
+    fkeys = np.unique(im_stream * nv + np.searchsorted(frame_values, im_frame))
+    frame_stream = fkeys // nv
+    frame_ids = frame_values[fkeys % nv] if fkeys.size else np.zeros(0, np.int64)
+    stream_frame_offsets = np.searchsorted(frame_stream, np.arange(n_streams + 1)).astype(np.int64)
+    row_key = stream * nv + np.searchsorted(frame_values, frame)
+    pos = np.searchsorted(fkeys, row_key)
+    on_frame = np.zeros(row_key.size, bool)         # with 'images', an annotation on a frame outside that list takes no part
+    if fkeys.size:
+        on_frame = (pos < fkeys.size) & (fkeys[np.minimum(pos, fkeys.size - 1)] == row_key)
+    keep = on_frame & ~((box[:, 2] < 1) | (box[:, 3] < 1))
+    src = np.nonzero(keep)[0]
+    order = src[np.argsort(pos[src], kind='stable')]
+    gframe = pos[order]
+    gt_id, max_ids = _dense_ids(stream[order], oid[order], per_stream=True)
+    frame_gt_offsets = np.searchsorted(gframe, np.arange(fkeys.size + 1)).astype(np.int64)
+    keys = [None] * n_streams
+    for key, s in stream_index.items():
+        keys[s] = key
+    return dict(
+        x=np.ascontiguousarray(box[order, 0]), y=np.ascontiguousarray(box[order, 1]),
+        w=np.ascontiguousarray(box[order, 2]), h=np.ascontiguousarray(box[order, 3]),
+        category=np.ascontiguousarray(cat[order]), level=np.ascontiguousarray(level[order]), gt_id=gt_id, max_gt_ids=max_ids,
+        source_row=order.astype(np.int64), frame_gt_offsets=frame_gt_offsets, stream_frame_offsets=stream_frame_offsets,
+        frame_ids=frame_ids.astype(np.int64), frame_values=frame_values, frame_keys=fkeys, stream_keys=keys,
+        stream_index=dict((k, i) for i, k in enumerate(keys)))
+
+
+def load_tracks(path_or_rows):
+    """Tracking JSON as tracking/track.py writes it -> columns in file order (streams numbered on their own)."""
+    rows = path_or_rows
+    if isinstance(path_or_rows, str):
+        with open(path_or_rows) as fp:
+            rows = json.load(fp)
+    stream_index = {}
+    stream, frame, box, cat, _, oid = _columns(rows, stream_index, False)
+    keys = [None] * len(stream_index)
+    for key, s in stream_index.items():
+        keys[s] = key
+    return dict(stream=stream, frame_id=frame, x=box[:, 0].copy(), y=box[:, 1].copy(), w=box[:, 2].copy(), h=box[:, 3].copy(),
+                category=cat, object_id=oid, stream_keys=keys)
+
+
+def tracks_from_packed(packed, out):
+    """Output of utils.track_packed -> the columns load_tracks() gives for the file track.py would write from it."""
+    f = np.asarray(out['frame'], dtype=np.int64)
+    stream = np.searchsorted(packed['stream_frame_offsets'], f, side='right') - 1
+    bbox = np.asarray(out['bbox'], dtype=np.float64).reshape(-1, 4)
+    return dict(stream=stream.astype(np.int64), frame_id=np.asarray(packed['frame_ids'], dtype=np.int64)[f],
+                x=bbox[:, 0].copy(), y=bbox[:, 1].copy(), w=bbox[:, 2].copy(), h=bbox[:, 3].copy(),
+                category=np.asarray(out['category'], dtype=np.int32), object_id=np.asarray(out['object_id']),
+                stream_keys=list(packed['stream_keys']))
+
+
+def _align(gt, tr, n_classes):
+    """Rows of one result in the kernel's order: those on the ground truth's frames sorted by frame (file order inside),
+    then the ignored ones.  Returns (order, frame_hyp_offsets, h_id)."""
+    n = int(tr['stream'].size)
+    n_frames = int(gt['frame_ids'].size)
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros(n_frames + 1, np.int64), np.zeros(0, np.int32)
+    to_gt = np.asarray([gt['stream_index'].get(k, -1) for k in tr['stream_keys']] + [-1], dtype=np.int64)
+    s = to_gt[tr['stream']]
+    fv, fkeys = gt['frame_values'], gt['frame_keys']
+    nv = max(1, fv.size)
+    r = np.searchsorted(fv, tr['frame_id'])
+    known = (s >= 0) & (r < fv.size)
+    if fv.size:
+        known &= fv[np.minimum(r, fv.size - 1)] == tr['frame_id']
+    key = np.where(known, s * nv + r, -1)
+    pos = np.searchsorted(fkeys, key)
+    if fkeys.size:
+        known &= (pos < fkeys.size) & (fkeys[np.minimum(pos, fkeys.size - 1)] == key)
+    else:
+        known &= False
+    known &= (tr['category'] >= 1) & (tr['category'] <= n_classes)
+    pos = np.where(known, pos, n_frames)
+    order = np.argsort(pos, kind='stable')
+    offsets = np.searchsorted(pos[order], np.arange(n_frames + 1)).astype(np.int64)
+    oid = tr['object_id']
+    if oid.dtype == object or oid.dtype.kind in 'US':
+        h_id, _ = _dense_ids(tr['stream'], oid, per_stream=False)
+    else:                                            # integer ids straight from the tracker: unique over the whole result
+        _, h_id = np.unique(oid, return_inverse=True)
+        h_id = h_id.astype(np.int32)
+    return order.astype(np.int64), offsets, np.ascontiguousarray(h_id[order])
+
+
+def _check_unique(gt, tr, order, offsets, h_id, set_index):
+    """An object id twice in one frame of one class: no metric is defined (WT_ERR_INVALID, with the image id)."""
+    n_on = int(offsets[-1])
+    if n_on == 0:
+        return
+    frame = np.searchsorted(offsets, np.arange(n_on), side='right') - 1
+    cat = tr['category'][order[:n_on]].astype(np.int64)
+    key = (frame * 64 + cat) * (int(h_id.max()) + 1) + h_id[:n_on]
+    u, first, count = np.unique(key, return_index=True, return_counts=True)
+    if (count > 1).any():
+        i = int(first[np.argmax(count > 1)])
+        f = int(frame[i])
+        s = int(np.searchsorted(gt['stream_frame_offsets'], f, side='right') - 1)
+        segment_id, camera_id = gt['stream_keys'][s]
+        raise _lib.WaymoTrackError('wt_mot_eval failed: WT_ERR_INVALID (result %d: object_id %s occurs twice in image %s/%d/%s)'
+                                   % (set_index, tr['object_id'][order[i]], segment_id, int(gt['frame_ids'][f]), camera_id))
+
+
+class MotResult(object):
+    """Scores of one tracking result.
+
+    counts    (n_streams, n_classes, 2, 5) int64: gt, tp, fn, fp, idsw for LEVEL_1, LEVEL_2, per stream
+    iou_sum   (n_streams, n_classes, 2) float64
+    table     {class id or 'ALL': {1: row, 2: row}}, row = gt, tp, fn, fp, idsw, iou_sum, MOTA, MOTP ('ALL' = classes 1, 2, 4)
+    ignored_rows   result rows that took no part (frames or streams the ground truth does not have)
+    hyp_match / hyp_switch (with per_row=True), one entry per result row in file order: index of the matched annotation in the
+        ground-truth file's list (-1 false positive, -2 ignored) and 1 where that match is an identity switch."""
+
+    def __init__(self, counts, iou_sum, ignored_rows, stream_keys, hyp_match=None, hyp_switch=None):
+        self.counts, self.iou_sum, self.ignored_rows, self.stream_keys = counts, iou_sum, ignored_rows, stream_keys
+        self.hyp_match, self.hyp_switch = hyp_match, hyp_switch
+        self.table = {}
+        n_classes = counts.shape[1]
+        for c in list(range(1, n_classes + 1)) + ['ALL']:
+            self.table[c] = {}
+            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
+            for li, lv in enumerate(LEVELS):
+                sel = counts[:, [cc - 1 for cc in classes], li, :]
+                row = dict((f, int(sel[..., fi].sum())) for fi, f in enumerate(FIELDS))
+                # the order of this sum is part of the definition: class by class, stream by stream (cumsum adds one by one)
+                parts = np.concatenate([iou_sum[:, cc - 1, li] for cc in classes]) if classes else np.zeros(0)
+                total = float(np.cumsum(parts)[-1]) if parts.size else 0.0
+                row['iou_sum'] = total
+                row['MOTA'] = 1.0 - (row['fn'] + row['fp'] + row['idsw']) / row['gt'] if row['gt'] else math.nan
+                row['MOTP'] = total / row['tp'] if row['tp'] else math.nan
+                self.table[c][lv] = row
+
+    def mota(self, level=2, category='ALL'):
+        return self.table[category][level]['MOTA']
+
+    def as_json(self):
+        return {'ignored_rows': int(self.ignored_rows),
+                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
+
+
+def pack_results(gt, tracks_list, n_classes):
+    """K results -> the concatenated columns and offsets wt_mot_eval_* takes (include/waymotrack.h)."""
+    if len(tracks_list) < 1:
+        raise ValueError('at least one result is needed')
+    orders, offsets, cols = [], [], dict((k, []) for k in ('x', 'y', 'w', 'h', 'category', 'h_id'))
+    set_rows = [0]
+    for k, tr in enumerate(tracks_list):
+        order, off, h_id = _align(gt, tr, n_classes)
+        _check_unique(gt, tr, order, off, h_id, k)
+        orders.append(order)
+        offsets.append(off)
+        for name in ('x', 'y', 'w', 'h'):
+            cols[name].append(np.asarray(tr[name], dtype=np.float64)[order])
+        cols['category'].append(np.asarray(tr['category'], dtype=np.int32)[order])
+        cols['h_id'].append(h_id)
+        set_rows.append(set_rows[-1] + int(order.size))
+    out = dict((n, np.ascontiguousarray(np.concatenate(cols[n]), dtype=np.float64)) for n in ('x', 'y', 'w', 'h'))
+    out['category'] = np.ascontiguousarray(np.concatenate(cols['category']), dtype=np.int32)
+    out['h_id'] = np.ascontiguousarray(np.concatenate(cols['h_id']), dtype=np.int32)
+    out['set_row_offsets'] = np.asarray(set_rows, dtype=np.int64)
+    out['frame_hyp_offsets'] = np.ascontiguousarray(np.stack(offsets), dtype=np.int64)
+    out['orders'] = orders
+    return out
+
+
+def max_frame_boxes(gt, packed, n_classes):
+    """Most boxes of one class in one frame, on either side (sizes the kernel's per-wavefront scratch)."""
+    n_frames = int(gt['frame_ids'].size)
+    best = 0
+
+    def side(cat, frame_offsets):
+        n = int(frame_offsets[-1])
+        if n == 0:
+            return 0
+        frame = np.searchsorted(frame_offsets, np.arange(n), side='right') - 1
+        ok = (cat[:n] >= 1) & (cat[:n] <= n_classes)
+        return int(np.bincount(frame[ok] * n_classes + cat[:n][ok] - 1, minlength=1).max()) if ok.any() else 0
+    best = side(gt['category'], gt['frame_gt_offsets']) if n_frames else 0
+    for k in range(packed['frame_hyp_offsets'].shape[0]):
+        lo = int(packed['set_row_offsets'][k])
+        best = max(best, side(packed['category'][lo:], packed['frame_hyp_offsets'][k]))
+    return best
+
+
+def _results(gt, packed, counts, iou_sum, hyp_match, hyp_switch, per_row):
+    results = []
+    set_rows = packed['set_row_offsets']
+    for k in range(len(set_rows) - 1):
+        lo, hi = int(set_rows[k]), int(set_rows[k + 1])
+        m = hyp_match[lo:hi]
+        match = switch = None
+        if per_row:                                  # back to the file's row order, ground-truth rows as annotation indices
+            order = packed['orders'][k]
+            match = np.empty(hi - lo, np.int64)
+            match[order] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
+            switch = np.empty(hi - lo, np.uint8)
+            switch[order] = hyp_switch[lo:hi]
+        results.append(MotResult(counts[k], iou_sum[k], int((m == -2).sum()), gt['stream_keys'], match, switch))
+    return results
+
+
+def evaluate_tracks(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False):
+    """Score K tracking results (load_tracks / tracks_from_packed) against one ground truth (load_ground_truth) in ONE
+    wt_mot_eval_host call.  Returns a list of K MotResult."""
+    lib = _lib.lib()
+    thr = _lib.as_f64(iou_threshold)
+    n_classes = int(thr.size)
+    p = pack_results(gt, tracks_list, n_classes)
+    K = len(tracks_list)
+    n_frames = int(gt['frame_ids'].size)
+    n_streams = len(gt['stream_keys'])
+    counts = np.zeros((K, n_streams, n_classes, 2, 5), np.int64)
+    iou_sum = np.zeros((K, n_streams, n_classes, 2), np.float64)
+    n_hyp = int(p['set_row_offsets'][-1])
+    hyp_match = np.full(n_hyp, -2, np.int64)
+    hyp_switch = np.zeros(n_hyp, np.uint8)
+    rc = lib.wt_mot_eval_host(
+        C.c_int64(gt['x'].size), _lib.ptr(gt['x']), _lib.ptr(gt['y']), _lib.ptr(gt['w']), _lib.ptr(gt['h']),
+        _lib.ptr(gt['category']), _lib.ptr(gt['level']), _lib.ptr(gt['gt_id']),
+        C.c_int64(n_frames), _lib.ptr(gt['frame_gt_offsets']), C.c_int32(n_streams), _lib.ptr(gt['stream_frame_offsets']),
+        C.c_int32(K), _lib.ptr(p['set_row_offsets']), _lib.ptr(p['frame_hyp_offsets']),
+        _lib.ptr(p['x']), _lib.ptr(p['y']), _lib.ptr(p['w']), _lib.ptr(p['h']), _lib.ptr(p['category']), _lib.ptr(p['h_id']),
+        C.c_int32(n_classes), _lib.ptr(thr), _lib.ptr(counts), _lib.ptr(iou_sum),
+        _lib.ptr(hyp_match), _lib.ptr(hyp_switch) if per_row else None)
+    _lib.check(rc, 'wt_mot_eval_host')
+    return _results(gt, p, counts, iou_sum, hyp_match, hyp_switch, per_row)
+
+
+class DeviceEvaluation(object):
+    """The same evaluation with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues one
+    wt_mot_eval_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.
+    This is the form a device-resident sweep (tracker output scored without leaving the GPU) builds on; the layout checks of
+    the host form are done here when the inputs are packed."""
+
+    def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD):
+        import torch
+        self.torch = torch
+        self.lib = _lib.lib()
+        self.gt = gt
+        self.thr = _lib.as_f64(iou_threshold)
+        self.n_classes = int(self.thr.size)
+        self.p = pack_results(gt, tracks_list, self.n_classes)
+        self.K = len(tracks_list)
+        self.n_frames = int(gt['frame_ids'].size)
+        self.n_streams = len(gt['stream_keys'])
+        self.n_hyp = int(self.p['set_row_offsets'][-1])
+        self.max_boxes = max_frame_boxes(gt, self.p, self.n_classes)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros(1, dtype=torch.from_numpy(a).dtype, device=dev)
+        self.g = dict((n, up(gt[n])) for n in ('x', 'y', 'w', 'h', 'category', 'level', 'gt_id', 'frame_gt_offsets', 'stream_frame_offsets'))
+        self.h = dict((n, up(self.p[n])) for n in ('x', 'y', 'w', 'h', 'category', 'h_id', 'set_row_offsets', 'frame_hyp_offsets'))
+        self.counts = torch.zeros((self.K, self.n_streams, self.n_classes, 2, 5), dtype=torch.int64, device=dev)
+        self.iou_sum = torch.zeros((self.K, self.n_streams, self.n_classes, 2), dtype=torch.float64, device=dev)
+        self.hyp_match = torch.zeros(max(1, self.n_hyp), dtype=torch.int64, device=dev)
+        self.hyp_switch = torch.zeros(max(1, self.n_hyp), dtype=torch.uint8, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.lib.wt_mot_eval_workspace.restype = C.c_size_t
+        self.ws_bytes = int(self.lib.wt_mot_eval_workspace(C.c_int32(self.K), C.c_int32(self.n_streams), C.c_int32(self.n_classes),
+                                                           C.c_int64(self.max_boxes), C.c_int32(int(gt['max_gt_ids']))))
+        if not self.ws_bytes:
+            _lib.check(4, 'wt_mot_eval_workspace')
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+
+    def launch(self):
+        g, h, v = self.g, self.h, C.c_void_p
+        d = lambda t: v(t.data_ptr())
+        rc = self.lib.wt_mot_eval_dev(
+            C.c_int64(self.gt['x'].size), d(g['x']), d(g['y']), d(g['w']), d(g['h']), d(g['category']), d(g['level']), d(g['gt_id']),
+            C.c_int64(self.n_frames), d(g['frame_gt_offsets']), C.c_int32(self.n_streams), d(g['stream_frame_offsets']),
+            C.c_int32(self.K), C.c_int64(self.n_hyp), d(h['set_row_offsets']), d(h['frame_hyp_offsets']),
+            d(h['x']), d(h['y']), d(h['w']), d(h['h']), d(h['category']), d(h['h_id']),
+            C.c_int32(self.n_classes), _lib.ptr(self.thr), C.c_int64(self.max_boxes), C.c_int32(int(self.gt['max_gt_ids'])),
+            d(self.counts), d(self.iou_sum), d(self.hyp_match), d(self.hyp_switch), d(self.status),
+            d(self.ws), C.c_size_t(self.ws_bytes), v(self.torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, 'wt_mot_eval_dev')
+
+    def results(self, per_row=False):
+        self.torch.cuda.current_stream().synchronize()
+        st = int(self.status.item())
+        if st:
+            raise _lib.WaymoTrackError('wt_mot_eval_dev failed: %s (status reported by the kernel)' % _lib._STATUS.get(st, st))
+        return _results(self.gt, self.p, self.counts.cpu().numpy(), self.iou_sum.cpu().numpy(),
+                        self.hyp_match.cpu().numpy()[:self.n_hyp], self.hyp_switch.cpu().numpy()[:self.n_hyp], per_row)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# threshold sweep
+def _grid_values(text):
+    """'0.5:1.0:0.05' (inclusive range) or '0.0,0.01,0.1' -> list of floats."""
+    if ':' in text:
+        lo, hi, step = (float(v) for v in text.split(':'))
+        n = int(math.floor((hi - lo) / step + 1e-9)) + 1
+        return [round(lo + i * step, 10) for i in range(n)]
+    return [float(v) for v in text.split(',')]
+
+
+def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4):
+    """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
+
+    grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
+    and 'min_hits'.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
+    thresholds and on (max_age, min_hits): every tracked setting uses ONE (score, iou) grid point for all classes -
+    K = |score| x |iou| x |max_age| x |min_hits| settings - and the best point is read off per class for each
+    (max_age, min_hits); no product over classes is tracked.  Best = highest ALL MOTA at the level; ties go to the setting that
+    comes first in grid order (max_age, min_hits, then per class score, iou).
+    Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}}."""
+    if isinstance(gt, str):
+        gt = load_ground_truth(gt)
+    with open(detections_path) as fp:
+        raw = json.load(fp)
+    if 'annotations' in raw:
+        raw = raw['annotations']
+    entries = {}                                     # read_data_file without the score filter: the kernel applies it per setting
+    for entry in raw:
+        segment_id, frame_id, camera_id = _split(entry['image_id'])
+        bucket = entries.setdefault(segment_id, {}).setdefault(camera_id, {}).setdefault(frame_id, [])
+        bbox = entry['bbox']
+        if bbox[2] < 1 or bbox[3] < 1:
+            continue
+        bucket.append({'bbox': bbox, 'score': entry['score'] if 'score' in entry else 1.0, 'category_id': entry['category_id']})
+    packed = T.pack_streams(entries)
+    settings, tracks = [], []
+    for max_age in grid['max_age']:
+        for min_hits in grid['min_hits']:
+            for score in grid['score']:
+                for iou in grid['iou']:
+                    out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
+                    settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)})
+                    tracks.append(tracks_from_packed(packed, out))
+    results = evaluate_tracks(gt, tracks, iou_threshold)
+    classes = [c for c in ALL_CLASSES if c <= n_classes]
+    ranked, best = {}, {}
+    per_mm = len(grid['score']) * len(grid['iou'])
+    for lv in LEVELS:
+        combos = []
+        for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
+            pick, total = {}, dict((f, 0) for f in FIELDS)
+            for c in classes:
+                top = None
+                for k in range(g, g + per_mm):
+                    row = results[k].table[c][lv]
+                    errors = row['fn'] + row['fp'] + row['idsw']       # gt is the same for every setting: fewest errors = highest MOTA
+                    if top is None or errors < top[0]:
+                        top = (errors, k)
+                pick[c] = top[1]
+                for f in FIELDS:
+                    total[f] += results[top[1]].table[c][lv][f]
+            mota = 1.0 - (total['fn'] + total['fp'] + total['idsw']) / total['gt'] if total['gt'] else math.nan
+            score_thr, iou_thr = [1.0] * n_classes, [1.0] * n_classes      # classes that are not evaluated are not tracked
+            for c in classes:
+                score_thr[c - 1], iou_thr[c - 1] = settings[pick[c]]['score'], settings[pick[c]]['iou']
+            combos.append({'max_age': settings[g]['max_age'], 'min_hits': settings[g]['min_hits'], 'score_threshold': score_thr,
+                           'iou_threshold': iou_thr, 'MOTA': mota, 'counts': total})
+        order = sorted(range(len(combos)), key=lambda i: (-(combos[i]['MOTA'] if combos[i]['MOTA'] == combos[i]['MOTA'] else -math.inf), i))
+        ranked[lv] = [combos[i] for i in order]
+        best[lv] = ranked[lv][0] if ranked[lv] else None
+    return {'settings': settings, 'results': results, 'ranked': ranked, 'best': best}
+
+
+def flag_line(setting):
+    """The tracking/track.py flags of a sweep result."""
+    join = lambda v: ','.join(repr(float(x)) for x in v)
+    return '--score-threshold=%s --iou-threshold=%s --max-age=%d --min-hits=%d' % (
+        join(setting['score_threshold']), join(setting['iou_threshold']), setting['max_age'], setting['min_hits'])
+
+
+def format_table(result, name=''):
+    lines = ['%s  (ignored rows: %d)' % (name, result.ignored_rows),
+             '%-6s %-8s %9s %9s %9s %9s %7s %9s %9s' % ('class', 'level', 'gt', 'tp', 'fn', 'fp', 'idsw', 'MOTA', 'MOTP')]
+    for c, rows in result.table.items():
+        for lv in LEVELS:
+            r = rows[lv]
+            lines.append('%-6s LEVEL_%d  %9d %9d %9d %9d %7d %9.5f %9.5f' % (c, lv, r['gt'], r['tp'], r['fn'], r['fp'], r['idsw'],
+                                                                         r['MOTA'], r['MOTP']))
+    return '\n'.join(lines)
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument('tracks', nargs='*', help='tracking JSON files written by tracking/track.py')
+    parser.add_argument('--annotations', required=True, help='ground-truth COCO json (waymo_to_coco.py)')
+    parser.add_argument('--iou-threshold', type=_floats, default=list(DEFAULT_IOU_THRESHOLD), help='matching IoU per class')
+    parser.add_argument('--json', help='write the tables (or the sweep) to this file')
+    parser.add_argument('--sweep', help='detections JSON: track it under every grid setting and rank the settings')
+    parser.add_argument('--score-grid', default='0.5:1.0:0.05')
+    parser.add_argument('--iou-grid', default='0.0,0.01,0.1,0.3')
+    parser.add_argument('--max-age', default='1,2,3')
+    parser.add_argument('--min-hits', default='0,1')
+    parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    gt = load_ground_truth(args.annotations)
+    if args.sweep:
+        grid = {'score': _grid_values(args.score_grid), 'iou': _grid_values(args.iou_grid),
+                'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')]}
+        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold))
+        for lv in LEVELS:
+            print('LEVEL_%d: %d settings tracked, best per class combined for each (max_age, min_hits)' % (lv, len(res['settings'])))
+            for r in res['ranked'][lv][:args.top]:
+                print('  MOTA %9.5f  %s' % (r['MOTA'], flag_line(r)))
+        if args.json:
+            with open(args.json, 'wt') as fp:
+                json.dump({'settings': res['settings'], 'tables': [r.as_json() for r in res['results']],
+                           'ranked': dict(('LEVEL_%d' % lv, v) for lv, v in res['ranked'].items())}, fp)
+        if res['best'][2] is not None:
+            print(flag_line(res['best'][2]))
+        return 0
+    if not args.tracks:
+        raise SystemExit('give at least one tracking JSON, or --sweep DETECTIONS.json')
+    results = evaluate_tracks(gt, [load_tracks(p) for p in args.tracks], args.iou_threshold)
+    for path, r in zip(args.tracks, results):
+        print(format_table(r, path))
+    if args.json:
+        with open(args.json, 'wt') as fp:
+            json.dump(dict((p, r.as_json()) for p, r in zip(args.tracks, results)), fp)
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())
