@@ -317,6 +317,49 @@ int wt_mot_eval_host(int64_t n_gt, const double* gx, const double* gy, const dou
                      int32_t n_classes, const double* thr,
                      int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch);
 
+/* =================================================================================================
+ * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
+ * ================================================================================================= */
+
+/* Scores K >= 1 detection results against one ground truth, as detnet/data/metric.py does on one host thread (match_class,
+ * _curves, voc_ap in the non-07 form): every detection takes the ground-truth box of highest IoU (the first one, numpy argmax)
+ * and is a true positive at threshold t when that IoU exceeds t and it is the most confident detection claiming that box.
+ * Equal confidences keep the input order: image order, then row order inside the image.
+ *
+ * Ground truth: SoA rows in image order - x1, y1, x2, y2 float64 normalised, label int32 in 1..n_classes - with the CSR offsets
+ * image_gt_offsets (n_images + 1) and image_area (n_images) float64 = width * height in pixels.
+ * Results: the K sets concatenated; set k owns rows set_row_offsets[k] .. set_row_offsets[k + 1], in image order (file order
+ * inside an image), image_det_offsets[k * (n_images + 1) + i] = offsets of image i inside the set.  conf, cx, cy, w, h float64
+ * normalised, category int32 in 1..n_classes.  A row takes part when conf > min_conf[k] (min_conf: K values, host pointer).
+ * thr: (n_classes, n_thr) IoU thresholds, host pointer; both host arrays are read before the call returns: thr travels as a kernel
+ * argument, min_conf in one hipMemcpyAsync of K doubles from the caller's (pageable) memory, which the runtime stages before it
+ * returns and which keeps the device form out of a hipGraph capture.  n_classes <= 16, n_thr <= 8; no limit on the rows of one image; K x n_images x n_classes
+ * below 2^26 and K x n_classes x n_thr below 2^21 (one workgroup each; more is WT_ERR_CAPACITY).
+ * Outputs: ap, ar float64 and npos, tp, fp int64, each (K, n_classes, n_thr, 4): buckets '' (all sizes), S, M, L of the box area
+ *          in pixels (< 32^2, < 96^2, the rest); ar is NaN without rows;
+ *          per row, each may be NULL: tp_flag (n_det, n_thr) uint8 1 = TP, 0 = FP, 2 = took no part; match_gt (n_det) the
+ *          ground-truth row of highest IoU, -1 when there is none; order (n_det) the row indices sorted by (set, class,
+ *          descending confidence), rows that took no part last; class_offsets (K, n_classes + 1) positions in `order`;
+ *          ctp, cfp (n_det, n_thr) int64: cumulative TP / FP of the all-sizes bucket at every position of `order` (together).
+ * The device form takes device pointers (except min_conf and thr), never synchronises or allocates and reports 0 or a WT_ERR_*
+ * in status_dev (device int32); it does not check the layout, the host form does (WT_ERR_INVALID names the set / image / row). */
+size_t wt_det_eval_workspace(int32_t k_sets, int64_t n_images, int32_t n_classes, int32_t n_thr, int64_t n_gt, int64_t n_det);
+int wt_det_eval_dev(int64_t n_gt, const double* gx1, const double* gy1, const double* gx2, const double* gy2, const int32_t* g_label,
+                    int64_t n_images, const int64_t* image_gt_offsets, const double* image_area,
+                    int32_t k_sets, int64_t n_det, const int64_t* set_row_offsets, const int64_t* image_det_offsets,
+                    const double* conf, const double* cx, const double* cy, const double* w, const double* h, const int32_t* category,
+                    const double* min_conf, int32_t n_classes, int32_t n_thr, const double* thr,
+                    double* ap, double* ar, int64_t* npos, int64_t* tp, int64_t* fp,
+                    uint8_t* tp_flag, int64_t* match_gt, int64_t* order, int64_t* class_offsets, int64_t* ctp, int64_t* cfp,
+                    int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_det_eval_host(int64_t n_gt, const double* gx1, const double* gy1, const double* gx2, const double* gy2, const int32_t* g_label,
+                     int64_t n_images, const int64_t* image_gt_offsets, const double* image_area,
+                     int32_t k_sets, const int64_t* set_row_offsets, const int64_t* image_det_offsets,
+                     const double* conf, const double* cx, const double* cy, const double* w, const double* h, const int32_t* category,
+                     const double* min_conf, int32_t n_classes, int32_t n_thr, const double* thr,
+                     double* ap, double* ar, int64_t* npos, int64_t* tp, int64_t* fp,
+                     uint8_t* tp_flag, int64_t* match_gt, int64_t* order, int64_t* class_offsets, int64_t* ctp, int64_t* cfp);
+
 /* --- Waymo Open Dataset protobuf emit (csrc/waymo_proto.hip; host code) -----------------------------------
  * metrics.Objects - and with submission != 0 the Submission envelope around it - written straight from columns: replaces
  * the per-object message building of /root/reference/coco_to_waymo.py:16-82 (create_pd_object / create_pb_submission) and

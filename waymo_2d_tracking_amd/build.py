@@ -29,6 +29,7 @@ UNITS = {
     'sort_engine.hip': ['-ffp-contract=off'],
     'sort_single.hip': ['-ffp-contract=off'],
     'mot_eval.hip': ['-ffp-contract=off'],             # CLEAR-MOT evaluation: float64 IoU in the reference's operation order
+    'det_eval.hip': ['-ffp-contract=off'],             # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_roialign.hip': [],
     'det_nms.hip': [],
     'det_deform.hip': [],

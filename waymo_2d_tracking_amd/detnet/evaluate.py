@@ -1,0 +1,456 @@
+"""AP / AR of detection results against ground truth on the GPU, and the sweep that tunes the ensemble's flags.
+
+    python -m waymo_2d_tracking_amd.detnet.evaluate --annotations GT.json DETS.json [DETS2.json ...]
+        [--metric waymo|voc] [--min-conf 0.01] [--json OUT]
+    python -m waymo_2d_tracking_amd.detnet.evaluate --annotations GT.json --sweep A.json B.json ...
+        --method soft_nms,nms --iou-grid 0.4:0.8:0.05 --cut-grid 0.9,1.0 --min-score-grid 0,0.01 [--weights 1,1]
+
+The metric is the one detnet/data/metric.py computes on one host thread (the reference's evaluation after inference), with
+the order of equal confidences defined; DESIGN.md section 16 has the exact definition.  Every (result, image, class) is an
+independent problem and one wavefront of the HIP kernels behind ``wt_det_eval_host`` (include/waymotrack.h): K results are
+scored in one call, which is what makes a sweep over ensemble settings cost seconds.  No arithmetic of the metric runs on the
+host; without the library or a GPU the calls fail.
+"""
+import argparse
+import ctypes as C
+import json
+import math
+
+import numpy as np
+
+from .. import _lib
+from .data.metric import load_ground_truth
+
+BUCKETS = ('', 'S', 'M', 'L')                       # the order of the last axis of every output
+METRICS = {'waymo': lambda name: (0.7,) if name == 'vehicle' else (0.5,), 'voc': lambda name: (0.5, 0.75)}
+DET_COLUMNS = ('conf', 'cx', 'cy', 'w', 'h')
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# packing
+def pack_ground_truth(annotations):
+    """COCO-format dict / file -> the columns wt_det_eval_* takes: boxes as metric.load_ground_truth gives them (float32-rounded,
+    normalised, duplicates removed) in ascending image-id order, with image_gt_offsets and image_area = width * height."""
+    if isinstance(annotations, dict) and 'image_gt_offsets' in annotations:
+        return annotations
+    image_ids, sizes, gt, classnames = load_ground_truth(annotations)
+    rows = [gt[k] for k in image_ids]
+    allrows = np.concatenate(rows).reshape(-1, 5) if rows else np.zeros((0, 5))
+    offsets = np.zeros(len(image_ids) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=offsets[1:])
+    col = lambda j: np.ascontiguousarray(allrows[:, j], dtype=np.float64)
+    return dict(image_ids=image_ids, index={k: i for i, k in enumerate(image_ids)}, sizes=sizes, classnames=classnames,
+                n_classes=len(classnames) - 1, x1=col(0), y1=col(1), x2=col(2), y2=col(3),
+                label=np.ascontiguousarray(allrows[:, 4], dtype=np.int32), image_gt_offsets=offsets,
+                image_area=np.asarray([float(sizes[k][0] * sizes[k][1]) for k in image_ids], np.float64))
+
+
+def _class_labels(gt, classnames):
+    """[(name, ground-truth label)] of the classes that are evaluated (metric.evaluate_detections skips unknown names)."""
+    names = list(classnames)
+    if names and names[0] == 'background':
+        names = names[1:]
+    known = gt['classnames']
+    return names, [(i, n, known.index(n)) for i, n in enumerate(names) if n in known and known.index(n) > 0]
+
+
+def _bad(message):
+    return _lib.WaymoTrackError('wt_det_eval failed: WT_ERR_INVALID (%s)' % message)
+
+
+def _wire_columns(gt, cols):
+    """Wire rows (pixel [x, y, w, h], score) as columns -> normalised float64 rows, the inverse of load_prediction:
+    conf = score, cx = (x + w / 2) / W, cy = (y + h / 2) / H, w = w / W, h = h / H, in that operation order."""
+    to_gt = np.asarray([gt['index'].get(str(k), -1) for k in cols['image_ids']], np.int64).reshape(-1)
+    image = to_gt[np.asarray(cols['image'], np.int64)]
+    if (image < 0).any():
+        k = cols['image_ids'][int(np.asarray(cols['image'])[np.argmax(image < 0)])]
+        raise _bad('detection on image %s, which the ground truth does not list: its size is unknown' % k)
+    cat = np.asarray(cols['category'], np.int64)
+    if ((cat < 1) | (cat > gt['n_classes'])).any():
+        i = int(np.argmax((cat < 1) | (cat > gt['n_classes'])))
+        raise _bad('category_id %d outside 1..%d in image %s' % (cat[i], gt['n_classes'], gt['image_ids'][image[i]]))
+    wh = np.asarray([gt['sizes'][k] for k in gt['image_ids']], np.float64).reshape(-1, 2)
+    W, H = wh[image, 0], wh[image, 1]
+    x, y, w, h = (np.asarray(cols[k], np.float64) for k in ('x', 'y', 'w', 'h'))
+    out = dict(image=image, category=cat.astype(np.int32), conf=np.asarray(cols['score'], np.float64),
+               cx=(x + w / 2) / W, cy=(y + h / 2) / H, w=w / W, h=h / H, source_row=np.arange(len(image), dtype=np.int64))
+    classes = [(n, i) for i, n in enumerate(gt['classnames']) if i > 0]
+    return out, classes
+
+
+def _set_columns(gt, s):
+    """One result in any accepted form -> (columns with `image` = ground-truth image index, [(class name, label)])."""
+    if isinstance(s, dict) and 'image_ids' in s and 'score' in s:              # wire rows as columns (ensemble.read_submission)
+        return _wire_columns(gt, s)
+    if isinstance(s, (str, bytes)) or hasattr(s, '__fspath__'):                # a detection JSON on disk
+        from .ensemble import read_submission
+        return _wire_columns(gt, read_submission(s))
+    if isinstance(s, (list, tuple)):                                           # parsed wire rows
+        from .ensemble import submission_columns
+        return _wire_columns(gt, submission_columns(list(s)))
+    if hasattr(s, 'classnames') and hasattr(s, 'shard_columns'):               # Predictions store
+        names, classes = _class_labels(gt, s.classnames or gt['classnames'][1:])
+        cols, tested = s.shard_columns()
+        to_gt = np.asarray([gt['index'].get(str(k), -1) if tested[i] else -1 for i, k in enumerate(s.image_ids)] + [-1], np.int64)
+        label_of = np.zeros(len(names) + 1, np.int64)
+        for i, _, label in classes:
+            label_of[i] = label
+        if len(cols['cls']) and (cols['cls'].min() < 0 or cols['cls'].max() >= len(names)):
+            bad = int(np.argmax((cols['cls'] < 0) | (cols['cls'] >= len(names))))
+            raise _bad('class index %d outside the %d class names in image %s' % (cols['cls'][bad], len(names), s.image_ids[cols['image'][bad]]))
+        image, label = to_gt[cols['image']], label_of[cols['cls']]
+        keep = np.nonzero((image >= 0) & (label > 0))[0]
+        out = dict(image=image[keep], category=label[keep].astype(np.int32), cls=cols['cls'][keep], source_row=keep.astype(np.int64),
+                   conf=cols['score'][keep].astype(np.float64), cx=cols['cx'][keep].astype(np.float64), cy=cols['cy'][keep].astype(np.float64),
+                   w=cols['w'][keep].astype(np.float64), h=cols['h'][keep].astype(np.float64))
+        return out, [(n, label) for _, n, label in classes]
+    if isinstance(s, dict):                                                    # {image_id: [per class (n, 5)]}
+        names, classes = _class_labels(gt, gt['classnames'][1:])
+        parts = {k: [] for k in ('image', 'category', 'cls') + DET_COLUMNS}
+        for image_id, per_class in s.items():
+            i = gt['index'].get(str(image_id))
+            if i is None or per_class is None:
+                continue
+            if len(per_class) != len(names):
+                raise _bad('image %s has %d class arrays, the ground truth has %d classes' % (image_id, len(per_class), len(names)))
+            for ci, _, label in classes:
+                a = np.asarray(per_class[ci], np.float64)
+                if a.size % 5:
+                    raise _bad('image %s, class %s: rows are [conf, cx, cy, w, h], got an array of shape %s' % (image_id, names[ci], a.shape))
+                a = a.reshape(-1, 5)
+                parts['image'].append(np.full(len(a), i, np.int64)); parts['category'].append(np.full(len(a), label, np.int32))
+                parts['cls'].append(np.full(len(a), ci, np.int32))
+                for j, k in enumerate(DET_COLUMNS):
+                    parts[k].append(a[:, j])
+        out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in parts.items()}
+        out['image'] = out['image'].astype(np.int64); out['category'] = out['category'].astype(np.int32); out['cls'] = out['cls'].astype(np.int32)
+        out['source_row'] = np.arange(len(out['image']), dtype=np.int64)
+        return out, [(n, label) for _, n, label in classes]
+    raise TypeError('a result is a Predictions store, a {image_id: [per class (n, 5)]} dict, or a detection JSON (path or rows)')
+
+
+def pack_detections(gt, sets):
+    """K results -> the concatenated columns and offsets wt_det_eval_* takes: per set the rows in image order; inside an image the
+    wire form keeps file order, the dict and Predictions forms go class by class in stored order."""
+    gt = pack_ground_truth(gt)
+    if len(sets) < 1:
+        raise ValueError('at least one result is needed')
+    n_images = len(gt['image_ids'])
+    cols = {k: [] for k in ('category', 'source_row') + DET_COLUMNS}
+    set_rows, offsets, classes = [0], [], []
+    for s in sets:
+        c, cls = _set_columns(gt, s)
+        key = c['image'] * (int(c['cls'].max()) + 1 if len(c['cls']) else 1) + c['cls'] if 'cls' in c else c['image']
+        order = np.argsort(key, kind='stable')
+        offsets.append(np.searchsorted(c['image'][order], np.arange(n_images + 1)).astype(np.int64))
+        for k in cols:
+            cols[k].append(c[k][order])
+        set_rows.append(set_rows[-1] + len(order))
+        classes.append(cls)
+    out = {k: np.ascontiguousarray(np.concatenate(cols[k]), dtype=np.float64) for k in DET_COLUMNS}
+    out['category'] = np.ascontiguousarray(np.concatenate(cols['category']), dtype=np.int32)
+    out['source_row'] = np.concatenate(cols['source_row']).astype(np.int64)
+    out['set_row_offsets'] = np.asarray(set_rows, np.int64)
+    out['image_det_offsets'] = np.ascontiguousarray(np.stack(offsets), dtype=np.int64)
+    out['classes'] = classes
+    return out
+
+
+def thresholds(gt, metric):
+    """(n_classes, n_thr) IoU thresholds of a preset, row c - 1 for label c."""
+    if metric not in METRICS:
+        raise ValueError("metric is 'waymo' or 'voc', got %r" % (metric,))
+    rows = [METRICS[metric](name) for name in gt['classnames'][1:]]
+    return np.ascontiguousarray(rows, dtype=np.float64).reshape(gt['n_classes'], -1)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# results
+class DetResult(object):
+    """Scores of one detection result.
+
+    ap, ar (n_classes, n_thr, 4) float64 and npos, tp, fp (n_classes, n_thr, 4) int64; last axis = BUCKETS ('', S, M, L)
+    classes   [(name, label)] of the evaluated classes, in the result's class order
+    with per_row=True, per packed row of the set (source_row = its row in the input): tp_flag (n, n_thr) uint8 (2 = took no part),
+    match_gt (index into the packed ground truth, -1 none), and per label c: order[c] (packed rows by descending confidence) with
+    ctp[c], cfp[c] (len(order[c]), n_thr) the cumulative counts of the all-sizes bucket along it."""
+
+    def __init__(self, metric, thr, classes, ap, ar, npos, tp, fp, per_row=None):
+        self.metric, self.thr, self.classes = metric, thr, classes
+        self.ap, self.ar, self.npos, self.tp, self.fp = ap, ar, npos, tp, fp
+        for k, v in (per_row or {}).items():
+            setattr(self, k, v)
+
+    def summary(self):
+        """The dict metric.evaluate_detections returns for this metric (same keys, same nesting)."""
+        out = {}
+        for name, c in self.classes:
+            ap, ar = self.ap[c - 1], self.ar[c - 1]
+            if self.metric == 'waymo':
+                out[name] = dict(ap=float(ap[0, 0]), ar=float(ar[0, 0]), T=int(self.npos[c - 1, 0, 0]), score=float(ap[0, 0]),
+                                 by_size={b: float(ap[0, i]) for i, b in enumerate(BUCKETS) if b})
+            else:
+                s = {}
+                for t, tv in enumerate(self.thr[c - 1].tolist()):
+                    for b in (('S', 'M', 'L', '') if tv == 0.5 else ('',)):
+                        s['ap@%s%s' % (tv, b)] = float(ap[t, BUCKETS.index(b)])
+                        s['ar@%s%s' % (tv, b)] = float(ar[t, BUCKETS.index(b)])
+                s['T'] = int(self.npos[c - 1, 0, 0])
+                s['score'] = s.get('ap@0.5')
+                out[name] = s
+        if self.metric == 'voc':
+            mean = {k: float(np.mean([out[name][k] for name, _ in self.classes])) for k in ('ap@0.5', 'ar@0.5', 'T')}
+            out['mean'] = mean
+            out['score'] = mean['ap@0.5']
+        return out
+
+    def mean_ap(self):
+        """Mean AP (first threshold, all sizes) over the classes that have ground truth: the figure evaluate_detections prints."""
+        aps = [self.ap[c - 1, 0, 0] for _, c in self.classes if self.npos[c - 1, 0, 0] > 0]
+        return float(np.mean(aps)) if aps else math.nan
+
+    def lines(self):
+        """The lines metric.evaluate_detections prints."""
+        s = self.summary()
+        out = ['%-12s ' % name + ' '.join('%s %.4f' % (k, x) for k, x in s[name].items() if isinstance(x, (int, float)))
+               for name, _ in self.classes]
+        out.append('* mean AP over classes with ground truth = %.4f' % self.mean_ap())
+        return out
+
+
+def _results(gt, p, metric, thr, out, per_row):
+    results = []
+    T = thr.shape[1]
+    for k, classes in enumerate(p['classes']):
+        rows = None
+        if per_row:
+            lo, hi = int(p['set_row_offsets'][k]), int(p['set_row_offsets'][k + 1])
+            co = out['class_offsets'][k]
+            rows = dict(source_row=p['source_row'][lo:hi], tp_flag=out['tp_flag'][lo:hi], match_gt=out['match_gt'][lo:hi],
+                        order={}, ctp={}, cfp={})
+            for c in range(1, gt['n_classes'] + 1):
+                a, b = int(co[c - 1]), int(co[c])
+                rows['order'][c] = out['order'][a:b] - lo
+                rows['ctp'][c] = out['ctp'][a:b].reshape(-1, T)
+                rows['cfp'][c] = out['cfp'][a:b].reshape(-1, T)
+        results.append(DetResult(metric, thr, classes, out['ap'][k], out['ar'][k], out['npos'][k], out['tp'][k], out['fp'][k], rows))
+    return results
+
+
+def _min_conf(min_conf, K):
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(min_conf, np.float64), (K,)) if np.ndim(min_conf) == 0 else min_conf, dtype=np.float64)
+    if m.shape != (K,):
+        raise ValueError('%d min_conf values for %d results' % (m.size, K))
+    return m
+
+
+def evaluate_detection_sets(gt, sets, metric='waymo', min_conf=0.01, per_row=False):
+    """Score K detection results against one ground truth (annotations, or pack_ground_truth's output) in ONE wt_det_eval_host
+    call.  min_conf: one value or one per result.  Returns a list of K DetResult."""
+    lib = _lib.lib()
+    gt = pack_ground_truth(gt)
+    p = sets if isinstance(sets, dict) and 'set_row_offsets' in sets else pack_detections(gt, sets)
+    K = len(p['set_row_offsets']) - 1
+    thr = thresholds(gt, metric)
+    nc, T = thr.shape
+    minc = _min_conf(min_conf, K)
+    n_det = int(p['set_row_offsets'][-1])
+    shape = (K, nc, T, len(BUCKETS))
+    out = dict(ap=np.zeros(shape), ar=np.zeros(shape), npos=np.zeros(shape, np.int64), tp=np.zeros(shape, np.int64), fp=np.zeros(shape, np.int64))
+    if per_row:
+        out.update(tp_flag=np.full((n_det, T), 2, np.uint8), match_gt=np.full(n_det, -1, np.int64), order=np.zeros(n_det, np.int64),
+                   class_offsets=np.zeros((K, nc + 1), np.int64), ctp=np.zeros((n_det, T), np.int64), cfp=np.zeros((n_det, T), np.int64))
+    opt = lambda k: _lib.ptr(out[k]) if per_row else None
+    rc = lib.wt_det_eval_host(
+        C.c_int64(gt['x1'].size), _lib.ptr(gt['x1']), _lib.ptr(gt['y1']), _lib.ptr(gt['x2']), _lib.ptr(gt['y2']), _lib.ptr(gt['label']),
+        C.c_int64(len(gt['image_ids'])), _lib.ptr(gt['image_gt_offsets']), _lib.ptr(gt['image_area']),
+        C.c_int32(K), _lib.ptr(p['set_row_offsets']), _lib.ptr(p['image_det_offsets']),
+        _lib.ptr(p['conf']), _lib.ptr(p['cx']), _lib.ptr(p['cy']), _lib.ptr(p['w']), _lib.ptr(p['h']), _lib.ptr(p['category']),
+        _lib.ptr(minc), C.c_int32(nc), C.c_int32(T), _lib.ptr(thr),
+        _lib.ptr(out['ap']), _lib.ptr(out['ar']), _lib.ptr(out['npos']), _lib.ptr(out['tp']), _lib.ptr(out['fp']),
+        opt('tp_flag'), opt('match_gt'), opt('order'), opt('class_offsets'), opt('ctp'), opt('cfp'))
+    _lib.check(rc, 'wt_det_eval_host')
+    return _results(gt, p, metric, thr, out, per_row)
+
+
+class DeviceDetEvaluation(object):
+    """The same evaluation with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues one
+    wt_det_eval_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.
+    This is the form a device-resident sweep (merged rows scored without leaving the GPU) builds on."""
+
+    def __init__(self, gt, sets, metric='waymo', min_conf=0.01):
+        import torch
+        self.torch = torch
+        self.lib = _lib.lib()
+        self.gt = gt = pack_ground_truth(gt)
+        self.p = p = sets if isinstance(sets, dict) and 'set_row_offsets' in sets else pack_detections(gt, sets)
+        self.metric = metric
+        self.thr = thresholds(gt, metric)
+        self.K = len(p['set_row_offsets']) - 1
+        self.minc = _min_conf(min_conf, self.K)
+        self.n_det = int(p['set_row_offsets'][-1])
+        self.n_images = len(gt['image_ids'])
+        nc, T = self.thr.shape
+        dev = torch.device('cuda', torch.cuda.current_device())
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros(1, dtype=torch.from_numpy(a).dtype, device=dev)
+        self.g = {n: up(gt[n]) for n in ('x1', 'y1', 'x2', 'y2', 'label', 'image_gt_offsets', 'image_area')}
+        self.d = {n: up(p[n]) for n in DET_COLUMNS + ('category', 'set_row_offsets', 'image_det_offsets')}
+        shape = (self.K, nc, T, len(BUCKETS))
+        z = lambda s, dt: torch.zeros(s, dtype=dt, device=dev)
+        n = max(1, self.n_det)
+        self.out = dict(ap=z(shape, torch.float64), ar=z(shape, torch.float64), npos=z(shape, torch.int64), tp=z(shape, torch.int64),
+                        fp=z(shape, torch.int64), tp_flag=z((n, T), torch.uint8), match_gt=z(n, torch.int64), order=z(n, torch.int64),
+                        class_offsets=z((self.K, nc + 1), torch.int64), ctp=z((n, T), torch.int64), cfp=z((n, T), torch.int64))
+        self.status = z(1, torch.int32)
+        self.ws_bytes = int(self.lib.wt_det_eval_workspace(C.c_int32(self.K), C.c_int64(self.n_images), C.c_int32(nc), C.c_int32(T),
+                                                           C.c_int64(gt['x1'].size), C.c_int64(self.n_det)))
+        if not self.ws_bytes:
+            _lib.check(4, 'wt_det_eval_workspace')
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+
+    def launch(self):
+        g, d, o, v = self.g, self.d, self.out, C.c_void_p
+        p = lambda t: v(t.data_ptr())
+        nc, T = self.thr.shape
+        rc = self.lib.wt_det_eval_dev(
+            C.c_int64(self.gt['x1'].size), p(g['x1']), p(g['y1']), p(g['x2']), p(g['y2']), p(g['label']),
+            C.c_int64(self.n_images), p(g['image_gt_offsets']), p(g['image_area']),
+            C.c_int32(self.K), C.c_int64(self.n_det), p(d['set_row_offsets']), p(d['image_det_offsets']),
+            p(d['conf']), p(d['cx']), p(d['cy']), p(d['w']), p(d['h']), p(d['category']),
+            _lib.ptr(self.minc), C.c_int32(nc), C.c_int32(T), _lib.ptr(self.thr),
+            p(o['ap']), p(o['ar']), p(o['npos']), p(o['tp']), p(o['fp']),
+            p(o['tp_flag']), p(o['match_gt']), p(o['order']), p(o['class_offsets']), p(o['ctp']), p(o['cfp']),
+            p(self.status), p(self.ws), C.c_size_t(self.ws_bytes), v(self.torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, 'wt_det_eval_dev')
+
+    def results(self, per_row=False):
+        self.torch.cuda.current_stream().synchronize()
+        st = int(self.status.item())
+        if st:
+            raise _lib.WaymoTrackError('wt_det_eval_dev failed: %s (status reported by the kernel)' % _lib._STATUS.get(st, st))
+        out = {k: t.cpu().numpy() for k, t in self.out.items()}
+        for k in ('tp_flag', 'match_gt', 'order', 'ctp', 'cfp'):
+            out[k] = out[k][:self.n_det]
+        return _results(self.gt, self.p, self.metric, self.thr, out, per_row)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ensemble sweep
+def _grid_values(text):
+    """'0.4:0.8:0.05' (inclusive range) or '0.9,1.0' -> list of floats."""
+    if ':' in text:
+        lo, hi, step = (float(v) for v in text.split(':'))
+        n = int(math.floor((hi - lo) / step + 1e-9)) + 1
+        return [round(lo + i * step, 10) for i in range(n)]
+    return [float(v) for v in text.split(',')]
+
+
+def flag_line(setting):
+    """The tail of the `python -m waymo_2d_tracking_amd.detnet.ensemble` command line of a sweep setting."""
+    return '-m %s --iou-thresh=%r --soft-nms-cut=%r --min-score=%r' % (
+        setting['method'], float(setting['iou_thresh']), float(setting['soft_nms_cut']), float(setting['min_score']))
+
+
+class SweepResult(object):
+    """settings (grid order), results (DetResult per setting), mean_ap per setting, ranked (indices into settings, best first),
+    best (the winning setting) and flag_line() (its ensemble command-line tail)."""
+
+    def __init__(self, settings, results, mean_ap, ranked):
+        self.settings, self.results, self.mean_ap, self.ranked = settings, results, mean_ap, ranked
+        self.best = settings[ranked[0]]
+
+    def flag_line(self):
+        return flag_line(self.best)
+
+
+def sweep(inputs, gt, grid, weights=None, metric='waymo', min_conf=0.01):
+    """Merge the input detection files (paths, or parsed row lists) under every setting of `grid` - dict with lists 'method',
+    'iou_thresh', 'soft_nms_cut', 'min_score', iterated in that nesting - with the ensemble's own code path, and score all K
+    merged results in ONE evaluation call.  Ranked by mean AP over the classes with ground truth; ties go to grid order.
+    Returns a SweepResult."""
+    from . import ensemble as E
+    gt = pack_ground_truth(gt)
+    subs = [E.read_submission(f) if not isinstance(f, (list, tuple, dict)) else (f if isinstance(f, dict) else E.submission_columns(list(f)))
+            for f in inputs]
+    w = E.normalise_weights(weights, len(subs))
+    settings, merged = [], []
+    for method in grid['method']:
+        if method not in E.METHODS:
+            raise ValueError('unknown ensemble method %r' % (method,))
+        for iou in grid['iou_thresh']:
+            for cut in grid['soft_nms_cut']:
+                for min_score in grid['min_score']:
+                    image_ids, category_ids, rows = E.merge_inputs(subs, w, min_score)
+                    packed = E.pack_groups(len(image_ids), category_ids, rows, len(subs))
+                    out5, counts = E.merge_groups(packed, len(subs), method, iou, cut)
+                    o = E.output_rows(packed, category_ids, out5, counts, min_score)
+                    b = o['bbox'].astype(np.float64).reshape(-1, 4)
+                    merged.append(dict(image_ids=image_ids, image=o['image'], category=o['category'], score=o['score'],
+                                       x=b[:, 0], y=b[:, 1], w=b[:, 2], h=b[:, 3]))
+                    settings.append({'method': method, 'iou_thresh': float(iou), 'soft_nms_cut': float(cut), 'min_score': float(min_score)})
+    if not settings:
+        raise ValueError('the grid is empty')
+    results = evaluate_detection_sets(gt, merged, metric, min_conf)
+    mean_ap = [r.mean_ap() for r in results]
+    ranked = sorted(range(len(settings)), key=lambda i: (-(mean_ap[i] if mean_ap[i] == mean_ap[i] else -math.inf), i))
+    return SweepResult(settings, results, mean_ap, ranked)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# command line
+def build_parser():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument('detections', nargs='*', help='detection JSON files (detnet/export.py, detnet/ensemble.py)')
+    parser.add_argument('--annotations', required=True, help='ground-truth COCO json (waymo_to_coco.py)')
+    parser.add_argument('--metric', choices=sorted(METRICS), default='waymo')
+    parser.add_argument('--min-conf', type=float, default=0.01, help='detections with a confidence above this take part')
+    parser.add_argument('--json', help='write the summaries (or the sweep) to this file')
+    parser.add_argument('--sweep', nargs='+', help='input detection files: merge them under every grid setting and rank the settings')
+    parser.add_argument('--method', default='soft_nms', help="comma-separated ensemble methods, e.g. 'soft_nms,nms'")
+    parser.add_argument('--iou-grid', default='0.4:0.8:0.05')
+    parser.add_argument('--cut-grid', default='0.9,1.0')
+    parser.add_argument('--min-score-grid', default='0,0.01')
+    parser.add_argument('--weights', help="per-input weights, e.g. '1,0.8' (divided by their maximum)")
+    parser.add_argument('--top', type=int, default=10, help='ranked settings to print')
+    return parser
+
+
+def grid_from_args(args):
+    return {'method': [m.strip() for m in args.method.split(',')], 'iou_thresh': _grid_values(args.iou_grid),
+            'soft_nms_cut': _grid_values(args.cut_grid), 'min_score': _grid_values(args.min_score_grid)}
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.sweep:
+        if args.detections:
+            raise SystemExit('give either detection files to score or --sweep INPUTS, not both')
+        if len(args.sweep) < 2:
+            raise SystemExit('--sweep needs at least two input files to merge')
+        weights = [float(v) for v in args.weights.split(',')] if args.weights else None
+        res = sweep(args.sweep, args.annotations, grid_from_args(args), weights, args.metric, args.min_conf)
+        print('%d settings merged and scored' % len(res.settings))
+        for i in res.ranked[:args.top]:
+            print('  mean AP %.5f  %s' % (res.mean_ap[i], flag_line(res.settings[i])))
+        if args.json:
+            with open(args.json, 'wt') as fp:
+                json.dump({'settings': res.settings, 'mean_ap': res.mean_ap, 'ranked': res.ranked,
+                           'summaries': [r.summary() for r in res.results]}, fp)
+        print(res.flag_line())
+        return 0
+    if not args.detections:
+        raise SystemExit('give at least one detection JSON, or --sweep A.json B.json ...')
+    results = evaluate_detection_sets(args.annotations, args.detections, args.metric, args.min_conf)
+    for path, r in zip(args.detections, results):
+        print(path)
+        for line in r.lines():
+            print(line)
+    if args.json:
+        with open(args.json, 'wt') as fp:
+            json.dump({p: r.summary() for p, r in zip(args.detections, results)}, fp)
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

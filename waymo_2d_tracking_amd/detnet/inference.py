@@ -72,6 +72,7 @@ def build_parser():
     parser.add_argument('--annotations', type=str, help='COCO-format ground truth for --eval')
     parser.add_argument('--resume', type=str)
     parser.add_argument('--eval', action='store_true')
+    parser.add_argument('--eval-gpu', action='store_true', help='with --eval: score on the GPU (detnet/evaluate.py) instead of the host loop')
     parser.add_argument('--export', type=str, help='path of export file')
     parser.add_argument('--export-format', type=str, choices=('json',), default='json')
     parser.add_argument('--profile', action='store_true')
@@ -433,6 +434,8 @@ def check_supported(args):
             raise NotImplementedError('--resize takes the length of the shorter edge (int); (h, w) pairs are not supported')
     if args.eval and not args.annotations:
         raise ValueError('--eval needs --annotations GT.json (COCO-format ground truth; the reference reads it from --data-root)')
+    if getattr(args, 'eval_gpu', False) and not args.eval:
+        raise ValueError('--eval-gpu selects how --eval scores the detections: give --eval --annotations GT.json with it')
     if args.export_format != 'json':
         raise NotImplementedError('--export-format json only')
     return check_views(args)
@@ -518,7 +521,11 @@ def run_rank(args, world, rank):
                         out[k] = im.size
             return out
         image_sizes = image_sizes_in_order() if (args.eval or args.export) else {}
-        if args.eval:
+        if args.eval and getattr(args, 'eval_gpu', False):
+            from .evaluate import evaluate_detection_sets
+            for line in evaluate_detection_sets(args.annotations, [predictions])[0].lines():
+                print(line)
+        elif args.eval:
             from .data.metric import evaluate_detections
             evaluate_detections(predictions, args.annotations, image_sizes, print_fn=print)
         if args.export:
