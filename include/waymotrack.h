@@ -218,6 +218,10 @@ const double* wt_detjson_score(const wt_detjson* f);
 const char* wt_detjson_image_id(const wt_detjson* f, int32_t i);
 int wt_detections_write_json(const char* path, int64_t n, const int32_t* image_index, int32_t n_images, const char* image_id_blob,
                              const int64_t* image_id_offsets, const int32_t* category, const int64_t* bbox4, const double* score);
+/* The same file for rows whose boxes are floats (detnet/ensemble_b.py:106-107 writes box.tolist() untruncated): every bbox value
+ * in Python repr form, as json.dump writes a float. */
+int wt_detections_write_json_f64(const char* path, int64_t n, const int32_t* image_index, int32_t n_images, const char* image_id_blob,
+                                 const int64_t* image_id_offsets, const int32_t* category, const double* bbox4, const double* score);
 /* Python repr() of a double (shortest round-trip digits); returns the length or -1 if cap is too small. */
 int wt_format_double(double v, char* out, int cap);
 
@@ -273,8 +277,32 @@ int wt_ensemble_slots_dev(const double* xywhs, const int32_t* category, int64_t 
                           double min_score, double* out_xywhs, int32_t* out_category, int64_t* out_counts,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Weighted boxes fusion and non-maximum weighted (the merge rules of detnet/ensemble_b.py) for G (image, category) groups at
+ * once.  The definition is the project's own - DESIGN.md, "Weighted boxes fusion and NMW" - and is not pinned against the
+ * ensemble_boxes package.  dets5 rows are [score, x_left, y_top, w, h] float64 with the score already multiplied by its input's
+ * weight; group_offsets (G+1) rows CSR; inside a group the rows are the inputs concatenated in input order, each in file order.
+ * group_wsum (G) float64: the weight sum of the inputs that have a row of any category in the group's image.
+ *   method 0: weighted_fusion - rows in descending score (ties: earlier row) join the cluster whose fused box has the greatest
+ *             IoU > iou_thresh (ties: earlier cluster) or start one; conf = mean score * min(wsum, members) / wsum
+ *   method 1: nmw - the same walk against each cluster's first member; box weighted by score * IoU with it, conf = its score
+ * out5 has the input's row capacity: group g writes out_counts[g] rows [conf, x_left, y_top, w, h] by descending conf (ties:
+ * creation order) starting at row group_offsets[g]; out_members (rows, int32) holds the member count of each output row and
+ * row_cluster (rows, int32) for each input row the position in its group's output of the cluster it joined; both may be NULL.
+ * A group with more than max_group_rows rows is not merged: its out_counts is -1.
+ * _dev: device pointers, stream-ordered, no allocation, no host synchronisation; workspace of wt_fuse_groups_workspace bytes
+ * (0 while max_group_rows <= wt_fuse_groups_lds_rows(), the rows whose state fits the kernel's LDS).  An invalid method, a
+ * negative size or a workspace that is too small is WT_ERR_INVALID. */
+int64_t wt_fuse_groups_lds_rows(void);
+size_t wt_fuse_groups_workspace(int64_t n_rows, int64_t n_groups, int64_t max_group_rows);
+int wt_fuse_groups_dev(const double* dets5, const int64_t* group_offsets, const double* group_wsum, int64_t n_rows,
+                       int64_t n_groups, int64_t max_group_rows, int method, double iou_thresh, double* out5,
+                       int32_t* out_members, int32_t* row_cluster, int64_t* out_counts, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int wt_fuse_groups_host(const double* dets5, const int64_t* group_offsets, const double* group_wsum, int64_t n_groups, int method,
+                        double iou_thresh, double* out5, int32_t* out_members, int32_t* row_cluster, int64_t* out_counts);
+
 /* =================================================================================================
- * MOT evaluation  (CLEAR-MOT per class and Waymo difficulty level; the definition is in DESIGN.md, "Tracking metric")
+ * MOT evaluation (CLEAR-MOT per class and Waymo difficulty level; the definition is in DESIGN.md, "Tracking metric")
  * ================================================================================================= */
 
 /* Scores K >= 1 tracking results against one ground truth: one wavefront per (result set, stream, class) walks the stream's

@@ -26,6 +26,7 @@ UNITS = {
     'json_io.hip': [],
     'waymo_proto.hip': [],
     'ensemble.hip': ['-ffp-contract=off'],
+    'ensemble_wbf.hip': ['-ffp-contract=off'],         # weighted boxes fusion / NMW: float64 sums and quotients in the order of the definition
     'sort_engine.hip': ['-ffp-contract=off'],
     'sort_single.hip': ['-ffp-contract=off'],
     'mot_eval.hip': ['-ffp-contract=off'],             # CLEAR-MOT evaluation: float64 IoU in the reference's operation order

@@ -460,10 +460,12 @@ const double* wt_detjson_h(const wt_detjson* f) { return f->h.data(); }
 const double* wt_detjson_score(const wt_detjson* f) { return f->score.data(); }
 const char* wt_detjson_image_id(const wt_detjson* f, int32_t i) { return f->image_ids[(size_t)i].c_str(); }
 
-int wt_detections_write_json(const char* path, int64_t n, const int32_t* image_index, int32_t n_images, const char* image_id_blob,
-                             const int64_t* image_id_offsets, const int32_t* category, const int64_t* bbox4, const double* score) {
-    if (!path || n < 0 || n_images < 0 || (n && (!image_index || !category || !bbox4 || !score || !image_id_blob || !image_id_offsets))) {
-        wt::set_error("wt_detections_write_json: bad argument");
+// one writer for both box types: exactly one of ibox4 (integers) / fbox4 (floats in repr form) is given
+static int write_detections(const char* what, const char* path, int64_t n, const int32_t* image_index, int32_t n_images,
+                            const char* image_id_blob, const int64_t* image_id_offsets, const int32_t* category, const int64_t* ibox4,
+                            const double* fbox4, const double* score) {
+    if (!path || n < 0 || n_images < 0 || (n && (!image_index || !category || (!ibox4 && !fbox4) || !score || !image_id_blob || !image_id_offsets))) {
+        wt::set_error("%s: bad argument", what);
         return WT_ERR_INVALID;
     }
     FILE* fp = fopen(path, "wb");
@@ -486,7 +488,12 @@ int wt_detections_write_json(const char* path, int64_t n, const int32_t* image_i
         buf += ", \"bbox\": [";
         for (int q = 0; q < 4; ++q) {
             if (q) buf += ", ";
-            buf += std::to_string((long long)bbox4[4 * i + q]);
+            if (ibox4) {
+                buf += std::to_string((long long)ibox4[4 * i + q]);
+            } else {
+                py_float_repr(fbox4[4 * i + q], num);
+                buf += num;
+            }
         }
         buf += "], \"score\": ";
         py_float_repr(score[i], num);
@@ -498,6 +505,18 @@ int wt_detections_write_json(const char* path, int64_t n, const int32_t* image_i
     fwrite(buf.data(), 1, buf.size(), fp);
     fclose(fp);
     return WT_OK;
+}
+
+int wt_detections_write_json(const char* path, int64_t n, const int32_t* image_index, int32_t n_images, const char* image_id_blob,
+                             const int64_t* image_id_offsets, const int32_t* category, const int64_t* bbox4, const double* score) {
+    return write_detections("wt_detections_write_json", path, n, image_index, n_images, image_id_blob, image_id_offsets, category, bbox4,
+                            nullptr, score);
+}
+
+int wt_detections_write_json_f64(const char* path, int64_t n, const int32_t* image_index, int32_t n_images, const char* image_id_blob,
+                                 const int64_t* image_id_offsets, const int32_t* category, const double* bbox4, const double* score) {
+    return write_detections("wt_detections_write_json_f64", path, n, image_index, n_images, image_id_blob, image_id_offsets, category,
+                            nullptr, bbox4, score);
 }
 
 int wt_format_double(double v, char* out, int cap) {

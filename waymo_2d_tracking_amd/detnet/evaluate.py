@@ -346,8 +346,15 @@ def _grid_values(text):
     return [float(v) for v in text.split(',')]
 
 
+# sweep names of the merge rules of detnet/ensemble_b.py -> its -m value; only iou_thresh varies for them
+B_METHODS = {'weighted_fusion_b': 'weighted_fusion', 'nmw': 'nmw'}
+
+
 def flag_line(setting):
-    """The tail of the `python -m waymo_2d_tracking_amd.detnet.ensemble` command line of a sweep setting."""
+    """The tail of the `python -m waymo_2d_tracking_amd.detnet.ensemble` command line of a sweep setting; for the methods of
+    B_METHODS the tail of the `python -m waymo_2d_tracking_amd.detnet.ensemble_b` command line."""
+    if setting['method'] in B_METHODS:
+        return '-m %s --iou-thresh=%r' % (B_METHODS[setting['method']], float(setting['iou_thresh']))
     return '-m %s --iou-thresh=%r --soft-nms-cut=%r --min-score=%r' % (
         setting['method'], float(setting['iou_thresh']), float(setting['soft_nms_cut']), float(setting['min_score']))
 
@@ -367,7 +374,9 @@ class SweepResult(object):
 def sweep(inputs, gt, grid, weights=None, metric='waymo', min_conf=0.01):
     """Merge the input detection files (paths, or parsed row lists) under every setting of `grid` - dict with lists 'method',
     'iou_thresh', 'soft_nms_cut', 'min_score', iterated in that nesting - with the ensemble's own code path, and score all K
-    merged results in ONE evaluation call.  Ranked by mean AP over the classes with ground truth; ties go to grid order.
+    merged results in ONE evaluation call.  The methods 'weighted_fusion_b' and 'nmw' are the merge rules of detnet/ensemble_b.py:
+    only iou_thresh varies for them (one setting per value, soft_nms_cut and min_score reported as None) and `weights` reach
+    them as given.  Ranked by mean AP over the classes with ground truth; ties go to grid order.
     Returns a SweepResult."""
     from . import ensemble as E
     gt = pack_ground_truth(gt)
@@ -376,6 +385,15 @@ def sweep(inputs, gt, grid, weights=None, metric='waymo', min_conf=0.01):
     w = E.normalise_weights(weights, len(subs))
     settings, merged = [], []
     for method in grid['method']:
+        if method in B_METHODS:                      # weighted boxes fusion / NMW: no cut, no minimal score - one setting per IoU value
+            from . import ensemble_b as EB
+            for iou in grid['iou_thresh']:
+                image_ids, o = EB.fuse_submissions(subs, B_METHODS[method], iou, weights)
+                b = o['bbox']
+                merged.append(dict(image_ids=image_ids, image=o['image'], category=o['category'], score=o['score'],
+                                   x=b[:, 0], y=b[:, 1], w=b[:, 2], h=b[:, 3]))
+                settings.append({'method': method, 'iou_thresh': float(iou), 'soft_nms_cut': None, 'min_score': None})
+            continue
         if method not in E.METHODS:
             raise ValueError('unknown ensemble method %r' % (method,))
         for iou in grid['iou_thresh']:
@@ -407,7 +425,7 @@ def build_parser():
     parser.add_argument('--min-conf', type=float, default=0.01, help='detections with a confidence above this take part')
     parser.add_argument('--json', help='write the summaries (or the sweep) to this file')
     parser.add_argument('--sweep', nargs='+', help='input detection files: merge them under every grid setting and rank the settings')
-    parser.add_argument('--method', default='soft_nms', help="comma-separated ensemble methods, e.g. 'soft_nms,nms'")
+    parser.add_argument('--method', default='soft_nms', help="comma-separated ensemble methods, e.g. 'soft_nms,nms'; 'weighted_fusion_b' and 'nmw' are the rules of detnet.ensemble_b")
     parser.add_argument('--iou-grid', default='0.4:0.8:0.05')
     parser.add_argument('--cut-grid', default='0.9,1.0')
     parser.add_argument('--min-score-grid', default='0,0.01')
