@@ -346,6 +346,60 @@ int wt_mot_eval_host(int64_t n_gt, const double* gx, const double* gy, const dou
                      int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch);
 
 /* =================================================================================================
+ * MOT identity evaluation (IDF1 / IDP / IDR per class and Waymo difficulty level; the definition is DESIGN.md section 18)
+ * ================================================================================================= */
+
+/* Scores the identity preservation of K >= 1 tracking results against one ground truth: one wavefront per (result set,
+ * stream, class) walks the stream's frames in order and counts, per (ground-truth trajectory, hypothesis trajectory), the
+ * frames where both have a box and IoU >= the class's threshold (one float32 matrix per difficulty level, the smaller side as
+ * rows), solves ONE assignment per level on that matrix (the Munkres of the tracker, on -n) and walks the frames once more to
+ * count the pairs whose trajectories are assigned to each other.  IoU as in wt_mot_eval_*.
+ *
+ * Ground truth and results: the SoA layout of wt_mot_eval_* unchanged (the same arrays can be passed), except that the object
+ * ids are replaced by trajectory indices: g_traj int32 = index of the row's trajectory among those of its (stream, class),
+ * h_traj int32 = the same among those of its (set, stream, class); rows of other categories and rows that take no part are not
+ * read.  A trajectory occurs at most once per frame.  g_ntraj (n_streams, n_classes) and h_ntraj (K, n_streams, n_classes)
+ * int32 are the trajectory counts (each <= 4096, more is WT_ERR_CAPACITY).
+ * mat_offsets (K * n_streams * n_classes + 1) int64, device form only: where each problem's two matrices start inside the
+ * matrix part of the workspace, in floats; problem p needs 2 * min(g, h) * (max(g, h) | 1) floats, matrix_floats =
+ * mat_offsets[last] is the total.  The host form computes them.
+ * max_gt_traj / max_hyp_traj: upper bounds of g_ntraj / h_ntraj (size the per-wavefront scratch).
+ * Outputs: id_counts (K, n_streams, n_classes, 2, 3) int64 = idtp, gt, hyp for LEVEL_1, LEVEL_2;
+ *          hyp_idmatch (n_hyp, 2) int64, may be NULL: per result row and level the ground-truth row the box is
+ *          identity-matched to, -1 not matched, -2 took no part or is left out at that level.  The matching behind it is ONE
+ *          optimal assignment; idtp does not depend on which.
+ * The device form takes device pointers (thr: host pointer, read before the call returns), is stream-ordered, never allocates
+ * or synchronises, and reports in status_dev (device int32) 0 or the WT_ERR_* a wavefront met (capacity: counts or offsets
+ * that do not fit the rows; assignment did not converge), after which that wavefront's outputs stay zero.  A workspace smaller
+ * than wt_mot_identity_workspace() says is WT_ERR_INVALID and nothing is launched.  It does not check the layout; the host form
+ * does (WT_ERR_INVALID names the frame), stages everything itself, and fails with WT_ERR_INVALID when the workspace it needs
+ * exceeds workspace_limit_bytes (0 = no limit): the caller then scores fewer results per call.
+ * wt_mot_identity_limits: 4096, and the sizes up to which the star arrays (2 min + max ints) and the zero bitmaps
+ * (min * ceil(max / 64) * 8 bytes) of the largest problem stay in LDS; beyond them they live in the workspace. */
+void wt_mot_identity_limits(int32_t* max_trajectories, int64_t* lds_stars_bytes, int64_t* lds_zmask_bytes);
+size_t wt_mot_identity_workspace(int32_t k_sets, int32_t n_streams, int32_t n_classes, int64_t max_gt_traj, int64_t max_hyp_traj,
+                                 int64_t matrix_floats);
+int wt_mot_identity_dev(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                        const int32_t* g_category, const int32_t* g_level, const int32_t* g_traj,
+                        int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                        int32_t k_sets, int64_t n_hyp, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                        const double* hx, const double* hy, const double* hw, const double* hh,
+                        const int32_t* h_category, const int32_t* h_traj,
+                        const int32_t* g_ntraj, const int32_t* h_ntraj, const int64_t* mat_offsets, int64_t matrix_floats,
+                        int32_t n_classes, const double* thr, int64_t max_gt_traj, int64_t max_hyp_traj,
+                        int64_t* id_counts, int64_t* hyp_idmatch, int32_t* status_dev,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int wt_mot_identity_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                         const int32_t* g_category, const int32_t* g_level, const int32_t* g_traj,
+                         int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t k_sets, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                         const double* hx, const double* hy, const double* hw, const double* hh,
+                         const int32_t* h_category, const int32_t* h_traj,
+                         const int32_t* g_ntraj, const int32_t* h_ntraj,
+                         int32_t n_classes, const double* thr, size_t workspace_limit_bytes,
+                         int64_t* id_counts, int64_t* hyp_idmatch);
+
+/* =================================================================================================
  * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

@@ -1,14 +1,15 @@
 """MOTA / MOTP of tracking results against ground truth, and the threshold sweep that tunes the tracker's flags.
 
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
-        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT]
+        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--identity] [--rank-by idf1]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
 kernel behind ``wt_mot_eval_host`` (include/waymotrack.h): K results are scored in one launch, which is what makes a
-sweep over tracker settings cost seconds.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
+sweep over tracker settings cost seconds.  --identity adds identity preservation (IDF1 / IDP / IDR, Ristani et al. 2016; DESIGN.md
+section 18) through ``wt_mot_identity_host``: per problem one trajectory-by-trajectory overlap matrix and one global assignment.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
 """
 import argparse
 import ctypes as C
@@ -387,6 +388,232 @@ class DeviceEvaluation(object):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# identity preservation (IDF1 / IDP / IDR)
+ID_FIELDS = ('idtp', 'gt', 'hyp')
+DEFAULT_WORKSPACE_LIMIT = 1 << 30                  # bytes of device workspace one wt_mot_identity call may ask for
+
+
+def _local_index(group, ident, n_groups):
+    """Rows with group >= 0: number the distinct `ident` values inside every group from 0.  Returns (index per row, 0 for the
+    other rows; count per group)."""
+    index = np.zeros(group.size, np.int32)
+    ok = group >= 0
+    if not ok.any():
+        return index, np.zeros(n_groups, np.int32)
+    base = int(ident[ok].max()) + 1
+    u, inv = np.unique(group[ok] * base + ident[ok], return_inverse=True)
+    ug = u // base
+    first = np.searchsorted(ug, np.arange(n_groups))
+    index[ok] = (inv - first[ug[inv]]).astype(np.int32)
+    return index, np.bincount(ug, minlength=n_groups).astype(np.int32)
+
+
+def trajectory_indices(gt, packed, n_classes):
+    """Class-local trajectory indices of wt_mot_identity_* (include/waymotrack.h) for pack_results() output:
+    g_traj, g_ntraj (n_streams, n_classes), h_traj, h_ntraj (K, n_streams, n_classes)."""
+    n_streams = len(gt['stream_keys'])
+    sfo = gt['stream_frame_offsets']
+
+    def groups(cat, frame_offsets, first):
+        n = int(frame_offsets[-1])
+        frame = np.searchsorted(frame_offsets, np.arange(n), side='right') - 1
+        stream = np.searchsorted(sfo, frame, side='right') - 1
+        c = cat[:n].astype(np.int64)
+        return np.where((c >= 1) & (c <= n_classes), (first + stream) * n_classes + c - 1, -1)
+    g_group = groups(gt['category'], gt['frame_gt_offsets'], 0) if gt['frame_ids'].size else np.zeros(0, np.int64)
+    g_traj, g_ntraj = _local_index(g_group, gt['gt_id'].astype(np.int64)[:g_group.size], n_streams * n_classes)
+    set_rows = packed['set_row_offsets']
+    K = len(set_rows) - 1
+    h_group = np.full(int(set_rows[-1]), -1, np.int64)
+    for k in range(K):
+        lo = int(set_rows[k])
+        on = groups(packed['category'][lo:], packed['frame_hyp_offsets'][k], k * n_streams)
+        h_group[lo:lo + on.size] = on
+    h_traj, h_ntraj = _local_index(h_group, packed['h_id'].astype(np.int64), K * n_streams * n_classes)
+    return (np.ascontiguousarray(g_traj), g_ntraj.reshape(n_streams, n_classes),
+            np.ascontiguousarray(h_traj), h_ntraj.reshape(K, n_streams, n_classes))
+
+
+def _matrix_floats(g_ntraj, h_ntraj):
+    """Per problem, the floats of its two matrices: 2 * min * (max | 1) (munkres_ld of csrc/sort_device.h)."""
+    g = np.broadcast_to(g_ntraj.astype(np.int64), h_ntraj.shape)
+    h = h_ntraj.astype(np.int64)
+    return 2 * np.minimum(g, h) * (np.maximum(g, h) | 1)
+
+
+def identity_row(idtp, gt, hyp):
+    return {'idtp': int(idtp), 'idfn': int(gt - idtp), 'idfp': int(hyp - idtp), 'gt': int(gt), 'hyp': int(hyp),
+            'idp': idtp / hyp if hyp else math.nan, 'idr': idtp / gt if gt else math.nan,
+            'idf1': 2 * idtp / (gt + hyp) if gt + hyp else math.nan}
+
+
+class IdentityResult(object):
+    """Identity scores of one tracking result.
+
+    id_counts   (n_streams, n_classes, 2, 3) int64: idtp, gt, hyp for LEVEL_1, LEVEL_2, per stream
+    table       {class id or 'ALL': {1: row, 2: row}}, row = idtp, idfn, idfp, gt, hyp, idp, idr, idf1 ('ALL' = classes 1, 2, 4,
+                counts summed stream by stream)
+    ignored_rows   result rows that took no part
+    hyp_idmatch (with per_row=True) (rows, 2) int64 in file order, LEVEL_1 then LEVEL_2: index of the identity-matched annotation
+                in the ground-truth file's list, -1 not matched, -2 took no part or left out at that level."""
+
+    def __init__(self, id_counts, ignored_rows, stream_keys, hyp_idmatch=None):
+        self.id_counts, self.ignored_rows, self.stream_keys, self.hyp_idmatch = id_counts, ignored_rows, stream_keys, hyp_idmatch
+        self.table = {}
+        n_classes = id_counts.shape[1]
+        for c in list(range(1, n_classes + 1)) + ['ALL']:
+            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
+            self.table[c] = {}
+            for li, lv in enumerate(LEVELS):
+                tot = id_counts[:, [cc - 1 for cc in classes], li, :].reshape(-1, 3).sum(axis=0)
+                self.table[c][lv] = identity_row(int(tot[0]), int(tot[1]), int(tot[2]))
+
+    def idf1(self, level=2, category='ALL'):
+        return self.table[category][level]['idf1']
+
+    def as_json(self):
+        return {'ignored_rows': int(self.ignored_rows),
+                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
+
+
+def _identity_results(gt, packed, id_counts, hyp_idmatch, per_row):
+    results = []
+    set_rows = packed['set_row_offsets']
+    for k in range(len(set_rows) - 1):
+        lo, hi = int(set_rows[k]), int(set_rows[k + 1])
+        match = None
+        if per_row:
+            m = hyp_idmatch[lo:hi]
+            match = np.empty((hi - lo, 2), np.int64)
+            match[packed['orders'][k]] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
+        ignored = (hi - lo) - int(packed['frame_hyp_offsets'][k][-1])
+        results.append(IdentityResult(id_counts[k], ignored, gt['stream_keys'], match))
+    return results
+
+
+def _identity_workspace(lib, k, n_streams, n_classes, max_g, max_h, floats):
+    lib.wt_mot_identity_workspace.restype = C.c_size_t
+    return int(lib.wt_mot_identity_workspace(C.c_int32(k), C.c_int32(n_streams), C.c_int32(n_classes), C.c_int64(max_g), C.c_int64(max_h),
+                                             C.c_int64(floats)))
+
+
+def _identity_calls(lib, g_ntraj, h_ntraj, limit):
+    """Consecutive result sets per call: as many as fit the workspace limit, at least one."""
+    K, n_streams, n_classes = h_ntraj.shape
+    floats = _matrix_floats(g_ntraj, h_ntraj).reshape(K, -1).sum(axis=1)
+    max_g = int(g_ntraj.max()) if g_ntraj.size else 0
+    calls, k0 = [], 0
+    while k0 < K:
+        k1 = k0 + 1
+        while k1 < K:
+            max_h = int(h_ntraj[k0:k1 + 1].max()) if h_ntraj[k0:k1 + 1].size else 0
+            need = _identity_workspace(lib, k1 + 1 - k0, n_streams, n_classes, max_g, max_h, int(floats[k0:k1 + 1].sum()))
+            if need == 0 or (limit and need > limit):
+                break
+            k1 += 1
+        calls.append((k0, k1))
+        k0 = k1
+    return calls
+
+
+def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, workspace_limit_bytes=DEFAULT_WORKSPACE_LIMIT):
+    """IDF1 / IDP / IDR of K tracking results against one ground truth through wt_mot_identity_host: as few calls as the workspace
+    limit allows (the results do not depend on the split).  Returns a list of K IdentityResult."""
+    lib = _lib.lib()
+    thr = _lib.as_f64(iou_threshold)
+    n_classes = int(thr.size)
+    p = pack_results(gt, tracks_list, n_classes)
+    g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, p, n_classes)
+    K = len(tracks_list)
+    n_frames = int(gt['frame_ids'].size)
+    n_streams = len(gt['stream_keys'])
+    id_counts = np.zeros((K, n_streams, n_classes, 2, 3), np.int64)
+    set_rows = p['set_row_offsets']
+    hyp_idmatch = np.full((int(set_rows[-1]), 2), -2, np.int64)
+    g_ntraj_c = np.ascontiguousarray(g_ntraj)
+    for k0, k1 in _identity_calls(lib, g_ntraj, h_ntraj, workspace_limit_bytes):
+        lo, hi = int(set_rows[k0]), int(set_rows[k1])
+        rows = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
+        fho = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
+        hn = np.ascontiguousarray(h_ntraj[k0:k1])
+        cnt = np.zeros((k1 - k0, n_streams, n_classes, 2, 3), np.int64)
+        match = np.full((hi - lo, 2), -2, np.int64)
+        rc = lib.wt_mot_identity_host(
+            C.c_int64(gt['x'].size), _lib.ptr(gt['x']), _lib.ptr(gt['y']), _lib.ptr(gt['w']), _lib.ptr(gt['h']),
+            _lib.ptr(gt['category']), _lib.ptr(gt['level']), _lib.ptr(g_traj),
+            C.c_int64(n_frames), _lib.ptr(gt['frame_gt_offsets']), C.c_int32(n_streams), _lib.ptr(gt['stream_frame_offsets']),
+            C.c_int32(k1 - k0), _lib.ptr(rows), _lib.ptr(fho),
+            _lib.ptr(p['x'][lo:hi]), _lib.ptr(p['y'][lo:hi]), _lib.ptr(p['w'][lo:hi]), _lib.ptr(p['h'][lo:hi]),
+            _lib.ptr(p['category'][lo:hi]), _lib.ptr(h_traj[lo:hi]), _lib.ptr(g_ntraj_c), _lib.ptr(hn),
+            C.c_int32(n_classes), _lib.ptr(thr), C.c_size_t(int(workspace_limit_bytes or 0)), _lib.ptr(cnt),
+            _lib.ptr(match) if per_row else None)
+        _lib.check(rc, 'wt_mot_identity_host')
+        id_counts[k0:k1] = cnt
+        hyp_idmatch[lo:hi] = match
+    return _identity_results(gt, p, id_counts, hyp_idmatch, per_row)
+
+
+class DeviceIdentity(object):
+    """evaluate_identity with everything resident in HBM, beside DeviceEvaluation: ``launch()`` enqueues one wt_mot_identity_dev
+    on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.  All K results go into
+    one call; workspace_bytes overrides the size of the workspace tensor (a smaller one is refused by the library)."""
+
+    def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, workspace_bytes=None):
+        import torch
+        self.torch = torch
+        self.lib = _lib.lib()
+        self.gt = gt
+        self.thr = _lib.as_f64(iou_threshold)
+        self.n_classes = int(self.thr.size)
+        self.p = pack_results(gt, tracks_list, self.n_classes)
+        self.K = len(tracks_list)
+        self.n_frames = int(gt['frame_ids'].size)
+        self.n_streams = len(gt['stream_keys'])
+        self.n_hyp = int(self.p['set_row_offsets'][-1])
+        g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, self.p, self.n_classes)
+        self.g_ntraj, self.h_ntraj = g_ntraj, h_ntraj
+        self.max_g = int(g_ntraj.max()) if g_ntraj.size else 0
+        self.max_h = int(h_ntraj.max()) if h_ntraj.size else 0
+        floats = _matrix_floats(g_ntraj, h_ntraj).reshape(-1)
+        mat_offsets = np.concatenate([[0], np.cumsum(floats)]).astype(np.int64)
+        self.matrix_floats = int(mat_offsets[-1])
+        self.ws_bytes = _identity_workspace(self.lib, self.K, self.n_streams, self.n_classes, self.max_g, self.max_h, self.matrix_floats)
+        if not self.ws_bytes:
+            _lib.check(4, 'wt_mot_identity_workspace')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros(1, dtype=torch.from_numpy(a).dtype, device=dev)
+        self.g = dict((n, up(gt[n])) for n in ('x', 'y', 'w', 'h', 'category', 'level', 'frame_gt_offsets', 'stream_frame_offsets'))
+        self.h = dict((n, up(self.p[n])) for n in ('x', 'y', 'w', 'h', 'category', 'set_row_offsets', 'frame_hyp_offsets'))
+        self.g['traj'], self.h['traj'] = up(g_traj), up(h_traj)
+        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = up(g_ntraj), up(h_ntraj), up(mat_offsets)
+        self.id_counts = torch.zeros((self.K, self.n_streams, self.n_classes, 2, 3), dtype=torch.int64, device=dev)
+        self.hyp_idmatch = torch.zeros((max(1, self.n_hyp), 2), dtype=torch.int64, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=dev)
+
+    def launch(self):
+        g, h, v = self.g, self.h, C.c_void_p
+        d = lambda t: v(t.data_ptr())
+        rc = self.lib.wt_mot_identity_dev(
+            C.c_int64(self.gt['x'].size), d(g['x']), d(g['y']), d(g['w']), d(g['h']), d(g['category']), d(g['level']), d(g['traj']),
+            C.c_int64(self.n_frames), d(g['frame_gt_offsets']), C.c_int32(self.n_streams), d(g['stream_frame_offsets']),
+            C.c_int32(self.K), C.c_int64(self.n_hyp), d(h['set_row_offsets']), d(h['frame_hyp_offsets']),
+            d(h['x']), d(h['y']), d(h['w']), d(h['h']), d(h['category']), d(h['traj']),
+            d(g['ntraj']), d(h['ntraj']), d(self.mat_offsets), C.c_int64(self.matrix_floats),
+            C.c_int32(self.n_classes), _lib.ptr(self.thr), C.c_int64(self.max_g), C.c_int64(self.max_h),
+            d(self.id_counts), d(self.hyp_idmatch), d(self.status),
+            d(self.ws), C.c_size_t(int(self.ws.numel())), v(self.torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, 'wt_mot_identity_dev')
+
+    def results(self, per_row=False):
+        self.torch.cuda.current_stream().synchronize()
+        st = int(self.status.item())
+        if st:
+            raise _lib.WaymoTrackError('wt_mot_identity_dev failed: %s (status reported by the kernel)' % _lib._STATUS.get(st, st))
+        return _identity_results(self.gt, self.p, self.id_counts.cpu().numpy(), self.hyp_idmatch.cpu().numpy()[:self.n_hyp], per_row)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # threshold sweep
 def _grid_values(text):
     """'0.5:1.0:0.05' (inclusive range) or '0.0,0.01,0.1' -> list of floats."""
@@ -397,7 +624,7 @@ def _grid_values(text):
     return [float(v) for v in text.split(',')]
 
 
-def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4):
+def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota'):
     """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
 
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
@@ -406,6 +633,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     K = |score| x |iou| x |max_age| x |min_hits| settings - and the best point is read off per class for each
     (max_age, min_hits); no product over classes is tracked.  Best = highest ALL MOTA at the level; ties go to the setting that
     comes first in grid order (max_age, min_hits, then per class score, iou).
+    identity=True scores every setting with evaluate_identity as well and adds 'IDF1' (with 'id_counts') to every ranked setting.
+    rank_by='idf1' (implies identity): per (max_age, min_hits) each class takes the grid point with its own highest class IDF1, the
+    combined row reports ALL from the summed identity counts and the rows are ranked by it (this is not the
+    argmax of ALL IDF1 over one shared grid point - hyp varies with the setting, and per-class flags can only be tuned per class).
     Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}}."""
     if isinstance(gt, str):
         gt = load_ground_truth(gt)
@@ -430,7 +661,12 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                     out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
                     settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)})
                     tracks.append(tracks_from_packed(packed, out))
+    if rank_by not in ('mota', 'idf1'):
+        raise ValueError("rank_by must be 'mota' or 'idf1'")
+    identity = identity or rank_by == 'idf1'
     results = evaluate_tracks(gt, tracks, iou_threshold)
+    id_results = evaluate_identity(gt, tracks, iou_threshold) if identity else None
+    key = 'IDF1' if rank_by == 'idf1' else 'MOTA'
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
     per_mm = len(grid['score']) * len(grid['iou'])
@@ -438,26 +674,39 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
             pick, total = {}, dict((f, 0) for f in FIELDS)
+            id_total = dict((f, 0) for f in ID_FIELDS)
             for c in classes:
                 top = None
                 for k in range(g, g + per_mm):
                     row = results[k].table[c][lv]
                     errors = row['fn'] + row['fp'] + row['idsw']       # gt is the same for every setting: fewest errors = highest MOTA
+                    if rank_by == 'idf1':                             # highest class IDF1 (NaN = nothing on either side: last)
+                        v = id_results[k].table[c][lv]['idf1']
+                        errors = -v if v == v else math.inf
                     if top is None or errors < top[0]:
                         top = (errors, k)
                 pick[c] = top[1]
                 for f in FIELDS:
                     total[f] += results[top[1]].table[c][lv][f]
+                if identity:
+                    for f in ID_FIELDS:
+                        id_total[f] += id_results[top[1]].table[c][lv][f]
             mota = 1.0 - (total['fn'] + total['fp'] + total['idsw']) / total['gt'] if total['gt'] else math.nan
             score_thr, iou_thr = [1.0] * n_classes, [1.0] * n_classes      # classes that are not evaluated are not tracked
             for c in classes:
                 score_thr[c - 1], iou_thr[c - 1] = settings[pick[c]]['score'], settings[pick[c]]['iou']
             combos.append({'max_age': settings[g]['max_age'], 'min_hits': settings[g]['min_hits'], 'score_threshold': score_thr,
                            'iou_threshold': iou_thr, 'MOTA': mota, 'counts': total})
-        order = sorted(range(len(combos)), key=lambda i: (-(combos[i]['MOTA'] if combos[i]['MOTA'] == combos[i]['MOTA'] else -math.inf), i))
+            if identity:
+                combos[-1]['IDF1'] = identity_row(id_total['idtp'], id_total['gt'], id_total['hyp'])['idf1']
+                combos[-1]['id_counts'] = id_total
+        order = sorted(range(len(combos)), key=lambda i: (-(combos[i][key] if combos[i][key] == combos[i][key] else -math.inf), i))
         ranked[lv] = [combos[i] for i in order]
         best[lv] = ranked[lv][0] if ranked[lv] else None
-    return {'settings': settings, 'results': results, 'ranked': ranked, 'best': best}
+    out = {'settings': settings, 'results': results, 'ranked': ranked, 'best': best}
+    if identity:
+        out['id_results'] = id_results
+    return out
 
 
 def flag_line(setting):
@@ -478,6 +727,16 @@ def format_table(result, name=''):
     return '\n'.join(lines)
 
 
+def format_identity_table(result, name=''):
+    lines = ['%s  identity' % name,
+             '%-6s %-8s %9s %9s %9s %9s %9s %9s' % ('class', 'level', 'IDTP', 'IDFN', 'IDFP', 'IDF1', 'IDP', 'IDR')]
+    for c, rows in result.table.items():
+        for lv in LEVELS:
+            r = rows[lv]
+            lines.append('%-6s LEVEL_%d  %9d %9d %9d %9.5f %9.5f %9.5f' % (c, lv, r['idtp'], r['idfn'], r['idfp'], r['idf1'], r['idp'], r['idr']))
+    return '\n'.join(lines)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('tracks', nargs='*', help='tracking JSON files written by tracking/track.py')
@@ -490,6 +749,8 @@ def build_parser():
     parser.add_argument('--max-age', default='1,2,3')
     parser.add_argument('--min-hits', default='0,1')
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
+    parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
+    parser.add_argument('--rank-by', choices=('mota', 'idf1'), default='mota', help='what the sweep ranks by (idf1 implies --identity)')
     return parser
 
 
@@ -499,26 +760,42 @@ def main(argv=None):
     if args.sweep:
         grid = {'score': _grid_values(args.score_grid), 'iou': _grid_values(args.iou_grid),
                 'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')]}
-        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold))
+        identity = args.identity or args.rank_by == 'idf1'
+        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by)
         for lv in LEVELS:
             print('LEVEL_%d: %d settings tracked, best per class combined for each (max_age, min_hits)' % (lv, len(res['settings'])))
             for r in res['ranked'][lv][:args.top]:
-                print('  MOTA %9.5f  %s' % (r['MOTA'], flag_line(r)))
+                if identity:
+                    print('  MOTA %9.5f  IDF1 %9.5f  %s' % (r['MOTA'], r['IDF1'], flag_line(r)))
+                else:
+                    print('  MOTA %9.5f  %s' % (r['MOTA'], flag_line(r)))
         if args.json:
             with open(args.json, 'wt') as fp:
-                json.dump({'settings': res['settings'], 'tables': [r.as_json() for r in res['results']],
-                           'ranked': dict(('LEVEL_%d' % lv, v) for lv, v in res['ranked'].items())}, fp)
+                doc = {'settings': res['settings'], 'tables': [r.as_json() for r in res['results']],
+                       'ranked': dict(('LEVEL_%d' % lv, v) for lv, v in res['ranked'].items())}
+                if identity:
+                    doc['identity_tables'] = [r.as_json() for r in res['id_results']]
+                    doc['rank_by'] = args.rank_by
+                json.dump(doc, fp)
         if res['best'][2] is not None:
             print(flag_line(res['best'][2]))
         return 0
     if not args.tracks:
         raise SystemExit('give at least one tracking JSON, or --sweep DETECTIONS.json')
-    results = evaluate_tracks(gt, [load_tracks(p) for p in args.tracks], args.iou_threshold)
-    for path, r in zip(args.tracks, results):
+    tracks = [load_tracks(p) for p in args.tracks]
+    results = evaluate_tracks(gt, tracks, args.iou_threshold)
+    id_results = evaluate_identity(gt, tracks, args.iou_threshold) if args.identity else [None] * len(results)
+    for path, r, ir in zip(args.tracks, results, id_results):
         print(format_table(r, path))
+        if ir is not None:
+            print(format_identity_table(ir, path))
     if args.json:
+        doc = dict((p, r.as_json()) for p, r in zip(args.tracks, results))
+        for p, ir in zip(args.tracks, id_results):
+            if ir is not None:
+                doc[p]['identity'] = ir.as_json()['table']
         with open(args.json, 'wt') as fp:
-            json.dump(dict((p, r.as_json()) for p, r in zip(args.tracks, results)), fp)
+            json.dump(doc, fp)
     return 0
 
 
