@@ -179,6 +179,9 @@ size_t wd_deform_packed_weight_floats(int c_in, int c_out, int groups);
 int wd_deform_pack_weight(const float* weight_oihw, int c_in, int c_out, int groups, float* packed, void* stream);
 /* Name of the kernel wd_deform_conv3x3_f32 dispatches for a shape (host-only; profiling / bench labels). */
 const char* wd_deform_conv3x3_variant(int c_in, int groups, int stride, int pad, int has_offset);
+/* Name of the kernel the calling thread's most recent wd_deform_conv3x3_f32 / _hint_f32 / _tab_f32 call launched: unlike the query above it
+ * knows the modulation mask and the far_offsets hint, which reroute the ping-pong kernel's shapes; "" if that call launched nothing. */
+const char* wd_deform_conv3x3_last_kernel(void);
 int wd_deform_conv3x3_f32(const float* x, const float* offset, const float* mask, const float* packed_weight,
                           const float* scale, const float* bias, int relu,
                           int batch, int h, int w, int c_in, int c_out, int groups, int stride, int pad,

@@ -86,8 +86,9 @@ def deform_conv3x3(x, offset, weight, groups, stride=1, pad=1, mask=None):
     Cout = weight.shape[0]
     Ho = (H + 2 * pad - 3) // stride + 1
     Wo = (W + 2 * pad - 3) // stride + 1
-    ho = torch.arange(Ho, dtype=torch.float64).view(1, Ho, 1)
-    wo = torch.arange(Wo, dtype=torch.float64).view(1, 1, Wo)
+    dev = x.device                                                # (a device tensor keeps the whole evaluation on that device)
+    ho = torch.arange(Ho, dtype=torch.float64, device=dev).view(1, Ho, 1)
+    wo = torch.arange(Wo, dtype=torch.float64, device=dev).view(1, 1, Wo)
     cols = []
     for k in range(9):
         kh, kw = k // 3, k % 3
@@ -96,7 +97,7 @@ def deform_conv3x3(x, offset, weight, groups, stride=1, pad=1, mask=None):
         inside = (hy > -1) & (wx > -1) & (hy < H) & (wx < W)
         hl = torch.floor(hy); wl = torch.floor(wx)
         lh = hy - hl; lw = wx - wl
-        val = torch.zeros((N, Cin, Ho, Wo), dtype=torch.float64)
+        val = torch.zeros((N, Cin, Ho, Wo), dtype=torch.float64, device=dev)
         for dh, dw, wgt in ((0, 0, (1 - lh) * (1 - lw)), (0, 1, (1 - lh) * lw), (1, 0, lh * (1 - lw)), (1, 1, lh * lw)):
             hh = (hl + dh).long(); ww = (wl + dw).long()
             ok = inside & (hh >= 0) & (hh <= H - 1) & (ww >= 0) & (ww <= W - 1)
@@ -110,7 +111,7 @@ def deform_conv3x3(x, offset, weight, groups, stride=1, pad=1, mask=None):
     col = torch.stack(cols, dim=2)                                # (N,Cin,9,Ho,Wo)
     cg = Cin // groups
     cog = Cout // groups
-    out = torch.zeros((N, Cout, Ho, Wo), dtype=torch.float64)
+    out = torch.zeros((N, Cout, Ho, Wo), dtype=torch.float64, device=dev)
     for g in range(groups):
         c = col[:, g * cg:(g + 1) * cg].reshape(N, cg * 9, Ho * Wo)
         wg = weight[g * cog:(g + 1) * cog].reshape(cog, cg * 9)

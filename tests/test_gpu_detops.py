@@ -1,5 +1,7 @@
 """Detector custom ops (HIP, through the C ABI) against the PyTorch restatement in oracle/detops_ref.py.
-float32 kernels vs float64 references: tolerances stated per test (north_star: 1e-4 on boxes/scores)."""
+float32 kernels vs float64 references; every test states its tolerance in its assertion (north_star: 1e-4 on boxes/scores).  One or two
+convenient shapes per kernel: the edge and multi-tile shapes of the forward kernels (several tiles per persistent workgroup, maps below a tile,
+rerouted dispatch, all GroupNorm widths) are in tests/test_gpu_forward_ops.py, those of the backward kernels in tests/test_gpu_backward_ops.py."""
 import os
 
 import numpy as np

@@ -765,21 +765,32 @@ static int deform_variant(int cg, int stride, int pad, bool has_offset, const ch
     return 0;
 }
 
-extern "C" {
-
-const char* wd_deform_conv3x3_variant(int c_in, int groups, int stride, int pad, int has_offset) {
-    if (groups <= 0 || c_in % groups) return "invalid";
-    const int cg = c_in / groups;
-    switch (deform_variant(cg, stride, pad, has_offset != 0, getenv("WD_DEFORM_PATCH"))) {
+// kernel name of a variant (deform_variant; 0 = the gather kernel in its four widths, with / without offsets)
+static const char* variant_kernel_name(int variant, int cg, bool has_offset) {
+    switch (variant) {
         case 3: return cg == 16 ? "deform_conv3x3_pp_kernel<16>" : "deform_conv3x3_pp_kernel<32>";
         case 2: return cg == 16 ? "deform_conv3x3_lds_kernel<16>" : "deform_conv3x3_lds_kernel<32>";
         case 1: return cg == 16 ? "deform_conv3x3_patch_kernel<16>" : cg == 32 ? "deform_conv3x3_patch_kernel<32>" : "deform_conv3x3_patch_kernel<64>";
         default: break;
     }
-    if (!has_offset && cg == 8 && stride == 1 && pad == 1 && (c_in % 128) == 0) return "grouped_conv3x3_c8_kernel";
     if (has_offset) return cg == 8 ? "deform_conv3x3_kernel<8,true>" : cg == 16 ? "deform_conv3x3_kernel<16,true>" : cg == 32 ? "deform_conv3x3_kernel<32,true>" : "deform_conv3x3_kernel<64,true>";
     return cg == 8 ? "deform_conv3x3_kernel<8,false>" : cg == 16 ? "deform_conv3x3_kernel<16,false>" : cg == 32 ? "deform_conv3x3_kernel<32,false>" : "deform_conv3x3_kernel<64,false>";
 }
+
+// what the last wd_deform_conv3x3*_f32 call of this thread launched (wd_deform_conv3x3_last_kernel)
+static thread_local const char* last_kernel = "";
+
+extern "C" {
+
+const char* wd_deform_conv3x3_variant(int c_in, int groups, int stride, int pad, int has_offset) {
+    if (groups <= 0 || c_in % groups) return "invalid";
+    const int cg = c_in / groups;
+    const int variant = deform_variant(cg, stride, pad, has_offset != 0, getenv("WD_DEFORM_PATCH"));
+    if (variant == 0 && !has_offset && cg == 8 && stride == 1 && pad == 1 && (c_in % 128) == 0) return "grouped_conv3x3_c8_kernel";
+    return variant_kernel_name(variant, cg, has_offset != 0);
+}
+
+const char* wd_deform_conv3x3_last_kernel(void) { return last_kernel; }
 
 size_t wd_deform_packed_weight_floats(int c_in, int c_out, int groups) {
     if (groups <= 0 || c_in % groups || c_in != c_out) return 0;
@@ -842,13 +853,17 @@ int wd_deform_conv3x3_tab_f32(const float* x, const float* offset, const float* 
     // (16 / 32 channels per group: register-fragment kernel, 64: shared-slab patch kernel); stride 2, plain grouped
     // convolution and 8 channels per group -> L1-gather kernel.  WD_DEFORM_PATCH=lds|all|none overrides (experiments).
     const char* mode = getenv("WD_DEFORM_PATCH");
+    last_kernel = "";
     // res2: plain grouped conv with 8 channels per group -> vector-unit kernel (det_gconv.hip)
-    if (!offset && !mask && cg == 8 && stride == 1 && pad == 1 && (c_in % 128) == 0 && ((uintptr_t)y & 7) == 0)
+    if (!offset && !mask && cg == 8 && stride == 1 && pad == 1 && (c_in % 128) == 0 && ((uintptr_t)y & 7) == 0) {
+        last_kernel = "grouped_conv3x3_c8_kernel";
         return wd_grouped_conv3x3_c8_launch(x, packed_weight, scale, bias, relu, batch, h, w, c_in, stream, y);
+    }
     int variant = deform_variant(cg, stride, pad, offset != nullptr, mode);
     if (variant == 3 && stride != 1 && mask) variant = 0;    // stride 2 + modulation mask: the gather kernel
     if (variant == 3 && stride == 1 && (mask || far_offsets)) variant = 2;  // the ping-pong kernel has no modulation mask; with many samples leaving
                                                              // the 14x14 patch its per-lane far path loses to the per-tile one
+    if (cg == 8 || cg == 16 || cg == 32 || cg == 64) last_kernel = variant_kernel_name(variant, cg, offset != nullptr);
     if (variant == 3)
         return wd_deform_pp_launch(x, offset, packed_weight, scale, bias, relu, batch, h, w, c_in, cg, stride, stream, y, table);
     if (variant == 2) {

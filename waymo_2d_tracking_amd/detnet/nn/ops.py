@@ -162,11 +162,9 @@ def deform_conv3x3(x, offset, packed_weight, groups, stride=1, pad=1, scale=None
                'wd_deform_conv3x3_f32')
     if log is not None:
         e1.record()
-        fn = _lib.lib().wd_deform_conv3x3_variant
+        fn = _lib.lib().wd_deform_conv3x3_last_kernel         # what the call above launched (mask and far_offsets reroute some shapes)
         fn.restype = C.c_char_p
-        name = fn(C.c_int(c), C.c_int(groups), C.c_int(stride), C.c_int(pad), C.c_int(0 if offset is None else 1)).decode()
-        if far_offsets and 'pp_kernel' in name:
-            name = 'deform_conv3x3_lds_kernel<32>'
+        name = fn().decode()
         log.append(('%s: deform_conv3x3 C=%d %dx%d s%d%s' % (name, c, ho, wo, stride, '' if offset is not None else ' (no offsets)'),
                     2.0 * c * (c // groups) * 9 * ho * wo * n, e0, e1))
     return y
