@@ -1,7 +1,7 @@
 """Detector custom ops (HIP, through the C ABI) against the PyTorch restatement in oracle/detops_ref.py.
 float32 kernels vs float64 references; every test states its tolerance in its assertion (north_star: 1e-4 on boxes/scores).  One or two
-convenient shapes per kernel: the edge and multi-tile shapes of the forward kernels (several tiles per persistent workgroup, maps below a tile,
-rerouted dispatch, all GroupNorm widths) are in tests/test_gpu_forward_ops.py, those of the backward kernels in tests/test_gpu_backward_ops.py."""
+convenient shapes per kernel: the edge and multi-tile shapes of the forward kernels are in tests/test_gpu_forward_ops.py, those of the backward
+kernels in tests/test_gpu_backward_ops.py, the exact-answer edge cases of the NMS sweeps and the kept-row compaction in tests/test_gpu_nms_edges.py."""
 import os
 
 import numpy as np

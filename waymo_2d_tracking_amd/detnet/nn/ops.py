@@ -68,12 +68,12 @@ def nms_sorted(boxes, idxs, iou_threshold):
     return nms_sorted_mask(boxes, idxs, iou_threshold).bool()
 
 
-def nms_sorted_mask(boxes, idxs, iou_threshold):
-    """nms_sorted as a uint8 mask (no dtype conversion launch)."""
+def nms_sorted_mask(boxes, idxs, iou_threshold, return_count=False):
+    """nms_sorted as a uint8 mask (no dtype conversion launch).  return_count: (mask, int32[1] number of kept rows, on the device)."""
     n = boxes.shape[0]
     keep = torch.zeros(n, dtype=torch.uint8, device=boxes.device)
     if n == 0:
-        return keep
+        return (keep, torch.zeros(1, dtype=torch.int32, device=boxes.device)) if return_count else keep
     boxes = boxes.contiguous().float()
     if idxs is not None:
         idxs = idxs.contiguous().to(torch.int32)
@@ -87,7 +87,7 @@ def nms_sorted_mask(boxes, idxs, iou_threshold):
     cnt = torch.zeros(1, dtype=torch.int32, device=boxes.device)
     _lib.check(lib.wd_nms_sorted_f32(_p(boxes), _p(idxs), C.c_int(n), C.c_float(iou_threshold), _p(keep), _p(cnt),
                                      _p(ws), C.c_size_t(ws.numel()), _stream()), 'wd_nms_sorted_f32')
-    return keep
+    return (keep, cnt) if return_count else keep
 
 
 def nms_select(boxes, scores, idxs, iou_threshold, cap, valid=None):
@@ -685,13 +685,13 @@ def sort_candidates(boxes, scores, group, valid, valid2=None):
     return out
 
 
-def nms_segmented(boxes, idxs, seg_offsets, iou_threshold):
+def nms_segmented(boxes, idxs, seg_offsets, iou_threshold, return_count=False):
     """Greedy NMS on independent row ranges (each sorted by descending score) in one pair of launches -> uint8 keep mask.
-    seg_offsets: python list of n_seg + 1 row offsets starting at 0."""
+    seg_offsets: python list of n_seg + 1 row offsets starting at 0.  return_count: (mask, int32[n_seg] kept rows per range, on the device)."""
     n = boxes.shape[0]
     keep = torch.zeros(n, dtype=torch.uint8, device=boxes.device)
     if n == 0:
-        return keep
+        return (keep, torch.zeros(len(seg_offsets) - 1, dtype=torch.int32, device=boxes.device)) if return_count else keep
     lib = _lib.lib()
     need = int(lib.wd_nms_workspace(C.c_int(n)))
     key = (boxes.device, torch.cuda.current_stream().cuda_stream)
@@ -704,7 +704,7 @@ def nms_segmented(boxes, idxs, seg_offsets, iou_threshold):
     offs = (C.c_int32 * (n_seg + 1))(*[int(v) for v in seg_offsets])
     _lib.check(lib.wd_nms_segmented_f32(_p(boxes.contiguous()), _p(idxs), offs, C.c_int(n_seg), C.c_float(iou_threshold), _p(keep),
                                         _p(cnt), _p(ws), C.c_size_t(ws.numel()), _stream()), 'wd_nms_segmented_f32')
-    return keep
+    return (keep, cnt) if return_count else keep
 
 
 def box_candidates(boxes, s0, s1, s2, n_valid, score_thresh, img_h, img_w):
