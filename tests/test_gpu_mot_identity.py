@@ -206,6 +206,38 @@ def test_ground_truth_against_itself_and_against_nothing(sequence):
     assert full.table['ALL'][1]['hyp'] >= full.table['ALL'][1]['gt'] == full.table['ALL'][1]['idtp']
 
 
+def test_empty_sides_through_all_four_forms():
+    """The early returns of the library: a result without rows, a result whose rows all lie on frames the ground truth does not
+    have, and a ground truth without streams.  Host and device form of both metrics, each against its reference."""
+    import mot_ref
+    from test_gpu_mot import assert_equals_reference as assert_equals_mot_reference
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    anns = [{'image_id': 'seg/%d/FRONT' % f, 'bbox': [100 * i + 3 * f, 10, 50, 60], 'category_id': 1 + i, 'object_id': 'o%d' % i,
+             'tracking_difficulty_level': 1 + i} for f in range(3) for i in range(2)]
+    rows = [{'image_id': 'seg/%d/FRONT' % f, 'bbox': [100 * i, 12, 50, 60], 'score': 0.9, 'category_id': 1 + i, 'object_id': str(i)}
+            for f in (7, 8) for i in range(2)]
+    for name, a, r, n_gt, ignored in (('empty_result', anns, [], 6, 0), ('rows_on_other_frames', anns, rows, 6, 4),
+                                      ('empty_ground_truth', [], rows[:2], 0, 2)):
+        mot_exp, id_exp = mot_ref.evaluate(a, r), mot_id_ref.evaluate(a, r)
+        assert (mot_exp['table']['ALL'][2]['gt'], mot_exp['ignored_rows'], id_exp['table']['ALL'][2]['gt']) == (n_gt, ignored, n_gt), name
+        gt, tracks = E.load_ground_truth(a), [E.load_tracks(r)]
+        assert len(gt['stream_keys']) == (1 if a else 0)
+        dev_mot, dev_id = E.DeviceEvaluation(gt, tracks), E.DeviceIdentity(gt, tracks)
+        dev_mot.launch()
+        dev_id.launch()
+        mot = [E.evaluate_tracks(gt, tracks, per_row=True)[0], dev_mot.results(per_row=True)[0]]
+        ident = [E.evaluate_identity(gt, tracks, per_row=True)[0], dev_id.results(per_row=True)[0]]
+        for got in mot:
+            assert_equals_mot_reference(got, mot_exp)
+            assert np.array_equal(got.counts, mot[0].counts) and np.array_equal(got.iou_sum, mot[0].iou_sum), name
+            assert np.array_equal(got.hyp_match, mot[0].hyp_match) and np.array_equal(got.hyp_switch, mot[0].hyp_switch), name
+        for got in ident:
+            assert_equals_reference(got, id_exp)
+            assert np.array_equal(got.id_counts, ident[0].id_counts) and got.hyp_idmatch.shape == (len(r), 2), name
+            assert (got.hyp_idmatch == -2).all(), name                       # no row took part
+            assert_rows_consistent(a, r, got)
+
+
 def _limits():
     from waymo_2d_tracking_amd import _lib
     n, stars, zmask = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)

@@ -483,11 +483,6 @@ __global__ __launch_bounds__(kCurveThreads) void det_curve_kernel(
     }
 }
 
-inline char* align256(void* p) {
-    const uintptr_t mis = (uintptr_t)p & 255;
-    return (char*)p + (mis ? 256 - mis : 0);
-}
-
 int check_sizes(int32_t k_sets, int64_t n_images, int32_t n_classes, int32_t n_thr, int64_t n_gt, int64_t n_det) {
     if (k_sets < 1 || n_images < 0 || n_gt < 0 || n_det < 0) { wt::set_error("wt_det_eval: bad argument"); return WT_ERR_INVALID; }
     if (n_classes < 1 || n_classes > kMaxClasses) { wt::set_error("wt_det_eval: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
@@ -534,7 +529,7 @@ int wt_det_eval_dev(int64_t n_gt, const double* gx1, const double* gy1, const do
     const int bits = seg_bits((size_t)K * C);
     size_t tmp = 0;
     WT_TRY(sort_tmp_bytes((size_t)n_det, bits, &tmp));
-    Workspace ws = carve(align256(workspace), (size_t)K, (size_t)C, (size_t)T, (size_t)n_gt, (size_t)n_det, tmp);
+    Workspace ws = carve(wt::align_ptr(workspace), (size_t)K, (size_t)C, (size_t)T, (size_t)n_gt, (size_t)n_det, tmp);
     if (!workspace || workspace_bytes < ws.bytes + 256) {
         wt::set_error("evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
         return WT_ERR_CAPACITY;
@@ -626,14 +621,14 @@ int wt_det_eval_host(int64_t n_gt, const double* gx1, const double* gy1, const d
     wt::DevBuf dg[4], dgl, dio, dia, dsr, dido, dd[5], dcat, dap, dar, dnp, dtp, dfp, dflag, dmatch, dorder, dco, dctp, dcfp, dstat, dws;
     const double* gsrc[4] = {gx1, gy1, gx2, gy2};
     const double* dsrc[5] = {conf, cx, cy, w, h};
-    for (int i = 0; i < 4; ++i) { WT_TRY(dg[i].alloc(8 * ng)); if (ng) WT_HIP(hipMemcpy(dg[i].p, gsrc[i], 8 * ng, hipMemcpyHostToDevice)); }
-    for (int i = 0; i < 5; ++i) { WT_TRY(dd[i].alloc(8 * nd)); if (nd) WT_HIP(hipMemcpy(dd[i].p, dsrc[i], 8 * nd, hipMemcpyHostToDevice)); }
-    WT_TRY(dgl.alloc(4 * ng)); if (ng) WT_HIP(hipMemcpy(dgl.p, g_label, 4 * ng, hipMemcpyHostToDevice));
-    WT_TRY(dcat.alloc(4 * nd)); if (nd) WT_HIP(hipMemcpy(dcat.p, category, 4 * nd, hipMemcpyHostToDevice));
-    WT_TRY(dio.alloc(8 * (ni + 1))); WT_HIP(hipMemcpy(dio.p, image_gt_offsets, 8 * (ni + 1), hipMemcpyHostToDevice));
-    WT_TRY(dia.alloc(8 * ni)); if (ni) WT_HIP(hipMemcpy(dia.p, image_area, 8 * ni, hipMemcpyHostToDevice));
-    WT_TRY(dsr.alloc(8 * (K + 1))); WT_HIP(hipMemcpy(dsr.p, set_row_offsets, 8 * (K + 1), hipMemcpyHostToDevice));
-    WT_TRY(dido.alloc(8 * K * (ni + 1))); WT_HIP(hipMemcpy(dido.p, image_det_offsets, 8 * K * (ni + 1), hipMemcpyHostToDevice));
+    for (int i = 0; i < 4; ++i) WT_TRY(dg[i].upload(gsrc[i], 8 * ng));
+    for (int i = 0; i < 5; ++i) WT_TRY(dd[i].upload(dsrc[i], 8 * nd));
+    WT_TRY(dgl.upload(g_label, 4 * ng));
+    WT_TRY(dcat.upload(category, 4 * nd));
+    WT_TRY(dio.upload(image_gt_offsets, 8 * (ni + 1)));
+    WT_TRY(dia.upload(image_area, 8 * ni));
+    WT_TRY(dsr.upload(set_row_offsets, 8 * (K + 1)));
+    WT_TRY(dido.upload(image_det_offsets, 8 * K * (ni + 1)));
     WT_TRY(dap.alloc(8 * n_out)); WT_TRY(dar.alloc(8 * n_out)); WT_TRY(dnp.alloc(8 * n_out)); WT_TRY(dtp.alloc(8 * n_out)); WT_TRY(dfp.alloc(8 * n_out));
     WT_TRY(dstat.alloc(16));
     if (tp_flag) WT_TRY(dflag.alloc(nd * T));

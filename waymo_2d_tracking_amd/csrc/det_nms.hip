@@ -273,8 +273,7 @@ int wd_nms_sorted_f32(const float* boxes, const int32_t* idxs, int n, float iou_
     }
     if (((uintptr_t)boxes & 15) != 0) { wt::set_error("boxes must be 16-byte aligned"); return WT_ERR_INVALID; }
     const int nb = (n + 63) / 64;
-    const uintptr_t mis = (uintptr_t)workspace & 255;
-    wt::Carver cv((char*)workspace + (mis ? 256 - mis : 0));
+    wt::Carver cv(wt::align_ptr(workspace));
     unsigned long long* mask = cv.take<unsigned long long>((size_t)n * nb);
     unsigned long long* removed = cv.take<unsigned long long>((size_t)nb + 1);
     unsigned long long* diag_pred = cv.take<unsigned long long>((size_t)n);
@@ -322,8 +321,7 @@ int wd_nms_segmented_f32(const float* boxes, const int32_t* idxs, const int32_t*
         return WT_ERR_CAPACITY;
     }
     const int nbm = (max_n + 63) / 64;
-    const uintptr_t mis = (uintptr_t)workspace & 255;
-    wt::Carver cv((char*)workspace + (mis ? 256 - mis : 0));
+    wt::Carver cv(wt::align_ptr(workspace));
     unsigned long long* mask = cv.take<unsigned long long>((size_t)n * ((n + 63) / 64));
     (void)cv.take<unsigned long long>((size_t)((n + 63) / 64) + 1);
     unsigned long long* diag_pred = cv.take<unsigned long long>((size_t)n);

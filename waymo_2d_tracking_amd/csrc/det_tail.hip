@@ -282,8 +282,7 @@ int wd_rpn_topk_decode_f32(const float* const* logits, const float* const* delta
     size_t half = 0;
     for (int l = 0; l < n_levels; ++l) half += (((size_t)n_per_level[l] + kChunk - 1) / kChunk) * (size_t)k;
     half = wt::align_up(half * 8);
-    const uintptr_t mis = (uintptr_t)workspace & 255;
-    char* base = (char*)workspace + (mis ? 256 - mis : 0);
+    char* base = wt::align_ptr(workspace);
     unsigned long long* buf[2] = {(unsigned long long*)base, (unsigned long long*)(base + half)};
     int cur_n[kMaxLevels];
     long long cur_off[kMaxLevels];

@@ -487,8 +487,6 @@ constexpr size_t kSlotsLdsBudget = kLdsBudget - 1024;      // room for the kerne
 // round(np.float64(s), 5) = numpy around: multiply, rint (half to even), divide (not CPython's correctly rounded round)
 __device__ __forceinline__ double round5_numpy(double s) { return rint(s * 1e5) / 1e5; }
 
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct SlotsWs {
     double* rows;      // per group K*S rows of 5: gathered input, later the group's final wire rows [x, y, w, h, score]
     double* merged;    // per group K*S rows of 5: merge output [score, x, y, w, h]
@@ -504,11 +502,11 @@ __host__ __device__ inline size_t slots_group_mem(int method, size_t ks) {
 __host__ inline SlotsWs slots_ws_layout(char* base, int64_t n_groups, size_t ks, int method, bool lds, size_t* total) {
     SlotsWs w;
     size_t off = 0;
-    const size_t rows_b = align256((size_t)n_groups * ks * 5 * sizeof(double));
+    const size_t rows_b = wt::align_up((size_t)n_groups * ks * 5 * sizeof(double));
     w.rows = reinterpret_cast<double*>(base + off); off += rows_b;
     w.merged = reinterpret_cast<double*>(base + off); off += rows_b;
-    w.count = reinterpret_cast<int32_t*>(base + off); off += align256((size_t)n_groups * sizeof(int32_t));
-    w.scratch_stride = lds ? 0 : align256(slots_group_mem(method, ks));
+    w.count = reinterpret_cast<int32_t*>(base + off); off += wt::align_up((size_t)n_groups * sizeof(int32_t));
+    w.scratch_stride = lds ? 0 : wt::align_up(slots_group_mem(method, ks));
     w.scratch = base + off; off += (size_t)n_groups * w.scratch_stride;
     *total = off;
     return w;

@@ -6,23 +6,17 @@
 // that still clear the threshold, assign the rest with the Munkres of sort_device.h on the gated float32 IoU matrix
 // (LDS when it fits, workspace otherwise), then count for both difficulty levels.  The IoU sum is accumulated one
 // match after the other in ground-truth row order, so that it is the same float64 number on every run and on the CPU.
-// Compile with -ffp-contract=off (IoU in the operation order of tracking/sort/sort.py:34-47).
-#include "common.h"
-#include "sort_device.h"
-#include <algorithm>
-#include <utility>
-#include <vector>
+// Compile with -ffp-contract=off (IoU in the operation order of tracking/sort/sort.py:34-47; eval_device.h has it).
+#include "eval_device.h"
+#include "eval_host.h"
 
 using namespace wtdev;
 
 namespace {
 
 constexpr int kMaxBoxes = 4096;               // per side and (frame, class): the limit of munkres_wave
-constexpr int kMaxClasses = 16;               // thresholds travel as a kernel argument
 constexpr int kLdsCostFloats = 8192;          // 32 KiB of cost matrix in LDS per wave
 constexpr size_t kLdsZmaskMax = 32 * 1024;    // zero bitmaps stay in LDS up to here (about 500 x 500), in the workspace beyond
-
-struct Thresholds { double v[kMaxClasses]; };
 
 struct Caps {
     int capN;                // boxes per side of one (frame, class)
@@ -78,32 +72,6 @@ Workspace carve(void* base, size_t n_problems, const Caps& c) {
     return w;
 }
 
-// sort.py:34-47 on two float64 boxes [x1, y1, x2, y2]
-__device__ __forceinline__ double iou_dd(const double a[4], const double b[4]) {
-    const double xx1 = (a[0] > b[0]) ? a[0] : b[0];
-    const double yy1 = (a[1] > b[1]) ? a[1] : b[1];
-    const double xx2 = (a[2] < b[2]) ? a[2] : b[2];
-    const double yy2 = (a[3] < b[3]) ? a[3] : b[3];
-    double w = xx2 - xx1; if (!(w > 0.)) w = 0.;
-    double h = yy2 - yy1; if (!(h > 0.)) h = 0.;
-    const double wh = w * h;
-    const double area_a = (a[2] - a[0]) * (a[3] - a[1]);
-    const double area_b = (b[2] - b[0]) * (b[3] - b[1]);
-    return wh / ((area_a + area_b) - wh);
-}
-
-struct Boxes {
-    const double *x, *y, *w, *h;
-    __device__ __forceinline__ void get(long long r, double o[4]) const {
-        const double xx = x[r], yy = y[r];
-        o[0] = xx; o[1] = yy; o[2] = xx + w[r]; o[3] = yy + h[r];
-    }
-};
-
-__device__ __forceinline__ double bcast_d(double v, int l) {
-    return __longlong_as_double((long long)readlane64((unsigned long long)__double_as_longlong(v), l));
-}
-
 __global__ __launch_bounds__(kWave) void mot_eval_kernel(
     Boxes G, const int32_t* __restrict__ g_cat, const int32_t* __restrict__ g_level, const int32_t* __restrict__ g_id,
     const int64_t* __restrict__ frame_gt_offsets, const int64_t* __restrict__ stream_frame_offsets, long long n_frames,
@@ -113,11 +81,9 @@ __global__ __launch_bounds__(kWave) void mot_eval_kernel(
     int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
-    const unsigned long long lt = lanemask_lt();
     const size_t p = blockIdx.x;
-    const int k = (int)(p / ((size_t)n_streams * C));
-    const int s = (int)((p / C) % n_streams);
-    const int c = (int)(p % C) + 1;
+    int k, s, c;
+    decode_problem(p, n_streams, C, &k, &s, &c);
     const int capN = caps.capN;
     const double thr = thr_all.v[c - 1];
 
@@ -156,21 +122,8 @@ __global__ __launch_bounds__(kWave) void mot_eval_kernel(
         const long long g0 = frame_gt_offsets[f], g1 = frame_gt_offsets[f + 1];
         const long long h0 = hbase + fho[f], h1 = hbase + fho[f + 1];
         // ---- this class's rows of the frame, in file order ----
-        int ng = 0, nh = 0;
-        for (long long base = g0; base < g1; base += kWave) {
-            const long long d = base + lane;
-            const bool mine = (d < g1) && g_cat[d] == c;
-            const unsigned long long mm = __ballot(mine);
-            if (mine) { const int q = ng + __popcll(mm & lt); if (q < capN) gidx[q] = (int)(d - g0); }
-            ng += __popcll(mm);
-        }
-        for (long long base = h0; base < h1; base += kWave) {
-            const long long d = base + lane;
-            const bool mine = (d < h1) && h_cat[d] == c;
-            const unsigned long long mm = __ballot(mine);
-            if (mine) { const int q = nh + __popcll(mm & lt); if (q < capN) hidx[q] = (int)(d - h0); }
-            nh += __popcll(mm);
-        }
+        const int ng = compact_rows(g_cat, g0, g1, c, gidx, capN);
+        const int nh = compact_rows(h_cat, h0, h1, c, hidx, capN);
         if (ng > capN || nh > capN) { err = kErrCapacity; break; }
         if (ng == 0 && nh == 0) continue;
         for (int i = lane; i < ng; i += kWave) gmatch[i] = -1;
@@ -203,21 +156,8 @@ __global__ __launch_bounds__(kWave) void mot_eval_kernel(
             wsync();
         }
         // ---- 2. the rest: Munkres on the gated IoU matrix ----
-        int nr = 0, nc = 0;
-        for (int base = 0; base < ng; base += kWave) {
-            const int i = base + lane;
-            const bool open = (i < ng) && gmatch[i] < 0;
-            const unsigned long long mm = __ballot(open);
-            if (open) rlist[nr + __popcll(mm & lt)] = i;
-            nr += __popcll(mm);
-        }
-        for (int base = 0; base < nh; base += kWave) {
-            const int j = base + lane;
-            const bool open = (j < nh) && hmatch[j] < 0;
-            const unsigned long long mm = __ballot(open);
-            if (open) clist[nc + __popcll(mm & lt)] = j;
-            nc += __popcll(mm);
-        }
+        const int nr = compact_wave(0, ng, [=](int i) { return gmatch[i] < 0; }, rlist, capN);
+        const int nc = compact_wave(0, nh, [=](int j) { return hmatch[j] < 0; }, clist, capN);
         wsync();
         if (nr > 0 && nc > 0) {
             const bool transposed = nc < nr;               // linear_assignment transposes when there are fewer columns than rows
@@ -324,9 +264,38 @@ __global__ void mot_fill_kernel(long long n, int64_t* __restrict__ hyp_match, ui
     if (hyp_switch) hyp_switch[i] = 0;
 }
 
-inline char* align256(void* p) {
-    const uintptr_t mis = (uintptr_t)p & 255;
-    return (char*)p + (mis ? 256 - mis : 0);
+// wt_mot_eval_dev on an input whose pointers are device pointers
+int launch(const wt::TrackInput& in, int64_t n_hyp, const double* thr, int64_t max_frame_boxes, int32_t max_gt_ids,
+           int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch, int32_t* status_dev,
+           void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    WT_TRY(wt::ensure_device());
+    if (in.k_sets < 1 || in.n_streams < 0 || in.n_frames < 0 || in.n_gt < 0 || n_hyp < 0 || !thr || !counts || !iou_sum || !status_dev) {
+        wt::set_error("wt_mot_eval: bad argument");
+        return WT_ERR_INVALID;
+    }
+    if (in.n_classes < 1 || in.n_classes > kMaxClasses) { wt::set_error("wt_mot_eval: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
+    Caps caps;
+    WT_TRY(pick_caps(max_frame_boxes, max_gt_ids, &caps));
+    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
+    if (n_hyp > 0 && (hyp_match || hyp_switch))
+        hipLaunchKernelGGL(mot_fill_kernel, dim3((unsigned)((n_hyp + 255) / 256)), dim3(256), 0, stream, (long long)n_hyp, hyp_match, hyp_switch);
+    const size_t n_problems = (size_t)in.k_sets * (size_t)in.n_streams * (size_t)in.n_classes;
+    if (n_problems == 0) { WT_HIP(hipGetLastError()); return WT_OK; }
+    if (n_problems > 0x7fffffffull) { wt::set_error("wt_mot_eval: %zu problems in one call", n_problems); return WT_ERR_CAPACITY; }
+    Workspace ws = carve(wt::align_ptr(workspace), n_problems, caps);
+    if (!workspace || workspace_bytes < ws.bytes + 256) {
+        wt::set_error("evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
+        return WT_ERR_CAPACITY;
+    }
+    if (caps.lds_bytes > 48 * 1024)
+        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mot_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)caps.lds_bytes));
+    const Boxes G = {in.gx, in.gy, in.gw, in.gh}, H = {in.hx, in.hy, in.hw, in.hh};
+    hipLaunchKernelGGL(mot_eval_kernel, dim3((unsigned)n_problems), dim3(kWave), caps.lds_bytes, stream, G, in.g_category, in.g_level, in.g_id,
+                       in.frame_gt_offsets, in.stream_frame_offsets, (long long)in.n_frames, (int)in.n_streams, (int)in.n_classes,
+                       in.set_row_offsets, in.frame_hyp_offsets, H, in.h_category, in.h_id, make_thresholds(thr, in.n_classes), caps, ws,
+                       counts, iou_sum, hyp_match, hyp_switch, (int*)status_dev);
+    WT_HIP(hipGetLastError());
+    return WT_OK;
 }
 
 }  // namespace
@@ -348,36 +317,10 @@ int wt_mot_eval_dev(int64_t n_gt, const double* gx, const double* gy, const doub
                     int32_t n_classes, const double* thr, int64_t max_frame_boxes, int32_t max_gt_ids,
                     int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch, int32_t* status_dev,
                     void* workspace, size_t workspace_bytes, void* stream_) {
-    WT_TRY(wt::ensure_device());
-    hipStream_t stream = (hipStream_t)stream_;
-    if (k_sets < 1 || n_streams < 0 || n_frames < 0 || n_gt < 0 || n_hyp < 0 || !thr || !counts || !iou_sum || !status_dev) {
-        wt::set_error("wt_mot_eval: bad argument");
-        return WT_ERR_INVALID;
-    }
-    if (n_classes < 1 || n_classes > kMaxClasses) { wt::set_error("wt_mot_eval: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
-    Caps caps;
-    WT_TRY(pick_caps(max_frame_boxes, max_gt_ids, &caps));
-    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
-    if (n_hyp > 0 && (hyp_match || hyp_switch))
-        hipLaunchKernelGGL(mot_fill_kernel, dim3((unsigned)((n_hyp + 255) / 256)), dim3(256), 0, stream, (long long)n_hyp, hyp_match, hyp_switch);
-    const size_t n_problems = (size_t)k_sets * (size_t)n_streams * (size_t)n_classes;
-    if (n_problems == 0) { WT_HIP(hipGetLastError()); return WT_OK; }
-    if (n_problems > 0x7fffffffull) { wt::set_error("wt_mot_eval: %zu problems in one call", n_problems); return WT_ERR_CAPACITY; }
-    Workspace ws = carve(align256(workspace), n_problems, caps);
-    if (!workspace || workspace_bytes < ws.bytes + 256) {
-        wt::set_error("evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
-        return WT_ERR_CAPACITY;
-    }
-    Thresholds t;
-    for (int i = 0; i < kMaxClasses; ++i) t.v[i] = i < n_classes ? thr[i] : 2.0;
-    if (caps.lds_bytes > 48 * 1024)
-        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mot_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)caps.lds_bytes));
-    const Boxes G = {gx, gy, gw, gh}, H = {hx, hy, hw, hh};
-    hipLaunchKernelGGL(mot_eval_kernel, dim3((unsigned)n_problems), dim3(kWave), caps.lds_bytes, stream, G, g_category, g_level, g_id,
-                       frame_gt_offsets, stream_frame_offsets, (long long)n_frames, (int)n_streams, (int)n_classes, set_row_offsets,
-                       frame_hyp_offsets, H, h_category, h_id, t, caps, ws, counts, iou_sum, hyp_match, hyp_switch, (int*)status_dev);
-    WT_HIP(hipGetLastError());
-    return WT_OK;
+    const wt::TrackInput in = {n_gt, gx, gy, gw, gh, g_category, g_level, g_id, n_frames, frame_gt_offsets, n_streams, stream_frame_offsets,
+                               k_sets, set_row_offsets, frame_hyp_offsets, hx, hy, hw, hh, h_category, h_id, n_classes};
+    return launch(in, n_hyp, thr, max_frame_boxes, max_gt_ids, counts, iou_sum, hyp_match, hyp_switch, status_dev, workspace, workspace_bytes,
+                  (hipStream_t)stream_);
 }
 
 int wt_mot_eval_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
@@ -388,108 +331,55 @@ int wt_mot_eval_host(int64_t n_gt, const double* gx, const double* gy, const dou
                      const int32_t* h_category, const int32_t* h_id,
                      int32_t n_classes, const double* thr,
                      int64_t* counts, double* iou_sum, int64_t* hyp_match, uint8_t* hyp_switch) {
-    if (k_sets < 1 || n_streams < 0 || n_frames < 0 || n_gt < 0 || !set_row_offsets || !frame_hyp_offsets || !frame_gt_offsets ||
-        !stream_frame_offsets || !thr || !counts || !iou_sum) {
-        wt::set_error("wt_mot_eval_host: bad argument");
-        return WT_ERR_INVALID;
-    }
-    if (n_classes < 1 || n_classes > kMaxClasses) { wt::set_error("wt_mot_eval: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
-    const int64_t n_hyp = set_row_offsets[k_sets];
-    // ---- the layout must be what the kernel walks: checked here, the device form trusts its caller ----
-    if (frame_gt_offsets[0] != 0 || frame_gt_offsets[n_frames] != n_gt || stream_frame_offsets[0] != 0 ||
-        stream_frame_offsets[n_streams] != n_frames || set_row_offsets[0] != 0) {
-        wt::set_error("wt_mot_eval_host: CSR offsets do not cover the rows");
-        return WT_ERR_INVALID;
-    }
-    for (int32_t s = 0; s < n_streams; ++s)
-        if (stream_frame_offsets[s + 1] < stream_frame_offsets[s]) { wt::set_error("stream_frame_offsets must be non-decreasing"); return WT_ERR_INVALID; }
+    const wt::TrackInput in = {n_gt, gx, gy, gw, gh, g_category, g_level, g_id, n_frames, frame_gt_offsets, n_streams, stream_frame_offsets,
+                               k_sets, set_row_offsets, frame_hyp_offsets, hx, hy, hw, hh, h_category, h_id, n_classes};
+    WT_TRY(wt::check_track_layout(in, "wt_mot_eval_host", thr && counts && iou_sum, kMaxClasses));
+    // an id is valid when it is not negative; on the way, the most boxes of one class in one frame and the largest ground-truth id
     std::vector<int64_t> per_class((size_t)n_classes);
     int64_t max_boxes = 0;
     int32_t max_id = -1;
-    std::vector<std::pair<int32_t, int32_t>> seen;
-    auto scan_frame = [&](const int32_t* cat, const int32_t* id, int64_t r0, int64_t r1, bool* dup) {
+    auto ids_unique = [&](const int32_t* cat, const int32_t* id, int64_t r0, int64_t r1) {
         std::fill(per_class.begin(), per_class.end(), 0);
-        seen.clear();
-        for (int64_t r = r0; r < r1; ++r) {
-            if (cat[r] < 1 || cat[r] > n_classes) continue;
-            if (id[r] < 0) { *dup = true; return; }
-            const int64_t v = ++per_class[(size_t)cat[r] - 1];
-            if (v > max_boxes) max_boxes = v;
-            seen.emplace_back(cat[r], id[r]);
-        }
-        std::sort(seen.begin(), seen.end());
-        *dup = std::adjacent_find(seen.begin(), seen.end()) != seen.end();
+        return wt::frame_ids_unique(cat, id, r0, r1, n_classes, [&](int64_t r) {
+            if (id[r] < 0) return false;
+            max_boxes = std::max(max_boxes, ++per_class[(size_t)cat[r] - 1]);
+            return true;
+        });
     };
-    for (int64_t f = 0; f < n_frames; ++f) {
-        const int64_t r0 = frame_gt_offsets[f], r1 = frame_gt_offsets[f + 1];
-        if (r1 < r0) { wt::set_error("frame_gt_offsets must be non-decreasing"); return WT_ERR_INVALID; }
-        for (int64_t r = r0; r < r1; ++r) {
-            if (g_id[r] < 0) { wt::set_error("ground-truth row %lld: negative object id", (long long)r); return WT_ERR_INVALID; }
-            if (g_id[r] > max_id) max_id = g_id[r];
-        }
-        bool dup = false;
-        scan_frame(g_category, g_id, r0, r1, &dup);
-        if (dup) { wt::set_error("ground truth: an object id occurs twice in frame %lld", (long long)f); return WT_ERR_INVALID; }
-    }
-    for (int32_t k = 0; k < k_sets; ++k) {
-        const int64_t* fho = frame_hyp_offsets + (size_t)k * (size_t)(n_frames + 1);
-        const int64_t rows = set_row_offsets[k + 1] - set_row_offsets[k];
-        if (rows < 0 || fho[0] != 0 || fho[n_frames] > rows) { wt::set_error("result set %d: frame_hyp_offsets do not fit its rows", (int)k); return WT_ERR_INVALID; }
-        for (int64_t f = 0; f < n_frames; ++f) {
-            if (fho[f + 1] < fho[f]) { wt::set_error("result set %d: frame_hyp_offsets must be non-decreasing", (int)k); return WT_ERR_INVALID; }
-            bool dup = false;
-            scan_frame(h_category, h_id, set_row_offsets[k] + fho[f], set_row_offsets[k] + fho[f + 1], &dup);
-            if (dup) { wt::set_error("result set %d: an object id is negative or occurs twice in frame %lld", (int)k, (long long)f); return WT_ERR_INVALID; }
-        }
-    }
+    WT_TRY(wt::walk_track_frames(in,
+        [&](int32_t, int64_t f, int64_t r0, int64_t r1) {
+            for (int64_t r = r0; r < r1; ++r) {              // every row, whatever its class: the kernel indexes by the id
+                if (g_id[r] < 0) { wt::set_error("ground-truth row %lld: negative object id", (long long)r); return WT_ERR_INVALID; }
+                if (g_id[r] > max_id) max_id = g_id[r];
+            }
+            if (ids_unique(g_category, g_id, r0, r1)) return WT_OK;
+            wt::set_error("ground truth: an object id occurs twice in frame %lld", (long long)f);
+            return WT_ERR_INVALID;
+        },
+        [&](int32_t k, int32_t, int64_t f, int64_t r0, int64_t r1) {
+            if (ids_unique(h_category, h_id, r0, r1)) return WT_OK;
+            wt::set_error("result set %d: an object id is negative or occurs twice in frame %lld", (int)k, (long long)f);
+            return WT_ERR_INVALID;
+        }));
     if (max_boxes > kMaxBoxes) {
         wt::set_error("%lld boxes of one class in one frame: the assignment kernel takes at most %d a side", (long long)max_boxes, kMaxBoxes);
         return WT_ERR_CAPACITY;
     }
     WT_TRY(wt::ensure_device());
-    const size_t ng = (size_t)n_gt, nh = (size_t)n_hyp;
-    const size_t n_problems = (size_t)k_sets * (size_t)n_streams * (size_t)n_classes;
-    wt::DevBuf dgx, dgy, dgw, dgh, dgc, dgl, dgi, dfo, dso, dsr, dfh, dhx, dhy, dhw, dhh, dhc, dhi, dcnt, dsum, dmatch, dswitch, dstat, dws;
-    WT_TRY(dgx.alloc(8 * ng)); WT_TRY(dgy.alloc(8 * ng)); WT_TRY(dgw.alloc(8 * ng)); WT_TRY(dgh.alloc(8 * ng));
-    WT_TRY(dgc.alloc(4 * ng)); WT_TRY(dgl.alloc(4 * ng)); WT_TRY(dgi.alloc(4 * ng));
-    WT_TRY(dfo.alloc(8 * (size_t)(n_frames + 1))); WT_TRY(dso.alloc(8 * (size_t)(n_streams + 1)));
-    WT_TRY(dsr.alloc(8 * (size_t)(k_sets + 1))); WT_TRY(dfh.alloc(8 * (size_t)k_sets * (size_t)(n_frames + 1)));
-    WT_TRY(dhx.alloc(8 * nh)); WT_TRY(dhy.alloc(8 * nh)); WT_TRY(dhw.alloc(8 * nh)); WT_TRY(dhh.alloc(8 * nh));
-    WT_TRY(dhc.alloc(4 * nh)); WT_TRY(dhi.alloc(4 * nh));
-    WT_TRY(dcnt.alloc(8 * n_problems * 10)); WT_TRY(dsum.alloc(8 * n_problems * 2)); WT_TRY(dstat.alloc(16));
+    wt::StagedTrackInput staged;
+    WT_TRY(staged.upload(in));
+    const size_t nh = (size_t)staged.n_hyp, n_problems = (size_t)k_sets * (size_t)n_streams * (size_t)n_classes;
+    wt::DevBuf dcnt, dsum, dmatch, dswitch, dws;
+    WT_TRY(dcnt.alloc(8 * n_problems * 10)); WT_TRY(dsum.alloc(8 * n_problems * 2));
     if (hyp_match) WT_TRY(dmatch.alloc(8 * nh));
     if (hyp_switch) WT_TRY(dswitch.alloc(nh));
-    if (ng) {
-        WT_HIP(hipMemcpy(dgx.p, gx, 8 * ng, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dgy.p, gy, 8 * ng, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dgw.p, gw, 8 * ng, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dgh.p, gh, 8 * ng, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dgc.p, g_category, 4 * ng, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dgl.p, g_level, 4 * ng, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dgi.p, g_id, 4 * ng, hipMemcpyHostToDevice));
-    }
-    if (nh) {
-        WT_HIP(hipMemcpy(dhx.p, hx, 8 * nh, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dhy.p, hy, 8 * nh, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dhw.p, hw, 8 * nh, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dhh.p, hh, 8 * nh, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dhc.p, h_category, 4 * nh, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dhi.p, h_id, 4 * nh, hipMemcpyHostToDevice));
-    }
-    WT_HIP(hipMemcpy(dfo.p, frame_gt_offsets, 8 * (size_t)(n_frames + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dso.p, stream_frame_offsets, 8 * (size_t)(n_streams + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dsr.p, set_row_offsets, 8 * (size_t)(k_sets + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dfh.p, frame_hyp_offsets, 8 * (size_t)k_sets * (size_t)(n_frames + 1), hipMemcpyHostToDevice));
     const size_t wsb = wt_mot_eval_workspace(k_sets, n_streams, n_classes, max_boxes, max_id + 1);
     if (!wsb) return WT_ERR_CAPACITY;
     WT_TRY(dws.alloc(wsb));
-    WT_TRY(wt_mot_eval_dev(n_gt, dgx.as<double>(), dgy.as<double>(), dgw.as<double>(), dgh.as<double>(), dgc.as<int32_t>(),
-                           dgl.as<int32_t>(), dgi.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams, dso.as<int64_t>(), k_sets, n_hyp,
-                           dsr.as<int64_t>(), dfh.as<int64_t>(), dhx.as<double>(), dhy.as<double>(), dhw.as<double>(), dhh.as<double>(),
-                           dhc.as<int32_t>(), dhi.as<int32_t>(), n_classes, thr, max_boxes, max_id + 1, dcnt.as<int64_t>(),
-                           dsum.as<double>(), hyp_match ? dmatch.as<int64_t>() : nullptr, hyp_switch ? dswitch.as<uint8_t>() : nullptr,
-                           dstat.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_HIP(hipDeviceSynchronize());
-    int32_t st = 0;
-    WT_HIP(hipMemcpy(&st, dstat.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (st) {
-        wt::set_error("evaluation kernel reported status %d (4 = capacity, 5 = assignment did not converge)", (int)st);
-        return (int)st;
-    }
+    WT_TRY(launch(staged.dev, staged.n_hyp, thr, max_boxes, max_id + 1, dcnt.as<int64_t>(), dsum.as<double>(),
+                  hyp_match ? dmatch.as<int64_t>() : nullptr, hyp_switch ? dswitch.as<uint8_t>() : nullptr, staged.status.as<int32_t>(),
+                  dws.p, wsb, nullptr));
+    WT_TRY(staged.finish("evaluation"));
     if (n_problems) {
         WT_HIP(hipMemcpy(counts, dcnt.p, 8 * n_problems * 10, hipMemcpyDeviceToHost));
         WT_HIP(hipMemcpy(iou_sum, dsum.p, 8 * n_problems * 2, hipMemcpyDeviceToHost));

@@ -10,23 +10,17 @@
 //   assignment   munkres_wave of sort_device.h in place on each level's matrix (-n: small integers, exact in float32).
 //   re-walk      the solve destroys the matrix, so the frames are walked once more: a pair with IoU >= thr whose
 //                trajectories are assigned to each other is an identity true positive.
-// Compile with -ffp-contract=off (IoU in the operation order of tracking/sort/sort.py:34-47).
-#include "common.h"
-#include "sort_device.h"
-#include <algorithm>
-#include <utility>
-#include <vector>
+// Compile with -ffp-contract=off (IoU in the operation order of tracking/sort/sort.py:34-47; eval_device.h has it).
+#include "eval_device.h"
+#include "eval_host.h"
 
 using namespace wtdev;
 
 namespace {
 
 constexpr int kMaxTraj = 4096;                // trajectories per side of one problem: the limit of munkres_wave
-constexpr int kMaxClasses = 16;               // thresholds travel as a kernel argument
 constexpr size_t kLdsStarsMax = 8 * 1024;     // star / prime arrays stay in LDS up to here (2 n + m <= 2048), in the workspace beyond
 constexpr size_t kLdsZmaskMax = 32 * 1024;    // zero bitmaps stay in LDS up to here (about 500 x 500), in the workspace beyond
-
-struct Thresholds { double v[kMaxClasses]; };
 
 struct Caps {
     int capG, capH;          // trajectories (= boxes of one frame at most) per side of one problem
@@ -76,43 +70,6 @@ Workspace carve(void* base, size_t n_problems, const Caps& c, size_t matrix_floa
     return w;
 }
 
-// sort.py:34-47 on two float64 boxes [x1, y1, x2, y2]
-__device__ __forceinline__ double iou_dd(const double a[4], const double b[4]) {
-    const double xx1 = (a[0] > b[0]) ? a[0] : b[0];
-    const double yy1 = (a[1] > b[1]) ? a[1] : b[1];
-    const double xx2 = (a[2] < b[2]) ? a[2] : b[2];
-    const double yy2 = (a[3] < b[3]) ? a[3] : b[3];
-    double w = xx2 - xx1; if (!(w > 0.)) w = 0.;
-    double h = yy2 - yy1; if (!(h > 0.)) h = 0.;
-    const double wh = w * h;
-    const double area_a = (a[2] - a[0]) * (a[3] - a[1]);
-    const double area_b = (b[2] - b[0]) * (b[3] - b[1]);
-    return wh / ((area_a + area_b) - wh);
-}
-
-struct Boxes {
-    const double *x, *y, *w, *h;
-    __device__ __forceinline__ void get(long long r, double o[4]) const {
-        const double xx = x[r], yy = y[r];
-        o[0] = xx; o[1] = yy; o[2] = xx + w[r]; o[3] = yy + h[r];
-    }
-};
-
-// rows of class c in [r0, r1), in file order, as offsets from r0; returns how many (more than cap: nothing beyond cap is written)
-__device__ __forceinline__ int compact_rows(const int32_t* __restrict__ cat, long long r0, long long r1, int c, int* idx, int cap) {
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lt = lanemask_lt();
-    int n = 0;
-    for (long long base = r0; base < r1; base += kWave) {
-        const long long d = base + lane;
-        const bool mine = (d < r1) && cat[d] == c;
-        const unsigned long long mm = __ballot(mine);
-        if (mine) { const int q = n + __popcll(mm & lt); if (q < cap) idx[q] = (int)(d - r0); }
-        n += __popcll(mm);
-    }
-    return n;
-}
-
 __global__ __launch_bounds__(kWave) void mot_identity_kernel(
     Boxes G, const int32_t* __restrict__ g_cat, const int32_t* __restrict__ g_level, const int32_t* __restrict__ g_traj,
     const int64_t* __restrict__ frame_gt_offsets, const int64_t* __restrict__ stream_frame_offsets, long long n_frames,
@@ -124,9 +81,8 @@ __global__ __launch_bounds__(kWave) void mot_identity_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const size_t p = blockIdx.x;
-    const int s = (int)((p / C) % n_streams);
-    const int k = (int)(p / ((size_t)n_streams * C));
-    const int c = (int)(p % C) + 1;
+    int k, s, c;
+    decode_problem(p, n_streams, C, &k, &s, &c);
     const double thr = thr_all.v[c - 1];
     const int nG = g_ntraj[(size_t)s * C + (c - 1)], nH = h_ntraj[p];
     const bool transposed = nH < nG;                       // the smaller side is the rows
@@ -297,9 +253,40 @@ __global__ void identity_fill_kernel(long long n, int64_t* __restrict__ hyp_idma
     if (i < n) hyp_idmatch[i] = -2;
 }
 
-inline char* align256(void* p) {
-    const uintptr_t mis = (uintptr_t)p & 255;
-    return (char*)p + (mis ? 256 - mis : 0);
+// wt_mot_identity_dev on an input whose pointers are device pointers
+int launch(const wt::TrackInput& in, int64_t n_hyp, const int32_t* g_ntraj, const int32_t* h_ntraj, const int64_t* mat_offsets,
+           int64_t matrix_floats, const double* thr, int64_t max_gt_traj, int64_t max_hyp_traj, int64_t* id_counts, int64_t* hyp_idmatch,
+           int32_t* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    WT_TRY(wt::ensure_device());
+    if (in.k_sets < 1 || in.n_streams < 0 || in.n_frames < 0 || in.n_gt < 0 || n_hyp < 0 || matrix_floats < 0 || !thr || !id_counts || !status_dev ||
+        !g_ntraj || !h_ntraj || !mat_offsets) {
+        wt::set_error("wt_mot_identity: bad argument");
+        return WT_ERR_INVALID;
+    }
+    if (in.n_classes < 1 || in.n_classes > kMaxClasses) { wt::set_error("wt_mot_identity: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
+    Caps caps;
+    WT_TRY(pick_caps(max_gt_traj, max_hyp_traj, &caps));
+    const size_t n_problems = (size_t)in.k_sets * (size_t)in.n_streams * (size_t)in.n_classes;
+    if (n_problems > 0x7fffffffull) { wt::set_error("wt_mot_identity: %zu problems in one call", n_problems); return WT_ERR_CAPACITY; }
+    Workspace ws = carve(wt::align_ptr(workspace), n_problems, caps, (size_t)matrix_floats);
+    if (n_problems && (!workspace || workspace_bytes < ws.bytes + 256)) {
+        wt::set_error("identity evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
+        return WT_ERR_INVALID;
+    }
+    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
+    if (n_hyp > 0 && hyp_idmatch)
+        hipLaunchKernelGGL(identity_fill_kernel, dim3((unsigned)((2 * n_hyp + 255) / 256)), dim3(256), 0, stream, (long long)(2 * n_hyp), hyp_idmatch);
+    if (n_problems == 0) { WT_HIP(hipGetLastError()); return WT_OK; }
+    WT_HIP(hipMemsetAsync(id_counts, 0, n_problems * 6 * sizeof(int64_t), stream));
+    if (caps.lds_bytes > 48 * 1024)
+        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mot_identity_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)caps.lds_bytes));
+    const Boxes G = {in.gx, in.gy, in.gw, in.gh}, H = {in.hx, in.hy, in.hw, in.hh};
+    hipLaunchKernelGGL(mot_identity_kernel, dim3((unsigned)n_problems), dim3(kWave), caps.lds_bytes, stream, G, in.g_category, in.g_level, in.g_id,
+                       in.frame_gt_offsets, in.stream_frame_offsets, (long long)in.n_frames, (int)in.n_streams, (int)in.n_classes,
+                       in.set_row_offsets, in.frame_hyp_offsets, H, in.h_category, in.h_id, g_ntraj, h_ntraj, mat_offsets, (long long)matrix_floats,
+                       make_thresholds(thr, in.n_classes), caps, ws, id_counts, hyp_idmatch, (int*)status_dev);
+    WT_HIP(hipGetLastError());
+    return WT_OK;
 }
 
 }  // namespace
@@ -329,39 +316,10 @@ int wt_mot_identity_dev(int64_t n_gt, const double* gx, const double* gy, const 
                         int32_t n_classes, const double* thr, int64_t max_gt_traj, int64_t max_hyp_traj,
                         int64_t* id_counts, int64_t* hyp_idmatch, int32_t* status_dev,
                         void* workspace, size_t workspace_bytes, void* stream_) {
-    WT_TRY(wt::ensure_device());
-    hipStream_t stream = (hipStream_t)stream_;
-    if (k_sets < 1 || n_streams < 0 || n_frames < 0 || n_gt < 0 || n_hyp < 0 || matrix_floats < 0 || !thr || !id_counts || !status_dev ||
-        !g_ntraj || !h_ntraj || !mat_offsets) {
-        wt::set_error("wt_mot_identity: bad argument");
-        return WT_ERR_INVALID;
-    }
-    if (n_classes < 1 || n_classes > kMaxClasses) { wt::set_error("wt_mot_identity: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
-    Caps caps;
-    WT_TRY(pick_caps(max_gt_traj, max_hyp_traj, &caps));
-    const size_t n_problems = (size_t)k_sets * (size_t)n_streams * (size_t)n_classes;
-    if (n_problems > 0x7fffffffull) { wt::set_error("wt_mot_identity: %zu problems in one call", n_problems); return WT_ERR_CAPACITY; }
-    Workspace ws = carve(align256(workspace), n_problems, caps, (size_t)matrix_floats);
-    if (n_problems && (!workspace || workspace_bytes < ws.bytes + 256)) {
-        wt::set_error("identity evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
-        return WT_ERR_INVALID;
-    }
-    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
-    if (n_hyp > 0 && hyp_idmatch)
-        hipLaunchKernelGGL(identity_fill_kernel, dim3((unsigned)((2 * n_hyp + 255) / 256)), dim3(256), 0, stream, (long long)(2 * n_hyp), hyp_idmatch);
-    if (n_problems == 0) { WT_HIP(hipGetLastError()); return WT_OK; }
-    WT_HIP(hipMemsetAsync(id_counts, 0, n_problems * 6 * sizeof(int64_t), stream));
-    Thresholds t;
-    for (int i = 0; i < kMaxClasses; ++i) t.v[i] = i < n_classes ? thr[i] : 2.0;
-    if (caps.lds_bytes > 48 * 1024)
-        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mot_identity_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)caps.lds_bytes));
-    const Boxes G = {gx, gy, gw, gh}, H = {hx, hy, hw, hh};
-    hipLaunchKernelGGL(mot_identity_kernel, dim3((unsigned)n_problems), dim3(kWave), caps.lds_bytes, stream, G, g_category, g_level, g_traj,
-                       frame_gt_offsets, stream_frame_offsets, (long long)n_frames, (int)n_streams, (int)n_classes, set_row_offsets,
-                       frame_hyp_offsets, H, h_category, h_traj, g_ntraj, h_ntraj, mat_offsets, (long long)matrix_floats, t, caps, ws,
-                       id_counts, hyp_idmatch, (int*)status_dev);
-    WT_HIP(hipGetLastError());
-    return WT_OK;
+    const wt::TrackInput in = {n_gt, gx, gy, gw, gh, g_category, g_level, g_traj, n_frames, frame_gt_offsets, n_streams, stream_frame_offsets,
+                               k_sets, set_row_offsets, frame_hyp_offsets, hx, hy, hw, hh, h_category, h_traj, n_classes};
+    return launch(in, n_hyp, g_ntraj, h_ntraj, mat_offsets, matrix_floats, thr, max_gt_traj, max_hyp_traj, id_counts, hyp_idmatch, status_dev,
+                  workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 int wt_mot_identity_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
@@ -373,21 +331,9 @@ int wt_mot_identity_host(int64_t n_gt, const double* gx, const double* gy, const
                          const int32_t* g_ntraj, const int32_t* h_ntraj,
                          int32_t n_classes, const double* thr, size_t workspace_limit_bytes,
                          int64_t* id_counts, int64_t* hyp_idmatch) {
-    if (k_sets < 1 || n_streams < 0 || n_frames < 0 || n_gt < 0 || !set_row_offsets || !frame_hyp_offsets || !frame_gt_offsets ||
-        !stream_frame_offsets || !thr || !id_counts || !g_ntraj || !h_ntraj) {
-        wt::set_error("wt_mot_identity_host: bad argument");
-        return WT_ERR_INVALID;
-    }
-    if (n_classes < 1 || n_classes > kMaxClasses) { wt::set_error("wt_mot_identity: n_classes must be 1..%d", kMaxClasses); return WT_ERR_INVALID; }
-    const int64_t n_hyp = set_row_offsets[k_sets];
-    // ---- the layout must be what the kernel walks: checked here, the device form trusts its caller ----
-    if (frame_gt_offsets[0] != 0 || frame_gt_offsets[n_frames] != n_gt || stream_frame_offsets[0] != 0 ||
-        stream_frame_offsets[n_streams] != n_frames || set_row_offsets[0] != 0) {
-        wt::set_error("wt_mot_identity_host: CSR offsets do not cover the rows");
-        return WT_ERR_INVALID;
-    }
-    for (int32_t s = 0; s < n_streams; ++s)
-        if (stream_frame_offsets[s + 1] < stream_frame_offsets[s]) { wt::set_error("stream_frame_offsets must be non-decreasing"); return WT_ERR_INVALID; }
+    const wt::TrackInput in = {n_gt, gx, gy, gw, gh, g_category, g_level, g_traj, n_frames, frame_gt_offsets, n_streams, stream_frame_offsets,
+                               k_sets, set_row_offsets, frame_hyp_offsets, hx, hy, hw, hh, h_category, h_traj, n_classes};
+    WT_TRY(wt::check_track_layout(in, "wt_mot_identity_host", thr && id_counts && g_ntraj && h_ntraj, kMaxClasses));
     const size_t n_problems = (size_t)k_sets * (size_t)n_streams * (size_t)n_classes;
     int64_t max_g = 0, max_h = 0;
     for (size_t i = 0; i < (size_t)n_streams * (size_t)n_classes; ++i) {
@@ -399,39 +345,20 @@ int wt_mot_identity_host(int64_t n_gt, const double* gx, const double* gy, const
         max_h = std::max<int64_t>(max_h, h_ntraj[i]);
     }
     // a trajectory index inside its problem's count, and at most once per frame and class
-    std::vector<std::pair<int32_t, int32_t>> seen;
-    auto scan_frame = [&](const int32_t* cat, const int32_t* traj, const int32_t* counts, int64_t r0, int64_t r1) -> bool {
-        seen.clear();
-        for (int64_t r = r0; r < r1; ++r) {
-            if (cat[r] < 1 || cat[r] > n_classes) continue;
-            if (traj[r] < 0 || traj[r] >= counts[cat[r] - 1]) return false;
-            seen.emplace_back(cat[r], traj[r]);
-        }
-        std::sort(seen.begin(), seen.end());
-        return std::adjacent_find(seen.begin(), seen.end()) == seen.end();
+    auto ids_unique = [&](const int32_t* cat, const int32_t* traj, const int32_t* counts, int64_t r0, int64_t r1) {
+        return wt::frame_ids_unique(cat, traj, r0, r1, n_classes, [&](int64_t r) { return traj[r] >= 0 && traj[r] < counts[cat[r] - 1]; });
     };
-    for (int32_t s = 0; s < n_streams; ++s)
-        for (int64_t f = stream_frame_offsets[s]; f < stream_frame_offsets[s + 1]; ++f) {
-            const int64_t r0 = frame_gt_offsets[f], r1 = frame_gt_offsets[f + 1];
-            if (r1 < r0) { wt::set_error("frame_gt_offsets must be non-decreasing"); return WT_ERR_INVALID; }
-            if (!scan_frame(g_category, g_traj, g_ntraj + (size_t)s * n_classes, r0, r1)) {
-                wt::set_error("ground truth: a trajectory index is out of range or occurs twice in frame %lld", (long long)f);
-                return WT_ERR_INVALID;
-            }
-        }
-    for (int32_t k = 0; k < k_sets; ++k) {
-        const int64_t* fho = frame_hyp_offsets + (size_t)k * (size_t)(n_frames + 1);
-        const int64_t rows = set_row_offsets[k + 1] - set_row_offsets[k];
-        if (rows < 0 || fho[0] != 0 || fho[n_frames] > rows) { wt::set_error("result set %d: frame_hyp_offsets do not fit its rows", (int)k); return WT_ERR_INVALID; }
-        for (int32_t s = 0; s < n_streams; ++s)
-            for (int64_t f = stream_frame_offsets[s]; f < stream_frame_offsets[s + 1]; ++f) {
-                if (fho[f + 1] < fho[f]) { wt::set_error("result set %d: frame_hyp_offsets must be non-decreasing", (int)k); return WT_ERR_INVALID; }
-                if (!scan_frame(h_category, h_traj, h_ntraj + ((size_t)k * n_streams + s) * n_classes, set_row_offsets[k] + fho[f], set_row_offsets[k] + fho[f + 1])) {
-                    wt::set_error("result set %d: a trajectory index is out of range or occurs twice in frame %lld", (int)k, (long long)f);
-                    return WT_ERR_INVALID;
-                }
-            }
-    }
+    WT_TRY(wt::walk_track_frames(in,
+        [&](int32_t s, int64_t f, int64_t r0, int64_t r1) {
+            if (ids_unique(g_category, g_traj, g_ntraj + (size_t)s * n_classes, r0, r1)) return WT_OK;
+            wt::set_error("ground truth: a trajectory index is out of range or occurs twice in frame %lld", (long long)f);
+            return WT_ERR_INVALID;
+        },
+        [&](int32_t k, int32_t s, int64_t f, int64_t r0, int64_t r1) {
+            if (ids_unique(h_category, h_traj, h_ntraj + ((size_t)k * n_streams + s) * n_classes, r0, r1)) return WT_OK;
+            wt::set_error("result set %d: a trajectory index is out of range or occurs twice in frame %lld", (int)k, (long long)f);
+            return WT_ERR_INVALID;
+        }));
     if (max_g > kMaxTraj || max_h > kMaxTraj) {
         wt::set_error("%lld trajectories of one class in one stream: the assignment kernel takes at most %d a side", (long long)std::max(max_g, max_h), kMaxTraj);
         return WT_ERR_CAPACITY;
@@ -450,49 +377,18 @@ int wt_mot_identity_host(int64_t n_gt, const double* gx, const double* gy, const
         return WT_ERR_INVALID;
     }
     WT_TRY(wt::ensure_device());
-    const size_t ng = (size_t)n_gt, nh = (size_t)n_hyp;
-    wt::DevBuf dgx, dgy, dgw, dgh, dgc, dgl, dgi, dfo, dso, dsr, dfh, dhx, dhy, dhw, dhh, dhc, dhi, dgn, dhn, dmo, dcnt, dmatch, dstat, dws;
-    WT_TRY(dgx.alloc(8 * ng)); WT_TRY(dgy.alloc(8 * ng)); WT_TRY(dgw.alloc(8 * ng)); WT_TRY(dgh.alloc(8 * ng));
-    WT_TRY(dgc.alloc(4 * ng)); WT_TRY(dgl.alloc(4 * ng)); WT_TRY(dgi.alloc(4 * ng));
-    WT_TRY(dfo.alloc(8 * (size_t)(n_frames + 1))); WT_TRY(dso.alloc(8 * (size_t)(n_streams + 1)));
-    WT_TRY(dsr.alloc(8 * (size_t)(k_sets + 1))); WT_TRY(dfh.alloc(8 * (size_t)k_sets * (size_t)(n_frames + 1)));
-    WT_TRY(dhx.alloc(8 * nh)); WT_TRY(dhy.alloc(8 * nh)); WT_TRY(dhw.alloc(8 * nh)); WT_TRY(dhh.alloc(8 * nh));
-    WT_TRY(dhc.alloc(4 * nh)); WT_TRY(dhi.alloc(4 * nh));
-    WT_TRY(dgn.alloc(4 * (size_t)n_streams * n_classes)); WT_TRY(dhn.alloc(4 * n_problems)); WT_TRY(dmo.alloc(8 * (n_problems + 1)));
-    WT_TRY(dcnt.alloc(8 * n_problems * 6)); WT_TRY(dstat.alloc(16));
+    wt::StagedTrackInput staged;
+    WT_TRY(staged.upload(in));
+    const size_t nh = (size_t)staged.n_hyp;
+    wt::DevBuf dgn, dhn, dmo, dcnt, dmatch, dws;
+    WT_TRY(dgn.upload(g_ntraj, 4 * (size_t)n_streams * n_classes)); WT_TRY(dhn.upload(h_ntraj, 4 * n_problems));
+    WT_TRY(dmo.upload(mat_offsets.data(), 8 * (n_problems + 1)));
+    WT_TRY(dcnt.alloc(8 * n_problems * 6));
     if (hyp_idmatch) WT_TRY(dmatch.alloc(16 * nh));
-    if (ng) {
-        WT_HIP(hipMemcpy(dgx.p, gx, 8 * ng, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dgy.p, gy, 8 * ng, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dgw.p, gw, 8 * ng, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dgh.p, gh, 8 * ng, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dgc.p, g_category, 4 * ng, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dgl.p, g_level, 4 * ng, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dgi.p, g_traj, 4 * ng, hipMemcpyHostToDevice));
-    }
-    if (nh) {
-        WT_HIP(hipMemcpy(dhx.p, hx, 8 * nh, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dhy.p, hy, 8 * nh, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dhw.p, hw, 8 * nh, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dhh.p, hh, 8 * nh, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dhc.p, h_category, 4 * nh, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dhi.p, h_traj, 4 * nh, hipMemcpyHostToDevice));
-    }
-    WT_HIP(hipMemcpy(dfo.p, frame_gt_offsets, 8 * (size_t)(n_frames + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dso.p, stream_frame_offsets, 8 * (size_t)(n_streams + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dsr.p, set_row_offsets, 8 * (size_t)(k_sets + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dfh.p, frame_hyp_offsets, 8 * (size_t)k_sets * (size_t)(n_frames + 1), hipMemcpyHostToDevice));
-    if (n_streams) WT_HIP(hipMemcpy(dgn.p, g_ntraj, 4 * (size_t)n_streams * n_classes, hipMemcpyHostToDevice));
-    if (n_problems) WT_HIP(hipMemcpy(dhn.p, h_ntraj, 4 * n_problems, hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dmo.p, mat_offsets.data(), 8 * (n_problems + 1), hipMemcpyHostToDevice));
     WT_TRY(dws.alloc(wsb));
-    WT_TRY(wt_mot_identity_dev(n_gt, dgx.as<double>(), dgy.as<double>(), dgw.as<double>(), dgh.as<double>(), dgc.as<int32_t>(),
-                               dgl.as<int32_t>(), dgi.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams, dso.as<int64_t>(), k_sets, n_hyp,
-                               dsr.as<int64_t>(), dfh.as<int64_t>(), dhx.as<double>(), dhy.as<double>(), dhw.as<double>(), dhh.as<double>(),
-                               dhc.as<int32_t>(), dhi.as<int32_t>(), dgn.as<int32_t>(), dhn.as<int32_t>(), dmo.as<int64_t>(), matrix_floats,
-                               n_classes, thr, max_g, max_h, dcnt.as<int64_t>(), hyp_idmatch ? dmatch.as<int64_t>() : nullptr,
-                               dstat.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_HIP(hipDeviceSynchronize());
-    int32_t st = 0;
-    WT_HIP(hipMemcpy(&st, dstat.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (st) {
-        wt::set_error("identity evaluation kernel reported status %d (4 = capacity, 5 = assignment did not converge)", (int)st);
-        return (int)st;
-    }
+    WT_TRY(launch(staged.dev, staged.n_hyp, dgn.as<int32_t>(), dhn.as<int32_t>(), dmo.as<int64_t>(), matrix_floats, thr, max_g, max_h,
+                  dcnt.as<int64_t>(), hyp_idmatch ? dmatch.as<int64_t>() : nullptr, staged.status.as<int32_t>(), dws.p, wsb, nullptr));
+    WT_TRY(staged.finish("identity evaluation"));
     if (n_problems) WT_HIP(hipMemcpy(id_counts, dcnt.p, 8 * n_problems * 6, hipMemcpyDeviceToHost));
     if (nh && hyp_idmatch) WT_HIP(hipMemcpy(hyp_idmatch, dmatch.p, 16 * nh, hipMemcpyDeviceToHost));
     return WT_OK;

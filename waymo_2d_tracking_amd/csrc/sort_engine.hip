@@ -535,11 +535,6 @@ int run_tracking(int64_t n_dets, const double* x, const double* y, const double*
     WT_HIP(hipGetLastError());
     return WT_OK;
 }
-
-inline char* align256(void* p) {
-    const uintptr_t mis = (uintptr_t)p & 255;
-    return (char*)p + (mis ? 256 - mis : 0);
-}
 }  // namespace
 
 extern "C" {
@@ -571,7 +566,7 @@ int wt_track_streams_dev(int64_t n_dets, const double* x, const double* y, const
         WT_HIP(hipMemsetAsync(n_births_dev, 0, sizeof(int64_t), stream));
         return WT_OK;
     }
-    char* base = align256(workspace);
+    char* base = wt::align_ptr(workspace);
     Workspace ws = carve_ws(base, n_dets, n_frames, n_streams, C, cap, capN, cost_g);
     State st = carve_state(base + ws.bytes, n_streams, C, cap);
     if (!workspace || workspace_bytes < ws.bytes + st.bytes + 256) {
@@ -597,7 +592,7 @@ int wt_track_state_init_dev(void* state, size_t state_bytes, int32_t n_streams, 
     WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
     if (n_streams <= 0) { wt::set_error("n_streams must be positive"); return WT_ERR_INVALID; }
     const int C = params->n_classes;
-    State st = carve_state(align256(state), n_streams, C, cap);
+    State st = carve_state(wt::align_ptr(state), n_streams, C, cap);
     if (!state || state_bytes < st.bytes + 256) {
         wt::set_error("tracker state too small: need %zu bytes, have %zu", st.bytes + 256, state_bytes);
         return WT_ERR_CAPACITY;
@@ -637,12 +632,12 @@ int wt_track_chunk_dev(void* state, size_t state_bytes,
         WT_HIP(hipMemsetAsync(n_births_dev, 0, sizeof(int64_t), stream));
         return WT_OK;
     }
-    State st = carve_state(align256(state), n_streams, C, cap);
+    State st = carve_state(wt::align_ptr(state), n_streams, C, cap);
     if (!state || state_bytes < st.bytes + 256) {
         wt::set_error("tracker state too small: need %zu bytes, have %zu", st.bytes + 256, state_bytes);
         return WT_ERR_CAPACITY;
     }
-    Workspace ws = carve_ws(align256(workspace), n_dets, n_frames, n_streams, C, cap, capN, cost_g);
+    Workspace ws = carve_ws(wt::align_ptr(workspace), n_dets, n_frames, n_streams, C, cap, capN, cost_g);
     if (!workspace || workspace_bytes < ws.bytes + 256) {
         wt::set_error("tracking workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
         return WT_ERR_CAPACITY;
@@ -661,7 +656,7 @@ int wt_track_global_ids_dev(const void* state, size_t state_bytes, int32_t n_str
     int cap, capN, lds_cost; bool cost_g; size_t lds;
     WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
     if (n_streams <= 0 || !stream_birth_prefix) { wt::set_error("bad arguments"); return WT_ERR_INVALID; }
-    State st = carve_state(align256(const_cast<void*>(state)), n_streams, params->n_classes, cap);
+    State st = carve_state(wt::align_ptr(const_cast<void*>(state)), n_streams, params->n_classes, cap);
     if (!state || state_bytes < st.bytes + 256) { wt::set_error("tracker state too small"); return WT_ERR_CAPACITY; }
     hipLaunchKernelGGL(stream_prefix_kernel, dim3(1), dim3(1024), 0, stream, (int)n_streams, st,
                        (long long*)stream_birth_prefix);
@@ -703,24 +698,16 @@ int wt_track_streams_host(int64_t n_dets, const double* x, const double* y, cons
         }
     const size_t nd = (size_t)n_dets;
     wt::DevBuf dx, dy, dw, dh, ds, dc, dfo, dso, dcw, dch, of, oc, ob, os, oi, dn, dws;
-    WT_TRY(dx.alloc(8 * nd)); WT_TRY(dy.alloc(8 * nd)); WT_TRY(dw.alloc(8 * nd)); WT_TRY(dh.alloc(8 * nd));
-    WT_TRY(ds.alloc(8 * nd)); WT_TRY(dc.alloc(4 * nd));
-    WT_TRY(dfo.alloc(8 * (size_t)(n_frames + 1))); WT_TRY(dso.alloc(8 * (size_t)(n_streams + 1)));
-    WT_TRY(dcw.alloc(8 * (size_t)n_streams)); WT_TRY(dch.alloc(8 * (size_t)n_streams));
-    WT_TRY(of.alloc(8 * (nd + 1))); WT_TRY(oc.alloc(4 * (nd + 1))); WT_TRY(ob.alloc(32 * (nd + 1)));
-    WT_TRY(os.alloc(8 * (nd + 1))); WT_TRY(oi.alloc(8 * (nd + 1))); WT_TRY(dn.alloc(16));
-    if (nd) {
-        WT_HIP(hipMemcpy(dx.p, x, 8 * nd, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dy.p, y, 8 * nd, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dw.p, w, 8 * nd, hipMemcpyHostToDevice)); WT_HIP(hipMemcpy(dh.p, h, 8 * nd, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(ds.p, score, 8 * nd, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(dc.p, category, 4 * nd, hipMemcpyHostToDevice));
-    }
-    WT_HIP(hipMemcpy(dfo.p, frame_det_offsets, 8 * (size_t)(n_frames + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dso.p, stream_frame_offsets, 8 * (size_t)(n_streams + 1), hipMemcpyHostToDevice));
+    WT_TRY(dx.upload(x, 8 * nd)); WT_TRY(dy.upload(y, 8 * nd)); WT_TRY(dw.upload(w, 8 * nd)); WT_TRY(dh.upload(h, 8 * nd));
+    WT_TRY(ds.upload(score, 8 * nd)); WT_TRY(dc.upload(category, 4 * nd));
+    WT_TRY(dfo.upload(frame_det_offsets, 8 * (size_t)(n_frames + 1)));
+    WT_TRY(dso.upload(stream_frame_offsets, 8 * (size_t)(n_streams + 1)));
     std::vector<double> zeros;
     if (!clip_w || !clip_h) zeros.assign((size_t)n_streams, 0.0);
-    WT_HIP(hipMemcpy(dcw.p, clip_w ? clip_w : zeros.data(), 8 * (size_t)n_streams, hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(dch.p, clip_h ? clip_h : zeros.data(), 8 * (size_t)n_streams, hipMemcpyHostToDevice));
+    WT_TRY(dcw.upload(clip_w ? clip_w : zeros.data(), 8 * (size_t)n_streams));
+    WT_TRY(dch.upload(clip_h ? clip_h : zeros.data(), 8 * (size_t)n_streams));
+    WT_TRY(of.alloc(8 * (nd + 1))); WT_TRY(oc.alloc(4 * (nd + 1))); WT_TRY(ob.alloc(32 * (nd + 1)));
+    WT_TRY(os.alloc(8 * (nd + 1))); WT_TRY(oi.alloc(8 * (nd + 1))); WT_TRY(dn.alloc(16));
     const size_t wsb = wt_track_streams_workspace(n_dets, n_frames, n_streams, max_frame, params);
     if (!wsb) return WT_ERR_CAPACITY;
     WT_TRY(dws.alloc(wsb));

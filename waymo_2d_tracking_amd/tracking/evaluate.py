@@ -303,15 +303,31 @@ def _results(gt, packed, counts, iou_sum, hyp_match, hyp_switch, per_row):
     return results
 
 
-def evaluate_tracks(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False):
+_BOX = ('x', 'y', 'w', 'h')
+
+
+def _gt_args(gt, g, ids, ptr):
+    """The ground-truth arguments every wt_mot_* call begins with.  g: the columns by name (gt itself, or its tensors), ids: the
+    id / trajectory column; ptr makes a pointer (_lib.ptr of numpy arrays for the host forms, the data pointer of tensors for the
+    device forms)."""
+    return ([C.c_int64(gt['x'].size)] + [ptr(g[n]) for n in _BOX + ('category', 'level')] +
+            [ptr(ids), C.c_int64(gt['frame_ids'].size), ptr(g['frame_gt_offsets']), C.c_int32(len(gt['stream_keys'])), ptr(g['stream_frame_offsets'])])
+
+
+def _hyp_args(K, n_hyp, h, ids, ptr):
+    """The result arguments that follow them.  n_hyp: None for the host forms, which read it from set_row_offsets."""
+    return ([C.c_int32(K)] + ([] if n_hyp is None else [C.c_int64(n_hyp)]) + [ptr(h['set_row_offsets']), ptr(h['frame_hyp_offsets'])] +
+            [ptr(h[n]) for n in _BOX + ('category',)] + [ptr(ids)])
+
+
+def evaluate_tracks(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, packed=None):
     """Score K tracking results (load_tracks / tracks_from_packed) against one ground truth (load_ground_truth) in ONE
-    wt_mot_eval_host call.  Returns a list of K MotResult."""
+    wt_mot_eval_host call.  packed: pack_results() of the same arguments, when the caller has it.  Returns a list of K MotResult."""
     lib = _lib.lib()
     thr = _lib.as_f64(iou_threshold)
     n_classes = int(thr.size)
-    p = pack_results(gt, tracks_list, n_classes)
+    p = packed if packed is not None else pack_results(gt, tracks_list, n_classes)
     K = len(tracks_list)
-    n_frames = int(gt['frame_ids'].size)
     n_streams = len(gt['stream_keys'])
     counts = np.zeros((K, n_streams, n_classes, 2, 5), np.int64)
     iou_sum = np.zeros((K, n_streams, n_classes, 2), np.float64)
@@ -319,24 +335,19 @@ def evaluate_tracks(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_ro
     hyp_match = np.full(n_hyp, -2, np.int64)
     hyp_switch = np.zeros(n_hyp, np.uint8)
     rc = lib.wt_mot_eval_host(
-        C.c_int64(gt['x'].size), _lib.ptr(gt['x']), _lib.ptr(gt['y']), _lib.ptr(gt['w']), _lib.ptr(gt['h']),
-        _lib.ptr(gt['category']), _lib.ptr(gt['level']), _lib.ptr(gt['gt_id']),
-        C.c_int64(n_frames), _lib.ptr(gt['frame_gt_offsets']), C.c_int32(n_streams), _lib.ptr(gt['stream_frame_offsets']),
-        C.c_int32(K), _lib.ptr(p['set_row_offsets']), _lib.ptr(p['frame_hyp_offsets']),
-        _lib.ptr(p['x']), _lib.ptr(p['y']), _lib.ptr(p['w']), _lib.ptr(p['h']), _lib.ptr(p['category']), _lib.ptr(p['h_id']),
+        *_gt_args(gt, gt, gt['gt_id'], _lib.ptr), *_hyp_args(K, None, p, p['h_id'], _lib.ptr),
         C.c_int32(n_classes), _lib.ptr(thr), _lib.ptr(counts), _lib.ptr(iou_sum),
         _lib.ptr(hyp_match), _lib.ptr(hyp_switch) if per_row else None)
     _lib.check(rc, 'wt_mot_eval_host')
     return _results(gt, p, counts, iou_sum, hyp_match, hyp_switch, per_row)
 
 
-class DeviceEvaluation(object):
-    """The same evaluation with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues one
-    wt_mot_eval_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.
-    This is the form a device-resident sweep (tracker output scored without leaving the GPU) builds on; the layout checks of
-    the host form are done here when the inputs are packed."""
+class _DeviceForm(object):
+    """What DeviceEvaluation and DeviceIdentity share: the packed results, the ground-truth and result columns as torch tensors
+    in HBM (self.g, self.h; the subclass adds its id columns), the status word, and the wait for a launch."""
+    name = None                                     # the C entry point, for messages
 
-    def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD):
+    def __init__(self, gt, tracks_list, iou_threshold):
         import torch
         self.torch = torch
         self.lib = _lib.lib()
@@ -345,44 +356,70 @@ class DeviceEvaluation(object):
         self.n_classes = int(self.thr.size)
         self.p = pack_results(gt, tracks_list, self.n_classes)
         self.K = len(tracks_list)
-        self.n_frames = int(gt['frame_ids'].size)
         self.n_streams = len(gt['stream_keys'])
         self.n_hyp = int(self.p['set_row_offsets'][-1])
+        self.device = torch.device('cuda', torch.cuda.current_device())
+        self.g = dict((n, self.up(gt[n])) for n in _BOX + ('category', 'level', 'frame_gt_offsets', 'stream_frame_offsets'))
+        self.h = dict((n, self.up(self.p[n])) for n in _BOX + ('category', 'set_row_offsets', 'frame_hyp_offsets'))
+        self.status = self.zeros(1, torch.int32)
+
+    def up(self, a):
+        """numpy array -> tensor on the device (one element where the array is empty: a pointer the library may be handed)."""
+        t = self.torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(self.device) if a.size else self.zeros(1, t.dtype)
+
+    def zeros(self, shape, dtype):
+        return self.torch.zeros(shape, dtype=dtype, device=self.device)
+
+    def d(self, t):
+        """Device pointer of a tensor; an empty one (no streams) has none, and the library wants one it then never follows."""
+        return C.c_void_p(t.data_ptr() if t.numel() else self.status.data_ptr())
+
+    def leading_args(self, g_ids, h_ids):
+        return _gt_args(self.gt, self.g, g_ids, self.d) + _hyp_args(self.K, self.n_hyp, self.h, h_ids, self.d)
+
+    def wait(self):
+        """Synchronise the current stream and raise what the kernel reported."""
+        self.torch.cuda.current_stream().synchronize()
+        st = int(self.status.item())
+        if st:
+            raise _lib.WaymoTrackError('%s failed: %s (status reported by the kernel)' % (self.name, _lib._STATUS.get(st, st)))
+
+
+class DeviceEvaluation(_DeviceForm):
+    """The same evaluation with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues one
+    wt_mot_eval_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.
+    This is the form a device-resident sweep (tracker output scored without leaving the GPU) builds on; the layout checks of
+    the host form are done here when the inputs are packed."""
+    name = 'wt_mot_eval_dev'
+
+    def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD):
+        _DeviceForm.__init__(self, gt, tracks_list, iou_threshold)
+        torch = self.torch
         self.max_boxes = max_frame_boxes(gt, self.p, self.n_classes)
-        dev = torch.device('cuda', torch.cuda.current_device())
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros(1, dtype=torch.from_numpy(a).dtype, device=dev)
-        self.g = dict((n, up(gt[n])) for n in ('x', 'y', 'w', 'h', 'category', 'level', 'gt_id', 'frame_gt_offsets', 'stream_frame_offsets'))
-        self.h = dict((n, up(self.p[n])) for n in ('x', 'y', 'w', 'h', 'category', 'h_id', 'set_row_offsets', 'frame_hyp_offsets'))
-        self.counts = torch.zeros((self.K, self.n_streams, self.n_classes, 2, 5), dtype=torch.int64, device=dev)
-        self.iou_sum = torch.zeros((self.K, self.n_streams, self.n_classes, 2), dtype=torch.float64, device=dev)
-        self.hyp_match = torch.zeros(max(1, self.n_hyp), dtype=torch.int64, device=dev)
-        self.hyp_switch = torch.zeros(max(1, self.n_hyp), dtype=torch.uint8, device=dev)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.g['gt_id'], self.h['h_id'] = self.up(gt['gt_id']), self.up(self.p['h_id'])
+        self.counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 5), torch.int64)
+        self.iou_sum = self.zeros((self.K, self.n_streams, self.n_classes, 2), torch.float64)
+        self.hyp_match = self.zeros(max(1, self.n_hyp), torch.int64)
+        self.hyp_switch = self.zeros(max(1, self.n_hyp), torch.uint8)
         self.lib.wt_mot_eval_workspace.restype = C.c_size_t
         self.ws_bytes = int(self.lib.wt_mot_eval_workspace(C.c_int32(self.K), C.c_int32(self.n_streams), C.c_int32(self.n_classes),
                                                            C.c_int64(self.max_boxes), C.c_int32(int(gt['max_gt_ids']))))
         if not self.ws_bytes:
             _lib.check(4, 'wt_mot_eval_workspace')
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
 
     def launch(self):
-        g, h, v = self.g, self.h, C.c_void_p
-        d = lambda t: v(t.data_ptr())
+        d = self.d
         rc = self.lib.wt_mot_eval_dev(
-            C.c_int64(self.gt['x'].size), d(g['x']), d(g['y']), d(g['w']), d(g['h']), d(g['category']), d(g['level']), d(g['gt_id']),
-            C.c_int64(self.n_frames), d(g['frame_gt_offsets']), C.c_int32(self.n_streams), d(g['stream_frame_offsets']),
-            C.c_int32(self.K), C.c_int64(self.n_hyp), d(h['set_row_offsets']), d(h['frame_hyp_offsets']),
-            d(h['x']), d(h['y']), d(h['w']), d(h['h']), d(h['category']), d(h['h_id']),
+            *self.leading_args(self.g['gt_id'], self.h['h_id']),
             C.c_int32(self.n_classes), _lib.ptr(self.thr), C.c_int64(self.max_boxes), C.c_int32(int(self.gt['max_gt_ids'])),
             d(self.counts), d(self.iou_sum), d(self.hyp_match), d(self.hyp_switch), d(self.status),
-            d(self.ws), C.c_size_t(self.ws_bytes), v(self.torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, 'wt_mot_eval_dev')
+            d(self.ws), C.c_size_t(self.ws_bytes), C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, self.name)
 
     def results(self, per_row=False):
-        self.torch.cuda.current_stream().synchronize()
-        st = int(self.status.item())
-        if st:
-            raise _lib.WaymoTrackError('wt_mot_eval_dev failed: %s (status reported by the kernel)' % _lib._STATUS.get(st, st))
+        self.wait()
         return _results(self.gt, self.p, self.counts.cpu().numpy(), self.iou_sum.cpu().numpy(),
                         self.hyp_match.cpu().numpy()[:self.n_hyp], self.hyp_switch.cpu().numpy()[:self.n_hyp], per_row)
 
@@ -516,16 +553,17 @@ def _identity_calls(lib, g_ntraj, h_ntraj, limit):
     return calls
 
 
-def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, workspace_limit_bytes=DEFAULT_WORKSPACE_LIMIT):
+def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, workspace_limit_bytes=DEFAULT_WORKSPACE_LIMIT,
+                      packed=None):
     """IDF1 / IDP / IDR of K tracking results against one ground truth through wt_mot_identity_host: as few calls as the workspace
-    limit allows (the results do not depend on the split).  Returns a list of K IdentityResult."""
+    limit allows (the results do not depend on the split).  packed: pack_results() of the same arguments, when the caller has it.
+    Returns a list of K IdentityResult."""
     lib = _lib.lib()
     thr = _lib.as_f64(iou_threshold)
     n_classes = int(thr.size)
-    p = pack_results(gt, tracks_list, n_classes)
+    p = packed if packed is not None else pack_results(gt, tracks_list, n_classes)
     g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, p, n_classes)
     K = len(tracks_list)
-    n_frames = int(gt['frame_ids'].size)
     n_streams = len(gt['stream_keys'])
     id_counts = np.zeros((K, n_streams, n_classes, 2, 3), np.int64)
     set_rows = p['set_row_offsets']
@@ -533,18 +571,15 @@ def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_
     g_ntraj_c = np.ascontiguousarray(g_ntraj)
     for k0, k1 in _identity_calls(lib, g_ntraj, h_ntraj, workspace_limit_bytes):
         lo, hi = int(set_rows[k0]), int(set_rows[k1])
-        rows = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
-        fho = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
+        h = dict((n, p[n][lo:hi]) for n in _BOX + ('category',))
+        h['set_row_offsets'] = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
+        h['frame_hyp_offsets'] = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
         hn = np.ascontiguousarray(h_ntraj[k0:k1])
         cnt = np.zeros((k1 - k0, n_streams, n_classes, 2, 3), np.int64)
         match = np.full((hi - lo, 2), -2, np.int64)
         rc = lib.wt_mot_identity_host(
-            C.c_int64(gt['x'].size), _lib.ptr(gt['x']), _lib.ptr(gt['y']), _lib.ptr(gt['w']), _lib.ptr(gt['h']),
-            _lib.ptr(gt['category']), _lib.ptr(gt['level']), _lib.ptr(g_traj),
-            C.c_int64(n_frames), _lib.ptr(gt['frame_gt_offsets']), C.c_int32(n_streams), _lib.ptr(gt['stream_frame_offsets']),
-            C.c_int32(k1 - k0), _lib.ptr(rows), _lib.ptr(fho),
-            _lib.ptr(p['x'][lo:hi]), _lib.ptr(p['y'][lo:hi]), _lib.ptr(p['w'][lo:hi]), _lib.ptr(p['h'][lo:hi]),
-            _lib.ptr(p['category'][lo:hi]), _lib.ptr(h_traj[lo:hi]), _lib.ptr(g_ntraj_c), _lib.ptr(hn),
+            *_gt_args(gt, gt, g_traj, _lib.ptr), *_hyp_args(k1 - k0, None, h, h_traj[lo:hi], _lib.ptr),
+            _lib.ptr(g_ntraj_c), _lib.ptr(hn),
             C.c_int32(n_classes), _lib.ptr(thr), C.c_size_t(int(workspace_limit_bytes or 0)), _lib.ptr(cnt),
             _lib.ptr(match) if per_row else None)
         _lib.check(rc, 'wt_mot_identity_host')
@@ -553,23 +588,15 @@ def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_
     return _identity_results(gt, p, id_counts, hyp_idmatch, per_row)
 
 
-class DeviceIdentity(object):
+class DeviceIdentity(_DeviceForm):
     """evaluate_identity with everything resident in HBM, beside DeviceEvaluation: ``launch()`` enqueues one wt_mot_identity_dev
     on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.  All K results go into
     one call; workspace_bytes overrides the size of the workspace tensor (a smaller one is refused by the library)."""
+    name = 'wt_mot_identity_dev'
 
     def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, workspace_bytes=None):
-        import torch
-        self.torch = torch
-        self.lib = _lib.lib()
-        self.gt = gt
-        self.thr = _lib.as_f64(iou_threshold)
-        self.n_classes = int(self.thr.size)
-        self.p = pack_results(gt, tracks_list, self.n_classes)
-        self.K = len(tracks_list)
-        self.n_frames = int(gt['frame_ids'].size)
-        self.n_streams = len(gt['stream_keys'])
-        self.n_hyp = int(self.p['set_row_offsets'][-1])
+        _DeviceForm.__init__(self, gt, tracks_list, iou_threshold)
+        torch = self.torch
         g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, self.p, self.n_classes)
         self.g_ntraj, self.h_ntraj = g_ntraj, h_ntraj
         self.max_g = int(g_ntraj.max()) if g_ntraj.size else 0
@@ -580,36 +607,24 @@ class DeviceIdentity(object):
         self.ws_bytes = _identity_workspace(self.lib, self.K, self.n_streams, self.n_classes, self.max_g, self.max_h, self.matrix_floats)
         if not self.ws_bytes:
             _lib.check(4, 'wt_mot_identity_workspace')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros(1, dtype=torch.from_numpy(a).dtype, device=dev)
-        self.g = dict((n, up(gt[n])) for n in ('x', 'y', 'w', 'h', 'category', 'level', 'frame_gt_offsets', 'stream_frame_offsets'))
-        self.h = dict((n, up(self.p[n])) for n in ('x', 'y', 'w', 'h', 'category', 'set_row_offsets', 'frame_hyp_offsets'))
-        self.g['traj'], self.h['traj'] = up(g_traj), up(h_traj)
-        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = up(g_ntraj), up(h_ntraj), up(mat_offsets)
-        self.id_counts = torch.zeros((self.K, self.n_streams, self.n_classes, 2, 3), dtype=torch.int64, device=dev)
-        self.hyp_idmatch = torch.zeros((max(1, self.n_hyp), 2), dtype=torch.int64, device=dev)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=dev)
+        self.g['traj'], self.h['traj'] = self.up(g_traj), self.up(h_traj)
+        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = self.up(g_ntraj), self.up(h_ntraj), self.up(mat_offsets)
+        self.id_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 3), torch.int64)
+        self.hyp_idmatch = self.zeros((max(1, self.n_hyp), 2), torch.int64)
+        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
 
     def launch(self):
-        g, h, v = self.g, self.h, C.c_void_p
-        d = lambda t: v(t.data_ptr())
+        d = self.d
         rc = self.lib.wt_mot_identity_dev(
-            C.c_int64(self.gt['x'].size), d(g['x']), d(g['y']), d(g['w']), d(g['h']), d(g['category']), d(g['level']), d(g['traj']),
-            C.c_int64(self.n_frames), d(g['frame_gt_offsets']), C.c_int32(self.n_streams), d(g['stream_frame_offsets']),
-            C.c_int32(self.K), C.c_int64(self.n_hyp), d(h['set_row_offsets']), d(h['frame_hyp_offsets']),
-            d(h['x']), d(h['y']), d(h['w']), d(h['h']), d(h['category']), d(h['traj']),
-            d(g['ntraj']), d(h['ntraj']), d(self.mat_offsets), C.c_int64(self.matrix_floats),
+            *self.leading_args(self.g['traj'], self.h['traj']),
+            d(self.g['ntraj']), d(self.h['ntraj']), d(self.mat_offsets), C.c_int64(self.matrix_floats),
             C.c_int32(self.n_classes), _lib.ptr(self.thr), C.c_int64(self.max_g), C.c_int64(self.max_h),
             d(self.id_counts), d(self.hyp_idmatch), d(self.status),
-            d(self.ws), C.c_size_t(int(self.ws.numel())), v(self.torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, 'wt_mot_identity_dev')
+            d(self.ws), C.c_size_t(int(self.ws.numel())), C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, self.name)
 
     def results(self, per_row=False):
-        self.torch.cuda.current_stream().synchronize()
-        st = int(self.status.item())
-        if st:
-            raise _lib.WaymoTrackError('wt_mot_identity_dev failed: %s (status reported by the kernel)' % _lib._STATUS.get(st, st))
+        self.wait()
         return _identity_results(self.gt, self.p, self.id_counts.cpu().numpy(), self.hyp_idmatch.cpu().numpy()[:self.n_hyp], per_row)
 
 
@@ -664,8 +679,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     if rank_by not in ('mota', 'idf1'):
         raise ValueError("rank_by must be 'mota' or 'idf1'")
     identity = identity or rank_by == 'idf1'
-    results = evaluate_tracks(gt, tracks, iou_threshold)
-    id_results = evaluate_identity(gt, tracks, iou_threshold) if identity else None
+    packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for both metrics
+    results = evaluate_tracks(gt, tracks, iou_threshold, packed=packed_results)
+    id_results = evaluate_identity(gt, tracks, iou_threshold, packed=packed_results) if identity else None
     key = 'IDF1' if rank_by == 'idf1' else 'MOTA'
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
