@@ -56,6 +56,29 @@ def linear_assignment(cost):
     return pairs[:k.value].astype(np.int64)
 
 
+def linear_assignment_stats(cost):
+    """linear_assignment plus the oracle's work counters: (pairs, dict(step6=executions of step 6 that changed the matrix,
+    paths=augmenting paths, longest_path=stars on the longest augmenting path))."""
+    cost = np.ascontiguousarray(cost, dtype=np.float32)
+    n, m = cost.shape
+    pairs = np.zeros((min(n, m) + 1, 2), dtype=np.int32)
+    k = C.c_int(0)
+    stats = np.zeros(3, dtype=np.int64)
+    rc = lib().wto_linear_assignment_stats_f32(_p(cost), C.c_int(n), C.c_int(m), _p(pairs), C.byref(k), _p(stats))
+    assert rc == 0, rc
+    return pairs[:k.value].astype(np.int64), dict(step6=int(stats[0]), paths=int(stats[1]), longest_path=int(stats[2]))
+
+
+def iou_cost(dets5, trks4):
+    """The float32 matrix associate() hands to the assignment: -iou, shape (n, t)."""
+    dets5 = np.ascontiguousarray(dets5, dtype=np.float32).reshape(-1, 5)
+    trks4 = np.ascontiguousarray(trks4, dtype=np.float64).reshape(-1, 4)
+    neg = np.zeros((len(dets5), len(trks4)), dtype=np.float32)
+    if neg.size:
+        lib().wto_iou_cost(_p(dets5), C.c_int(len(dets5)), _p(trks4), C.c_int(len(trks4)), _p(neg))
+    return neg
+
+
 def associate(dets5, trks4, iou_threshold):
     dets5 = np.ascontiguousarray(dets5, dtype=np.float32).reshape(-1, 5)
     trks4 = np.ascontiguousarray(trks4, dtype=np.float64).reshape(-1, 4)
@@ -92,6 +115,13 @@ class Sort(object):
         rc = lib().wto_sort_state(C.c_void_p(self._h), C.c_int(cap), _p(ids), _p(x), _p(P), C.byref(n))
         assert rc == 0, rc
         return ids[:n.value].copy(), x[:n.value].copy(), P[:n.value].copy()
+
+    def predicted(self, cap=8192):
+        """Predicted boxes (t, 4) the next update() associates against; the tracker is not changed."""
+        boxes = np.zeros((cap, 4)); n = C.c_int(0)
+        rc = lib().wto_sort_predicted(C.c_void_p(self._h), C.c_int(cap), _p(boxes), C.byref(n))
+        assert rc == 0, rc
+        return boxes[:n.value].copy()
 
     def __del__(self):
         if getattr(self, '_h', None):

@@ -40,6 +40,7 @@ typedef struct {
     float* C;
     unsigned char *row_cov, *col_cov;
     int *row_star, *col_star, *row_prime;
+    int64_t* stats;      /* optional work counters (wto_linear_assignment_stats_f32), NULL: none */
 } munkres_t;
 
 static void mk_clear_covers(munkres_t* s)
@@ -102,6 +103,7 @@ static int mk_run(munkres_t* s)
                         if (s->row_cov[r]) for (c = 0; c < m; ++c) C[(size_t)r * m + c] = C[(size_t)r * m + c] + mn;
                     for (c = 0; c < m; ++c)
                         if (!s->col_cov[c]) for (r = 0; r < n; ++r) C[(size_t)r * m + c] = C[(size_t)r * m + c] - mn;
+                    if (s->stats) s->stats[0] += 1;
                 }
                 continue;
             }
@@ -113,12 +115,18 @@ static int mk_run(munkres_t* s)
         /* step 5: augmenting path from Z0; stars on the path are removed, primes become stars */
         {
             int pr = z0r, pc = z0c;
+            int64_t path_stars = 0;                      /* stars on the path: each one moves to its row's prime */
             for (;;) {
                 int r2 = s->col_star[pc];
                 s->row_star[pr] = pc; s->col_star[pc] = pr;
                 if (r2 < 0) break;
                 pr = r2; pc = s->row_prime[r2];
+                ++path_stars;
                 if (++guard > guard_max) return 5;
+            }
+            if (s->stats) {
+                s->stats[1] += 1;
+                if (path_stars > s->stats[2]) s->stats[2] = path_stars;
             }
             mk_clear_covers(s);
             for (r = 0; r < n; ++r) s->row_prime[r] = -1;
@@ -126,12 +134,13 @@ static int mk_run(munkres_t* s)
     }
 }
 
-int wto_linear_assignment_f32(const float* cost, int n_rows, int n_cols, int* pairs, int* n_pairs)
+static int linear_assignment_impl(const float* cost, int n_rows, int n_cols, int* pairs, int* n_pairs, int64_t* stats)
 {
     *n_pairs = 0;
     if (n_rows <= 0 || n_cols <= 0) return 0;
     const int transposed = n_cols < n_rows;
     munkres_t s;
+    s.stats = stats;
     s.n = transposed ? n_cols : n_rows;
     s.m = transposed ? n_rows : n_cols;
     s.C = (float*)malloc(sizeof(float) * (size_t)s.n * s.m);
@@ -158,6 +167,30 @@ int wto_linear_assignment_f32(const float* cost, int n_rows, int n_cols, int* pa
     }
     free(s.C); free(s.row_cov); free(s.col_cov); free(s.row_star); free(s.col_star); free(s.row_prime);
     return rc;
+}
+
+int wto_linear_assignment_f32(const float* cost, int n_rows, int n_cols, int* pairs, int* n_pairs)
+{
+    return linear_assignment_impl(cost, n_rows, n_cols, pairs, n_pairs, NULL);
+}
+
+/* the same run with work counters: stats[0] step-6 executions that changed the matrix, stats[1] augmenting paths,
+ * stats[2] stars on the longest augmenting path */
+int wto_linear_assignment_stats_f32(const float* cost, int n_rows, int n_cols, int* pairs, int* n_pairs, int64_t stats[3])
+{
+    stats[0] = stats[1] = stats[2] = 0;
+    return linear_assignment_impl(cost, n_rows, n_cols, pairs, n_pairs, stats);
+}
+
+/* test hook: the float32 matrix handed to linear_assignment by wto_associate (sort.py:201-206), -iou, (n, t) row-major */
+void wto_iou_cost(const float* dets5, int n, const double* trks4, int t, float* neg)
+{
+    int d, k;
+    for (d = 0; d < n; ++d)
+        for (k = 0; k < t; ++k) {
+            float v = (float)wto_iou(dets5 + 5 * (size_t)d, trks4 + 4 * (size_t)k);
+            neg[(size_t)d * t + k] = -v;
+        }
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -392,6 +425,24 @@ int wto_sort_state(const wto_sort* s, int cap, int64_t* ids, double* x7, double*
 }
 
 static int is_bad(double v) { return v != v || v == INFINITY || v == -INFINITY; }
+
+/* test hook: the predicted boxes the NEXT wto_sort_update will associate against (sort.py:256-265), in list order;
+ * works on copies, the tracker is not changed */
+int wto_sort_predicted(const wto_sort* s, int cap, double* boxes4, int* n_boxes)
+{
+    int i, t = 0;
+    for (i = 0; i < s->n_trk; ++i) {
+        track_t c = s->trk[i];
+        double b[4];
+        track_predict(&c);
+        x_to_bbox(c.x, b);
+        if (is_bad(b[0]) || is_bad(b[1]) || is_bad(b[2]) || is_bad(b[3])) continue;
+        if (t < cap) memcpy(boxes4 + 4 * (size_t)t, b, sizeof(b));
+        ++t;
+    }
+    *n_boxes = t;
+    return t > cap ? 4 : 0;
+}
 
 int wto_sort_update(wto_sort* s, const float* dets5, int n, double iou_threshold, double* out6, int cap, int* k_out)
 {

@@ -1,7 +1,7 @@
 """HIP SORT engine (through the C ABI of libwaymotrack.so) against the reference-generated golden vectors and
 against the CPU oracle on seeded inputs.  Track IDs / assignments / order bit-exact; boxes within 1e-6 of the
 reference fixture (north_star: 1e-4) and bit-identical to the oracle except the libm-vs-ocml exp() of the
-confidence (<= 2 ulp)."""
+confidence (<= 2 ulp).  Adversarial inputs for every Munkres / association variant are in test_gpu_sort_assignment.py."""
 import json
 import os
 
