@@ -400,6 +400,63 @@ int wt_mot_identity_host(int64_t n_gt, const double* gx, const double* gy, const
                          int64_t* id_counts, int64_t* hyp_idmatch);
 
 /* =================================================================================================
+ * MOT HOTA evaluation (HOTA / DetA / AssA / LocA per class and Waymo difficulty level; the definition is DESIGN.md section 19)
+ * ================================================================================================= */
+
+/* Scores K >= 1 tracking results against one ground truth with HOTA (Luiten et al. 2021) at the 19 localisation thresholds
+ * alpha_a = (a + 1) / 20: one wavefront per (result set, stream, class, difficulty level) walks the stream's frames twice.  The
+ * first walk adds, per (ground-truth trajectory, hypothesis trajectory), the frame's S / (row + col - S) of every overlapping
+ * pair into a float64 matrix and turns it into the alignment score A = P / (cg + ch - P); the second solves ONE assignment per
+ * frame on the float32 matrix A * IoU (the Munkres of the tracker on its negative, no gate) and counts every kept pair at the
+ * thresholds its IoU reaches.  LEVEL_1 is the same computation without the level-2 ground-truth rows and without the result rows
+ * that, in their frame, reach the class's thr with a removed row and with no counted one; thr has no other use.  IoU as in
+ * wt_mot_eval_*.
+ *
+ * Ground truth, results, trajectory indices and counts: exactly the arguments of wt_mot_identity_*.
+ * mat_offsets (K * n_streams * n_classes + 1) int64, device form only: where each problem's cells start inside the matrix part
+ * of the workspace; problem p needs 2 * g_ntraj * h_ntraj cells (one matrix per level), matrix_cells = mat_offsets[last] is the
+ * total.  A cell is 46 bytes: the float64 score and 19 uint16 match counts.  The host form computes the offsets.
+ * max_frame_boxes: upper bound of the boxes of ONE class in one frame on either side (<= 4096, more is WT_ERR_CAPACITY);
+ * max_gt_traj / max_hyp_traj: upper bounds of g_ntraj / h_ntraj (<= 4096 likewise).  A stream has at most 65535 frames.
+ * Outputs: hota_counts (K, n_streams, n_classes, 2, 21) int64 = gt, hyp, tp[19] for LEVEL_1, LEVEL_2;
+ *          hota_sums (K, n_streams, n_classes, 2, 19, 4) float64 = ass, assre, asspr, loc per threshold; loc is added in frame
+ *          order, then ground-truth row order; the association sums are added per lane over the cells l, l + 64, ... and then
+ *          over the lanes in order, the same on every run;
+ *          hyp_match (n_hyp, 2) int64, may be NULL: per result row and level the ground-truth row the frame's assignment
+ *          gave it, -1 unmatched, -2 took no part or was removed at that level.  It does not depend on the threshold.
+ * The device form takes device pointers (thr: host pointer, read before the call returns), is stream-ordered, never allocates
+ * or synchronises, and reports in status_dev (device int32) 0 or the WT_ERR_* a wavefront met (capacity: counts or offsets that
+ * do not fit the rows; assignment did not converge), after which that wavefront's outputs stay zero.  A workspace smaller than
+ * wt_mot_hota_workspace() says is WT_ERR_INVALID and nothing is launched.  It does not check the layout; the host form does
+ * (WT_ERR_INVALID names the frame), stages everything itself, and fails with WT_ERR_INVALID when the workspace it needs exceeds
+ * workspace_limit_bytes (0 = no limit): the caller then scores fewer results per call.
+ * wt_mot_hota_limits: 4096, 4096, 65535, and the sizes up to which a frame's cost matrix (min * (max | 1) floats) and its zero
+ * bitmaps (n * ceil(n / 64) * 8 bytes at max_frame_boxes = n) stay in LDS; beyond them they live in the workspace. */
+void wt_mot_hota_limits(int32_t* max_frame_boxes, int32_t* max_trajectories, int32_t* max_stream_frames, int64_t* lds_cost_floats,
+                        int64_t* lds_zmask_bytes);
+size_t wt_mot_hota_workspace(int32_t k_sets, int32_t n_streams, int32_t n_classes, int64_t max_frame_boxes, int64_t max_gt_traj,
+                             int64_t max_hyp_traj, int64_t matrix_cells);
+int wt_mot_hota_dev(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                    const int32_t* g_category, const int32_t* g_level, const int32_t* g_traj,
+                    int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                    int32_t k_sets, int64_t n_hyp, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                    const double* hx, const double* hy, const double* hw, const double* hh,
+                    const int32_t* h_category, const int32_t* h_traj,
+                    const int32_t* g_ntraj, const int32_t* h_ntraj, const int64_t* mat_offsets, int64_t matrix_cells,
+                    int32_t n_classes, const double* thr, int64_t max_frame_boxes, int64_t max_gt_traj, int64_t max_hyp_traj,
+                    int64_t* hota_counts, double* hota_sums, int64_t* hyp_match, int32_t* status_dev,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int wt_mot_hota_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                     const int32_t* g_category, const int32_t* g_level, const int32_t* g_traj,
+                     int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                     int32_t k_sets, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                     const double* hx, const double* hy, const double* hw, const double* hh,
+                     const int32_t* h_category, const int32_t* h_traj,
+                     const int32_t* g_ntraj, const int32_t* h_ntraj,
+                     int32_t n_classes, const double* thr, size_t workspace_limit_bytes,
+                     int64_t* hota_counts, double* hota_sums, int64_t* hyp_match);
+
+/* =================================================================================================
  * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

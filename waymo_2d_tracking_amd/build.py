@@ -31,6 +31,7 @@ UNITS = {
     'sort_single.hip': ['-ffp-contract=off'],
     'mot_eval.hip': ['-ffp-contract=off'],             # CLEAR-MOT evaluation: float64 IoU in the reference's operation order
     'mot_identity.hip': ['-ffp-contract=off'],         # IDF1 / IDP / IDR: the same float64 IoU, trajectory overlap counts and one global assignment
+    'mot_hota.hip': ['-ffp-contract=off'],             # HOTA: the same float64 IoU, float64 alignment scores, one assignment per frame for 19 thresholds
     'det_eval.hip': ['-ffp-contract=off'],             # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_roialign.hip': [],
     'det_nms.hip': [],

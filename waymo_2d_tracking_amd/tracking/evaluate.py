@@ -1,15 +1,17 @@
 """MOTA / MOTP of tracking results against ground truth, and the threshold sweep that tunes the tracker's flags.
 
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
-        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity]
+        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--identity] [--rank-by idf1]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--identity] [--hota] [--rank-by idf1|hota]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
 kernel behind ``wt_mot_eval_host`` (include/waymotrack.h): K results are scored in one launch, which is what makes a
 sweep over tracker settings cost seconds.  --identity adds identity preservation (IDF1 / IDP / IDR, Ristani et al. 2016; DESIGN.md
-section 18) through ``wt_mot_identity_host``: per problem one trajectory-by-trajectory overlap matrix and one global assignment.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
+section 18) through ``wt_mot_identity_host``: per problem one trajectory-by-trajectory overlap matrix and one global assignment.
+--hota adds HOTA / DetA / AssA / LocA (Luiten et al. 2021) through ``wt_mot_hota_host``: one wavefront per
+problem and difficulty level, one assignment per frame scored at 19 localisation thresholds.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
 """
 import argparse
 import ctypes as C
@@ -629,6 +631,211 @@ class DeviceIdentity(_DeviceForm):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# HOTA (DetA / AssA / LocA over 19 localisation thresholds)
+N_ALPHAS = 19
+HOTA_SUMS = ('ass', 'assre', 'asspr', 'loc')
+HOTA_NAMES = ('HOTA', 'DetA', 'AssA', 'DetRe', 'DetPr', 'AssRe', 'AssPr', 'LocA')
+
+
+def _matrix_cells(g_ntraj, h_ntraj):
+    """Per problem, the cells of its two matrices (LEVEL_1, LEVEL_2): 2 * g * h."""
+    return 2 * np.broadcast_to(g_ntraj.astype(np.int64), h_ntraj.shape) * h_ntraj.astype(np.int64)
+
+
+def hota_row(gt, hyp, tp, sums):
+    """Added counts (gt, hyp, tp[19]) and sums ((19, 4): ass, assre, asspr, loc) -> the reported row: the eight scores averaged
+    over the thresholds (LocA over those with a match), HOTA(0), LocA(0) and 'per_alpha' with the 19 values of each.  NaN where a
+    denominator is 0; the association scores of a threshold without a match are 0."""
+    gt, hyp = int(gt), int(hyp)
+    per = dict((n, []) for n in HOTA_NAMES)
+    div = lambda a, b: a / b if b else math.nan
+    for a in range(N_ALPHAS):
+        t = int(tp[a])
+        ass, assre, asspr, loc = (float(v) for v in sums[a])
+        per['DetA'].append(div(t, gt + hyp - t))
+        per['DetRe'].append(div(t, gt))
+        per['DetPr'].append(div(t, hyp))
+        per['AssA'].append(ass / t if t else 0.0)
+        per['AssRe'].append(assre / t if t else 0.0)
+        per['AssPr'].append(asspr / t if t else 0.0)
+        per['LocA'].append(div(loc, t))
+        per['HOTA'].append(math.sqrt(per['DetA'][a] * per['AssA'][a]) if gt + hyp else math.nan)
+    row = {'gt': gt, 'hyp': hyp, 'tp': [int(v) for v in tp]}
+    for n in HOTA_NAMES:
+        vals = per[n] if n != 'LocA' else [v for v, t in zip(per[n], tp) if t > 0]
+        total = 0.0
+        for v in vals:                               # one after the other, a ascending
+            total = total + v
+        row[n] = total / len(vals) if vals else math.nan
+    row['HOTA(0)'], row['LocA(0)'] = per['HOTA'][0], per['LocA'][0]
+    row['per_alpha'] = per
+    return row
+
+
+def _hota_added(counts, sums, classes, li):
+    """Counts and sums of `classes` at level index li, added class by class, stream by stream (the order is part of the definition)."""
+    cnt = np.zeros(2 + N_ALPHAS, np.int64)
+    tot = np.zeros((N_ALPHAS, 4), np.float64)
+    for cc in classes:
+        for s in range(counts.shape[0]):
+            cnt += counts[s, cc - 1, li]
+            tot = tot + sums[s, cc - 1, li]
+    return cnt, tot
+
+
+class HotaResult(object):
+    """HOTA scores of one tracking result.
+
+    hota_counts (n_streams, n_classes, 2, 21) int64: gt, hyp, tp[19] for LEVEL_1, LEVEL_2, per stream
+    hota_sums   (n_streams, n_classes, 2, 19, 4) float64: ass, assre, asspr, loc per threshold alpha_a = (a + 1) / 20
+    table       {class id or 'ALL': {1: row, 2: row}}, row = hota_row() of the added counts ('ALL' = classes 1, 2, 4)
+    ignored_rows   result rows that took no part
+    hyp_match   (with per_row=True) (rows, 2) int64 in file order, LEVEL_1 then LEVEL_2: index of the annotation in the ground-truth
+                file's list that the frame's assignment gave the box, -1 unmatched, -2 took no part or removed at that level."""
+
+    def __init__(self, hota_counts, hota_sums, ignored_rows, stream_keys, hyp_match=None):
+        self.hota_counts, self.hota_sums, self.ignored_rows, self.stream_keys = hota_counts, hota_sums, ignored_rows, stream_keys
+        self.hyp_match = hyp_match
+        self.table = {}
+        n_classes = hota_counts.shape[1]
+        for c in list(range(1, n_classes + 1)) + ['ALL']:
+            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
+            self.table[c] = {}
+            for li, lv in enumerate(LEVELS):
+                cnt, tot = _hota_added(hota_counts, hota_sums, classes, li)
+                self.table[c][lv] = hota_row(cnt[0], cnt[1], cnt[2:], tot)
+                self.table[c][lv]['sums'] = dict((n, tot[:, i].tolist()) for i, n in enumerate(HOTA_SUMS))
+
+    def hota(self, level=2, category='ALL'):
+        return self.table[category][level]['HOTA']
+
+    def as_json(self):
+        return {'ignored_rows': int(self.ignored_rows),
+                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
+
+
+def _hota_results(gt, packed, hota_counts, hota_sums, hyp_match, per_row):
+    results = []
+    set_rows = packed['set_row_offsets']
+    for k in range(len(set_rows) - 1):
+        lo, hi = int(set_rows[k]), int(set_rows[k + 1])
+        match = None
+        if per_row:
+            m = hyp_match[lo:hi]
+            match = np.empty((hi - lo, 2), np.int64)
+            match[packed['orders'][k]] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
+        ignored = (hi - lo) - int(packed['frame_hyp_offsets'][k][-1])
+        results.append(HotaResult(hota_counts[k], hota_sums[k], ignored, gt['stream_keys'], match))
+    return results
+
+
+def _hota_workspace(lib, k, n_streams, n_classes, max_boxes, max_g, max_h, cells):
+    lib.wt_mot_hota_workspace.restype = C.c_size_t
+    return int(lib.wt_mot_hota_workspace(C.c_int32(k), C.c_int32(n_streams), C.c_int32(n_classes), C.c_int64(max_boxes), C.c_int64(max_g),
+                                         C.c_int64(max_h), C.c_int64(cells)))
+
+
+def _hota_calls(lib, g_ntraj, h_ntraj, max_boxes, limit):
+    """Consecutive result sets per call: as many as fit the workspace limit, at least one.  max_boxes: the bound of the whole
+    input (a smaller per-call bound would only shrink the workspace)."""
+    K, n_streams, n_classes = h_ntraj.shape
+    cells = _matrix_cells(g_ntraj, h_ntraj).reshape(K, -1).sum(axis=1)
+    max_g = int(g_ntraj.max()) if g_ntraj.size else 0
+    calls, k0 = [], 0
+    while k0 < K:
+        k1 = k0 + 1
+        while k1 < K:
+            max_h = int(h_ntraj[k0:k1 + 1].max()) if h_ntraj[k0:k1 + 1].size else 0
+            need = _hota_workspace(lib, k1 + 1 - k0, n_streams, n_classes, max_boxes, max_g, max_h, int(cells[k0:k1 + 1].sum()))
+            if need == 0 or (limit and need > limit):
+                break
+            k1 += 1
+        calls.append((k0, k1))
+        k0 = k1
+    return calls
+
+
+def evaluate_hota(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, workspace_limit_bytes=DEFAULT_WORKSPACE_LIMIT,
+                  packed=None):
+    """HOTA / DetA / AssA / LocA of K tracking results against one ground truth through wt_mot_hota_host: as few calls as the
+    workspace limit allows (the results do not depend on the split).  iou_threshold: the class thresholds, used by LEVEL_1's
+    removal rule only.  packed: pack_results() of the same arguments, when the caller has it.  Returns a list of K HotaResult."""
+    lib = _lib.lib()
+    thr = _lib.as_f64(iou_threshold)
+    n_classes = int(thr.size)
+    p = packed if packed is not None else pack_results(gt, tracks_list, n_classes)
+    g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, p, n_classes)
+    K = len(tracks_list)
+    n_streams = len(gt['stream_keys'])
+    hota_counts = np.zeros((K, n_streams, n_classes, 2, 2 + N_ALPHAS), np.int64)
+    hota_sums = np.zeros((K, n_streams, n_classes, 2, N_ALPHAS, 4), np.float64)
+    set_rows = p['set_row_offsets']
+    hyp_match = np.full((int(set_rows[-1]), 2), -2, np.int64)
+    g_ntraj_c = np.ascontiguousarray(g_ntraj)
+    for k0, k1 in _hota_calls(lib, g_ntraj, h_ntraj, max_frame_boxes(gt, p, n_classes), workspace_limit_bytes):
+        lo, hi = int(set_rows[k0]), int(set_rows[k1])
+        h = dict((n, p[n][lo:hi]) for n in _BOX + ('category',))
+        h['set_row_offsets'] = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
+        h['frame_hyp_offsets'] = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
+        hn = np.ascontiguousarray(h_ntraj[k0:k1])
+        cnt = np.zeros((k1 - k0,) + hota_counts.shape[1:], np.int64)
+        sums = np.zeros((k1 - k0,) + hota_sums.shape[1:], np.float64)
+        match = np.full((hi - lo, 2), -2, np.int64)
+        rc = lib.wt_mot_hota_host(
+            *_gt_args(gt, gt, g_traj, _lib.ptr), *_hyp_args(k1 - k0, None, h, h_traj[lo:hi], _lib.ptr),
+            _lib.ptr(g_ntraj_c), _lib.ptr(hn),
+            C.c_int32(n_classes), _lib.ptr(thr), C.c_size_t(int(workspace_limit_bytes or 0)), _lib.ptr(cnt), _lib.ptr(sums),
+            _lib.ptr(match) if per_row else None)
+        _lib.check(rc, 'wt_mot_hota_host')
+        hota_counts[k0:k1] = cnt
+        hota_sums[k0:k1] = sums
+        hyp_match[lo:hi] = match
+    return _hota_results(gt, p, hota_counts, hota_sums, hyp_match, per_row)
+
+
+class DeviceHota(_DeviceForm):
+    """evaluate_hota with everything resident in HBM, beside DeviceEvaluation and DeviceIdentity: ``launch()`` enqueues one
+    wt_mot_hota_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.  All K
+    results go into one call; workspace_bytes overrides the size of the workspace tensor (a smaller one is refused by the library)."""
+    name = 'wt_mot_hota_dev'
+
+    def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, workspace_bytes=None):
+        _DeviceForm.__init__(self, gt, tracks_list, iou_threshold)
+        torch = self.torch
+        g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, self.p, self.n_classes)
+        self.g_ntraj, self.h_ntraj = g_ntraj, h_ntraj
+        self.max_boxes = max_frame_boxes(gt, self.p, self.n_classes)
+        self.max_g = int(g_ntraj.max()) if g_ntraj.size else 0
+        self.max_h = int(h_ntraj.max()) if h_ntraj.size else 0
+        mat_offsets = np.concatenate([[0], np.cumsum(_matrix_cells(g_ntraj, h_ntraj).reshape(-1))]).astype(np.int64)
+        self.matrix_cells = int(mat_offsets[-1])
+        self.ws_bytes = _hota_workspace(self.lib, self.K, self.n_streams, self.n_classes, self.max_boxes, self.max_g, self.max_h, self.matrix_cells)
+        if not self.ws_bytes:
+            _lib.check(4, 'wt_mot_hota_workspace')
+        self.g['traj'], self.h['traj'] = self.up(g_traj), self.up(h_traj)
+        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = self.up(g_ntraj), self.up(h_ntraj), self.up(mat_offsets)
+        self.hota_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 2 + N_ALPHAS), torch.int64)
+        self.hota_sums = self.zeros((self.K, self.n_streams, self.n_classes, 2, N_ALPHAS, 4), torch.float64)
+        self.hyp_match = self.zeros((max(1, self.n_hyp), 2), torch.int64)
+        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
+
+    def launch(self):
+        d = self.d
+        rc = self.lib.wt_mot_hota_dev(
+            *self.leading_args(self.g['traj'], self.h['traj']),
+            d(self.g['ntraj']), d(self.h['ntraj']), d(self.mat_offsets), C.c_int64(self.matrix_cells),
+            C.c_int32(self.n_classes), _lib.ptr(self.thr), C.c_int64(self.max_boxes), C.c_int64(self.max_g), C.c_int64(self.max_h),
+            d(self.hota_counts), d(self.hota_sums), d(self.hyp_match), d(self.status),
+            d(self.ws), C.c_size_t(int(self.ws.numel())), C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, self.name)
+
+    def results(self, per_row=False):
+        self.wait()
+        return _hota_results(self.gt, self.p, self.hota_counts.cpu().numpy(), self.hota_sums.cpu().numpy(),
+                             self.hyp_match.cpu().numpy()[:self.n_hyp], per_row)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # threshold sweep
 def _grid_values(text):
     """'0.5:1.0:0.05' (inclusive range) or '0.0,0.01,0.1' -> list of floats."""
@@ -639,7 +846,7 @@ def _grid_values(text):
     return [float(v) for v in text.split(',')]
 
 
-def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota'):
+def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False):
     """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
 
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
@@ -652,6 +859,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     rank_by='idf1' (implies identity): per (max_age, min_hits) each class takes the grid point with its own highest class IDF1, the
     combined row reports ALL from the summed identity counts and the rows are ranked by it (this is not the
     argmax of ALL IDF1 over one shared grid point - hyp varies with the setting, and per-class flags can only be tuned per class).
+    hota=True scores every setting with evaluate_hota as well and adds 'HOTA', 'DetA', 'AssA', 'LocA' (with 'hota_counts') to every
+    ranked setting.  rank_by='hota' (implies hota): per (max_age, min_hits) each class takes the grid point with its own highest class
+    HOTA, ties going to grid order; the combined row reports ALL from the added counts and sums and the rows are ranked by its HOTA
+    (DESIGN.md section 19).
     Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}}."""
     if isinstance(gt, str):
         gt = load_ground_truth(gt)
@@ -676,13 +887,15 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                     out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
                     settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)})
                     tracks.append(tracks_from_packed(packed, out))
-    if rank_by not in ('mota', 'idf1'):
-        raise ValueError("rank_by must be 'mota' or 'idf1'")
+    if rank_by not in ('mota', 'idf1', 'hota'):
+        raise ValueError("rank_by must be 'mota', 'idf1' or 'hota'")
     identity = identity or rank_by == 'idf1'
+    hota = hota or rank_by == 'hota'
     packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for both metrics
     results = evaluate_tracks(gt, tracks, iou_threshold, packed=packed_results)
     id_results = evaluate_identity(gt, tracks, iou_threshold, packed=packed_results) if identity else None
-    key = 'IDF1' if rank_by == 'idf1' else 'MOTA'
+    hota_results = evaluate_hota(gt, tracks, iou_threshold, packed=packed_results) if hota else None
+    key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
     per_mm = len(grid['score']) * len(grid['iou'])
@@ -691,6 +904,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
             pick, total = {}, dict((f, 0) for f in FIELDS)
             id_total = dict((f, 0) for f in ID_FIELDS)
+            hota_cnt, hota_sum = np.zeros(2 + N_ALPHAS, np.int64), np.zeros((N_ALPHAS, 4), np.float64)
             for c in classes:
                 top = None
                 for k in range(g, g + per_mm):
@@ -698,6 +912,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                     errors = row['fn'] + row['fp'] + row['idsw']       # gt is the same for every setting: fewest errors = highest MOTA
                     if rank_by == 'idf1':                             # highest class IDF1 (NaN = nothing on either side: last)
                         v = id_results[k].table[c][lv]['idf1']
+                        errors = -v if v == v else math.inf
+                    if rank_by == 'hota':                             # highest class HOTA, NaN last
+                        v = hota_results[k].table[c][lv]['HOTA']
                         errors = -v if v == v else math.inf
                     if top is None or errors < top[0]:
                         top = (errors, k)
@@ -707,6 +924,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 if identity:
                     for f in ID_FIELDS:
                         id_total[f] += id_results[top[1]].table[c][lv][f]
+                if hota:                                              # the pick's class row, added class by class
+                    r = hota_results[top[1]].table[c][lv]
+                    hota_cnt += np.asarray([r['gt'], r['hyp']] + r['tp'], np.int64)
+                    hota_sum = hota_sum + np.asarray([r['sums'][n] for n in HOTA_SUMS], np.float64).T
             mota = 1.0 - (total['fn'] + total['fp'] + total['idsw']) / total['gt'] if total['gt'] else math.nan
             score_thr, iou_thr = [1.0] * n_classes, [1.0] * n_classes      # classes that are not evaluated are not tracked
             for c in classes:
@@ -716,12 +937,19 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
             if identity:
                 combos[-1]['IDF1'] = identity_row(id_total['idtp'], id_total['gt'], id_total['hyp'])['idf1']
                 combos[-1]['id_counts'] = id_total
+            if hota:
+                r = hota_row(hota_cnt[0], hota_cnt[1], hota_cnt[2:], hota_sum)
+                combos[-1].update((n, r[n]) for n in ('HOTA', 'DetA', 'AssA', 'LocA'))
+                combos[-1]['hota_counts'] = {'gt': r['gt'], 'hyp': r['hyp'], 'tp': r['tp'],
+                                             'sums': dict((n, hota_sum[:, i].tolist()) for i, n in enumerate(HOTA_SUMS))}
         order = sorted(range(len(combos)), key=lambda i: (-(combos[i][key] if combos[i][key] == combos[i][key] else -math.inf), i))
         ranked[lv] = [combos[i] for i in order]
         best[lv] = ranked[lv][0] if ranked[lv] else None
     out = {'settings': settings, 'results': results, 'ranked': ranked, 'best': best}
     if identity:
         out['id_results'] = id_results
+    if hota:
+        out['hota_results'] = hota_results
     return out
 
 
@@ -753,6 +981,16 @@ def format_identity_table(result, name=''):
     return '\n'.join(lines)
 
 
+def format_hota_table(result, name=''):
+    lines = ['%s  HOTA' % name,
+             '%-6s %-8s %9s %9s %9s %9s %9s %9s %9s %9s %9s %9s' % (('class', 'level') + HOTA_NAMES + ('HOTA(0)', 'LocA(0)'))]
+    for c, rows in result.table.items():
+        for lv in LEVELS:
+            r = rows[lv]
+            lines.append('%-6s LEVEL_%d  ' % (c, lv) + ' '.join('%9.5f' % r[n] for n in HOTA_NAMES + ('HOTA(0)', 'LocA(0)')))
+    return '\n'.join(lines)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('tracks', nargs='*', help='tracking JSON files written by tracking/track.py')
@@ -766,7 +1004,9 @@ def build_parser():
     parser.add_argument('--min-hits', default='0,1')
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
-    parser.add_argument('--rank-by', choices=('mota', 'idf1'), default='mota', help='what the sweep ranks by (idf1 implies --identity)')
+    parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
+    parser.add_argument('--rank-by', choices=('mota', 'idf1', 'hota'), default='mota',
+                        help='what the sweep ranks by (idf1 implies --identity, hota implies --hota)')
     return parser
 
 
@@ -777,20 +1017,22 @@ def main(argv=None):
         grid = {'score': _grid_values(args.score_grid), 'iou': _grid_values(args.iou_grid),
                 'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')]}
         identity = args.identity or args.rank_by == 'idf1'
-        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by)
+        hota = args.hota or args.rank_by == 'hota'
+        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota)
         for lv in LEVELS:
             print('LEVEL_%d: %d settings tracked, best per class combined for each (max_age, min_hits)' % (lv, len(res['settings'])))
             for r in res['ranked'][lv][:args.top]:
-                if identity:
-                    print('  MOTA %9.5f  IDF1 %9.5f  %s' % (r['MOTA'], r['IDF1'], flag_line(r)))
-                else:
-                    print('  MOTA %9.5f  %s' % (r['MOTA'], flag_line(r)))
+                extra = ('  IDF1 %9.5f' % r['IDF1'] if identity else '') + ('  HOTA %9.5f' % r['HOTA'] if hota else '')
+                print('  MOTA %9.5f%s  %s' % (r['MOTA'], extra, flag_line(r)))
         if args.json:
             with open(args.json, 'wt') as fp:
                 doc = {'settings': res['settings'], 'tables': [r.as_json() for r in res['results']],
                        'ranked': dict(('LEVEL_%d' % lv, v) for lv, v in res['ranked'].items())}
                 if identity:
                     doc['identity_tables'] = [r.as_json() for r in res['id_results']]
+                    doc['rank_by'] = args.rank_by
+                if hota:
+                    doc['hota_tables'] = [r.as_json() for r in res['hota_results']]
                     doc['rank_by'] = args.rank_by
                 json.dump(doc, fp)
         if res['best'][2] is not None:
@@ -801,15 +1043,21 @@ def main(argv=None):
     tracks = [load_tracks(p) for p in args.tracks]
     results = evaluate_tracks(gt, tracks, args.iou_threshold)
     id_results = evaluate_identity(gt, tracks, args.iou_threshold) if args.identity else [None] * len(results)
-    for path, r, ir in zip(args.tracks, results, id_results):
+    hota_results = evaluate_hota(gt, tracks, args.iou_threshold) if args.hota else [None] * len(results)
+    for path, r, ir, hr in zip(args.tracks, results, id_results, hota_results):
         print(format_table(r, path))
         if ir is not None:
             print(format_identity_table(ir, path))
+        if hr is not None:
+            print(format_hota_table(hr, path))
     if args.json:
         doc = dict((p, r.as_json()) for p, r in zip(args.tracks, results))
         for p, ir in zip(args.tracks, id_results):
             if ir is not None:
                 doc[p]['identity'] = ir.as_json()['table']
+        for p, hr in zip(args.tracks, hota_results):
+            if hr is not None:
+                doc[p]['hota'] = hr.as_json()['table']
         with open(args.json, 'wt') as fp:
             json.dump(doc, fp)
     return 0
