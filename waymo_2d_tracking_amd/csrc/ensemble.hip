@@ -279,17 +279,26 @@ __device__ void ensemble_fusion_group(const double* __restrict__ in, int n, cons
 
 
 // ---- dependency-free soft-NMS (ensemble path: conf_thresh == 0, 0 <= thr < cut) ---------------------------------
-// With conf_thresh = 0 a box only leaves the list when its score turns NaN / negative, so for finite non-negative
-// scores every box survives and the decay of box j is just the product, in rank order, of the weights of the boxes
-// ranked above it - the weights depend on geometry only.  That removes the per-rank barrier of the serial loop:
+// With conf_thresh = 0 a box only leaves the list when its score turns NaN / negative.  A group is taken here only if
+//   (a) every score is finite and >= 0, and
+//   (b) every box has x2 > x1, y2 > y1 and a finite area > 0, and cut is finite.
+// Proof that no weight is NaN then: for a pair (i above j) the clamped intersection sides are <= j's own sides (rounding is
+// monotone), so 0 <= inter <= area_j and (area_j - inter) + area_i >= area_i > 0: IoU = inter / union is a finite number >= 0
+// (0 if the sum overflows), and (cut - IoU) / (cut - thr) is finite.  So every box survives and the decay of box j is just the
+// product, in rank order, of the weights of the boxes ranked above it - the weights depend on geometry only.  Without (b) the
+// reference's IoU can be 0 / 0 or inf - inf (two zero-area boxes, an area that underflows, overflows or cancels a negative one, a
+// non-finite coordinate): the victim's score turns NaN, it leaves, and every later box sees another list - serial work.
+// That removes the per-rank barrier of the serial loop:
 //   * 256 threads per group rank the boxes by counting and rewrite them in rank order in LDS (killers, read-only);
 //   * victims are walked in x-sorted order, 64 per wavefront, so that a killer overlaps either several lanes of a
 //     wave or none: the cheap interval test + one ballot skips the two float64 divisions for most (killer, chunk)
 //     pairs (a non-overlapping pair has weight clamp(cut/(cut-thr)) == 1 exactly, so skipping is bit-exact);
 //   * no synchronisation inside the main loop.
-// Groups with NaN / negative scores, thr < 0 or conf_thresh > 0 are flagged and handled by the serial kernel.
+// Groups that fail (a) or (b) are flagged and handled by the serial kernel; thr < 0 or cut <= thr never launch this kernel.
 constexpr int kFastThreads = 256;
 constexpr int kFastMaxPerThread = 8;             // n <= 2048
+// v_cmp_class masks: bit 5 -0, 6 +0, 7 +subnormal, 8 +normal
+constexpr int kClassFiniteNonNeg = 0x1e0, kClassFinitePos = 0x180;
 
 __host__ __device__ inline size_t fast_mem_bytes(size_t cap) { return cap * (6 * sizeof(double) + sizeof(int)) + 32; }
 
@@ -329,13 +338,17 @@ __global__ __launch_bounds__(kFastThreads) void softnms_fast_kernel(
                 const double cx = centre ? x : x + w / 2, cy = centre ? y : y + h / 2;
                 const double hx = w * 0.5, hy = h * 0.5;
                 bs[k] = sc; b1[k] = cx - hx; b2[k] = cy - hy; b3[k] = cx + hx; b4[k] = cy + hy;
-                mybad = mybad || !(sc >= 0.) || !(sc - sc == 0.);
+                // (a) score finite and >= 0 (+-0, positive subnormal or normal); (b) width > 0 and the area positive and finite, which
+                // with width > 0 implies height > 0.  One class test each: no NaN, no infinity, no wrong sign passes.
+                const double wd = b3[k] - b1[k];
+                const double ar = wd * (b4[k] - b2[k]);
+                mybad |= !__builtin_amdgcn_class(sc, kClassFiniteNonNeg) | !__builtin_amdgcn_class(ar, kClassFinitePos) | !(wd > 0.);
                 int cnt = 0;
                 for (int j = 0; j < n; ++j) cnt += before(ks[j], j, sc, i) ? 1 : 0;
                 rk[k] = cnt;
             }
         }
-        if (mybad) bad = 1;
+        if (mybad || !(cut - cut == 0.)) bad = 1;
         __syncthreads();
         if (bad) { if (tid == 0) fallback[g] = 1; __syncthreads(); continue; }
         // 3. rewrite in rank order (all reads of the raw arrays are done)
