@@ -457,6 +457,68 @@ int wt_mot_hota_host(int64_t n_gt, const double* gx, const double* gy, const dou
                      int64_t* hota_counts, double* hota_sums, int64_t* hyp_match);
 
 /* =================================================================================================
+ * Track refinement (length filter, linear gap filling, mean track score; the definition is DESIGN.md section 20)
+ * ================================================================================================= */
+
+/* Refines R >= 1 tracking results under J jobs: job j names a result, job_result[j], and its parameters, and yields a result of
+ * its own.  One wavefront per (job, stream) walks the stream's frame slots twice: the first walk links every row to the next
+ * observation of its trajectory and counts, the second emits.  A trajectory = the rows of one (result, stream) with the same
+ * local index; its class is the category of its first observation.  A trajectory with fewer than min_len[class] observations is
+ * removed; between two consecutive observations n slots apart, 2 <= n <= max_gap[class] + 1, one row is added at each slot in
+ * between with x, y, w, h, score = va + (vb - va) * ((double)j / (double)n), every operation rounded on its own in float64, and
+ * the category of the earlier one; with score_mode 1 every row of a trajectory carries the mean of its observed scores, added
+ * one by one in slot order and divided by their count (0: observed rows keep theirs).
+ *
+ * Results: the R sets concatenated, SoA - x, y, w, h, score float64, category int32 in 1..n_classes, local int32 = the row's
+ * trajectory numbered densely per (result, stream) - set r owning rows set_row_offsets[r] .. set_row_offsets[r + 1], sorted by
+ * frame slot, with frame_row_offsets[r * (n_frames + 1) + f] their offsets inside the set (rows behind the last offset take no
+ * part) and stream_frame_offsets (n_streams + 1) the slots of each stream.  A trajectory occurs at most once per slot.
+ * The host form takes n_traj (R, n_streams) int32, the trajectory counts; the device forms take their running sum traj_offsets
+ * (R * n_streams + 1) int64 with n_traj_total = its last entry and max_traj = an upper bound of the counts.
+ * Jobs: job_result (J) int32, job_max_gap and job_min_len (J, n_classes) int32 (>= 0 and >= 1), job_score_mode (J) int32.
+ * Outputs, job after job, inside a job slot after slot, inside a slot the surviving input rows in input order, then the added
+ * rows in ascending local index: out_frame int64 (slot), out_category, out_bbox (n, 4) = x, y, w, h, out_score, out_local,
+ * out_source int64 = the row's index inside its result, or -1 - (index of the gap's later observation) for an added row;
+ * job_row_offsets (J + 1) int64 = the rows of each job; out_frame_row_offsets (J, n_frames + 1) int64 = the slot offsets inside
+ * each job, the frame_hyp_offsets wt_mot_*_dev takes.  max_gap 0, min_len 1, score_mode 0 reproduces the input.
+ *
+ * wt_refine_tracks_plan_dev links, counts and scans: device pointers, stream-ordered, no allocation, no synchronisation; it
+ * writes job_row_offsets (device) and reports in status_dev (device int32) 0 or WT_ERR_CAPACITY (counts, indices or offsets that
+ * do not fit the rows).  wt_refine_tracks_emit_dev writes the rows, given the same arguments and the workspace the plan left; it
+ * waits for the stream once, to read the planned size: out_cap below it is WT_ERR_CAPACITY and nothing is launched.  A workspace
+ * smaller than wt_refine_tracks_workspace() says is WT_ERR_INVALID.  The device forms do not check the layout; the host form does
+ * (WT_ERR_INVALID names the result and the row or frame slot), stages, plans and emits; with out_cap = 0 it only plans and
+ * returns job_row_offsets (the output pointers may then be NULL): the sizing call.
+ * wt_refine_tracks_limits: the trajectory count of one (result, stream) up to which the per-trajectory tables stay in LDS;
+ * above it they live in the workspace. */
+void wt_refine_tracks_limits(int32_t* lds_trajectories);
+size_t wt_refine_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_refine_tracks_plan_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                              int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                              const double* score, const int32_t* category, const int32_t* local,
+                              const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                              int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_gap, const int32_t* job_min_len, int32_t n_classes,
+                              int64_t* job_row_offsets, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_refine_tracks_emit_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                              int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                              const double* x, const double* y, const double* w, const double* h, const double* score,
+                              const int32_t* category, const int32_t* local,
+                              const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                              int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_gap, const int32_t* job_min_len,
+                              const int32_t* job_score_mode, int32_t n_classes, const int64_t* job_row_offsets, int64_t out_cap,
+                              int64_t* out_frame, int32_t* out_category, double* out_bbox, double* out_score, int32_t* out_local,
+                              int64_t* out_source, int64_t* out_frame_row_offsets,
+                              int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_refine_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                          int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                          const double* x, const double* y, const double* w, const double* h, const double* score,
+                          const int32_t* category, const int32_t* local, const int32_t* n_traj,
+                          int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_gap, const int32_t* job_min_len,
+                          const int32_t* job_score_mode, int32_t n_classes, int64_t out_cap,
+                          int64_t* out_frame, int32_t* out_category, double* out_bbox, double* out_score, int32_t* out_local,
+                          int64_t* out_source, int64_t* out_frame_row_offsets, int64_t* job_row_offsets);
+
+/* =================================================================================================
  * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

@@ -1,0 +1,70 @@
+// The layout checks of wt_refine_tracks_host (csrc/refine_host.h) as a program of their own, for a host sanitizer:
+//
+//     hipcc -Xarch_host -fsanitize=address,undefined -g -O1 tools/refine_layout_check.cpp -o refine_layout_check && ./refine_layout_check
+//
+// It feeds check_refine_layout one valid layout and the malformed ones the entry point must refuse, prints what each gave and
+// returns 0 when every answer is the expected one.  No device is touched.
+#include "../waymo_2d_tracking_amd/csrc/refine_host.h"
+
+#include <string>
+
+namespace wt {
+static char g_error[512];
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+}
+int hip_fail(hipError_t, const char* what) { set_error("%s", what); return WT_ERR_HIP; }
+}  // namespace wt
+
+namespace {
+
+struct Case {                                   // two results over two streams (3 + 2 slots), two jobs, four classes
+    std::vector<int64_t> sfo = {0, 3, 5}, sro = {0, 5, 7};
+    std::vector<int64_t> fro = {0, 2, 2, 3, 5, 5, /* result 1 */ 0, 0, 1, 1, 1, 2};
+    std::vector<double> v = {1, 2, 3, 4, 5, 6, 7};
+    std::vector<int32_t> cat = {1, 2, 1, 4, 1, 3, 3}, local = {0, 1, 0, 0, 1, 0, 0}, n_traj = {2, 2, 1, 1};
+    std::vector<int32_t> job_result = {0, 1}, gap = {0, 1, 2, 3, 0, 0, 0, 0}, len = {1, 1, 2, 2, 1, 1, 1, 1}, mode = {0, 1};
+    wt::RefineInput in() const {
+        return {5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), v.data(), cat.data(), local.data(),
+                n_traj.data(), 2, job_result.data(), gap.data(), len.data(), mode.data(), 4};
+    }
+};
+
+int failures = 0;
+
+void expect(const char* name, const Case& c, int want, const char* text) {
+    int64_t max_traj = -1, total = -1;
+    wt::g_error[0] = 0;
+    const int rc = wt::check_refine_layout(c.in(), &max_traj, &total);
+    const bool ok = rc == want && (want == WT_OK ? (max_traj == 2 && total == 6) : std::string(wt::g_error).find(text) != std::string::npos);
+    printf("%-28s rc %d  %s%s\n", name, rc, wt::g_error, ok ? "" : "   <-- UNEXPECTED");
+    failures += !ok;
+}
+
+}  // namespace
+
+int main() {
+    Case c;
+    expect("valid", c, WT_OK, "");
+    { Case d; d.fro[2] = 1; expect("frames not sorted", d, WT_ERR_INVALID, "non-decreasing"); }
+    { Case d; d.fro[11] = 3; expect("offsets beyond the rows", d, WT_ERR_INVALID, "do not fit its rows"); }
+    { Case d; d.fro[6] = 1; expect("first offset not 0", d, WT_ERR_INVALID, "do not fit its rows"); }
+    { Case d; d.sfo[2] = 4; expect("streams do not cover", d, WT_ERR_INVALID, "do not cover"); }
+    { Case d; d.sfo[1] = 6; expect("stream offsets descend", d, WT_ERR_INVALID, "non-decreasing"); }
+    { Case d; d.cat[3] = 5; expect("class above n_classes", d, WT_ERR_INVALID, "category 5 outside"); }
+    { Case d; d.cat[6] = 0; expect("class 0", d, WT_ERR_INVALID, "category 0 outside"); }
+    { Case d; d.local[1] = 0; expect("duplicate in a slot", d, WT_ERR_INVALID, "trajectory 0 occurs twice in frame 0"); }
+    { Case d; d.local[4] = 2; expect("local index = count", d, WT_ERR_INVALID, "trajectory index 2 outside"); }
+    { Case d; d.local[5] = -1; expect("negative local index", d, WT_ERR_INVALID, "trajectory index -1 outside"); }
+    { Case d; d.n_traj[3] = -1; expect("negative trajectory count", d, WT_ERR_INVALID, "negative trajectory count"); }
+    { Case d; d.job_result[1] = 2; expect("job names no result", d, WT_ERR_INVALID, "result 2 outside"); }
+    { Case d; d.gap[5] = -1; expect("negative max_gap", d, WT_ERR_INVALID, "max_gap of class 2"); }
+    { Case d; d.len[0] = 0; expect("min_len 0", d, WT_ERR_INVALID, "min_len of class 1"); }
+    { Case d; d.mode[0] = 2; expect("unknown score mode", d, WT_ERR_INVALID, "score_mode"); }
+    { Case d; d.n_traj = {0, 0, 0, 0}; expect("no trajectories declared", d, WT_ERR_INVALID, "trajectory index 0 outside"); }
+    printf("%d unexpected\n", failures);
+    return failures ? 1 : 0;
+}

@@ -32,7 +32,8 @@ UNITS = {
     'mot_eval.hip': ['-ffp-contract=off'],             # CLEAR-MOT evaluation: float64 IoU in the reference's operation order
     'mot_identity.hip': ['-ffp-contract=off'],         # IDF1 / IDP / IDR: the same float64 IoU, trajectory overlap counts and one global assignment
     'mot_hota.hip': ['-ffp-contract=off'],             # HOTA: the same float64 IoU, float64 alignment scores, one assignment per frame for 19 thresholds
-    'det_eval.hip': ['-ffp-contract=off'],             # detection AP: float64 IoU / precision / recall rounded operation by operation
+    'track_refine.hip': ['-ffp-contract=off'],         # track refinement: a fill is va + (vb - va) * (j / n), every operation rounded on its own
+    'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_roialign.hip': [],
     'det_nms.hip': [],
     'det_deform.hip': [],

@@ -74,4 +74,10 @@ __device__ __forceinline__ void decode_problem(size_t p, int n_streams, int C, i
     *c = (int)(p % C) + 1;
 }
 
+// block p = (job j, stream s), the stream fastest (track_refine.hip)
+__device__ __forceinline__ void decode_job_stream(size_t p, int n_streams, int* j, int* s) {
+    *j = (int)(p / (size_t)n_streams);
+    *s = (int)(p % (size_t)n_streams);
+}
+
 }  // namespace wtdev

@@ -3,7 +3,7 @@
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
         [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--identity] [--hota] [--rank-by idf1|hota]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
@@ -850,7 +850,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
 
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
-    and 'min_hits'.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
+    and 'min_hits', and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
+    tracked result is refined under all (gap, min_len) pairs in one call, the pairs are the innermost axes of `settings`, and the
+    per-class pick ranges over them too - refinement is per trajectory with per-class parameters, so it stays valid.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
     thresholds and on (max_age, min_hits): every tracked setting uses ONE (score, iou) grid point for all classes -
     K = |score| x |iou| x |max_age| x |min_hits| settings - and the best point is read off per class for each
     (max_age, min_hits); no product over classes is tracked.  Best = highest ALL MOTA at the level; ties go to the setting that
@@ -880,11 +882,21 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
         bucket.append({'bbox': bbox, 'score': entry['score'] if 'score' in entry else 1.0, 'category_id': entry['category_id']})
     packed = T.pack_streams(entries)
     settings, tracks = [], []
+    gaps, lens = [int(v) for v in grid.get('gap', [0])], [int(v) for v in grid.get('min_len', [1])]
+    refining = gaps != [0] or lens != [1]           # the two innermost axes: one tracked result refined under every (gap, length)
+    jobs = [{'max_gap': g, 'min_len': n} for g in gaps for n in lens]
     for max_age in grid['max_age']:
         for min_hits in grid['min_hits']:
             for score in grid['score']:
                 for iou in grid['iou']:
                     out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
+                    if refining:
+                        from .refine import refine_tracks
+                        for job, refined in zip(jobs, refine_tracks(packed, [out], jobs, n_classes)):
+                            settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou),
+                                             'interp_gap': job['max_gap'], 'min_len': job['min_len']})
+                            tracks.append(tracks_from_packed(packed, refined))
+                        continue
                     settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)})
                     tracks.append(tracks_from_packed(packed, out))
     if rank_by not in ('mota', 'idf1', 'hota'):
@@ -898,7 +910,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou'])
+    per_mm = len(grid['score']) * len(grid['iou']) * len(jobs)
     for lv in LEVELS:
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
@@ -934,6 +946,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 score_thr[c - 1], iou_thr[c - 1] = settings[pick[c]]['score'], settings[pick[c]]['iou']
             combos.append({'max_age': settings[g]['max_age'], 'min_hits': settings[g]['min_hits'], 'score_threshold': score_thr,
                            'iou_threshold': iou_thr, 'MOTA': mota, 'counts': total})
+            if refining:                                              # classes that are not evaluated are not refined either
+                combos[-1]['interp_gap'], combos[-1]['min_len'] = [0] * n_classes, [1] * n_classes
+                for c in classes:
+                    combos[-1]['interp_gap'][c - 1], combos[-1]['min_len'][c - 1] = settings[pick[c]]['interp_gap'], settings[pick[c]]['min_len']
             if identity:
                 combos[-1]['IDF1'] = identity_row(id_total['idtp'], id_total['gt'], id_total['hyp'])['idf1']
                 combos[-1]['id_counts'] = id_total
@@ -956,8 +972,12 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
 def flag_line(setting):
     """The tracking/track.py flags of a sweep result."""
     join = lambda v: ','.join(repr(float(x)) for x in v)
-    return '--score-threshold=%s --iou-threshold=%s --max-age=%d --min-hits=%d' % (
+    line = '--score-threshold=%s --iou-threshold=%s --max-age=%d --min-hits=%d' % (
         join(setting['score_threshold']), join(setting['iou_threshold']), setting['max_age'], setting['min_hits'])
+    if 'interp_gap' in setting:
+        line += ' --interpolate-gap=%s --min-track-len=%s' % (','.join('%d' % v for v in setting['interp_gap']),
+                                                              ','.join('%d' % v for v in setting['min_len']))
+    return line
 
 
 def format_table(result, name=''):
@@ -1002,6 +1022,8 @@ def build_parser():
     parser.add_argument('--iou-grid', default='0.0,0.01,0.1,0.3')
     parser.add_argument('--max-age', default='1,2,3')
     parser.add_argument('--min-hits', default='0,1')
+    parser.add_argument('--gap-grid', default='0', help='track refinement: gaps of up to this many frames are interpolated (tracking/refine.py)')
+    parser.add_argument('--min-len-grid', default='1', help='track refinement: tracks observed in fewer frames are dropped')
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
     parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
@@ -1015,7 +1037,8 @@ def main(argv=None):
     gt = load_ground_truth(args.annotations)
     if args.sweep:
         grid = {'score': _grid_values(args.score_grid), 'iou': _grid_values(args.iou_grid),
-                'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')]}
+                'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')],
+                'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')]}
         identity = args.identity or args.rank_by == 'idf1'
         hota = args.hota or args.rank_by == 'hota'
         res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota)

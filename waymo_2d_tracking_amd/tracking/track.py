@@ -20,6 +20,10 @@ def _floats(s):
     return [float(item) for item in s.split(',')]
 
 
+def _ints(s):
+    return [int(item) for item in s.split(',')]
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("--ground-truth", type=str, default='/data/waymo/det2d/validation/images.json',
@@ -33,10 +37,28 @@ def build_parser():
                         help='score threshold to track')
     parser.add_argument("--iou-threshold", type=_floats, default=[0.01, 0.01, 1.0, 0.0],
                         help='IOU threshold for tracking')
+    parser.add_argument("--interpolate-gap", type=_ints, default=[0],
+                        help='fill gaps of up to this many frames inside a track by linear interpolation (one value, or one per class)')
+    parser.add_argument("--min-track-len", type=_ints, default=[1],
+                        help='drop tracks observed in fewer frames than this (one value, or one per class)')
+    parser.add_argument("--track-score", choices=('keep', 'mean'), default='keep',
+                        help='mean: every box of a track carries the mean score of its observed boxes')
     parser.add_argument("--segment-id", type=str, help='track only a single segment')
     parser.add_argument("--python-io", action='store_true',
                         help='parse / write JSON with the Python json module (default: native reader / writer of libwaymotrack)')
     return parser
+
+
+def refines(args):
+    """Whether the flags ask for any refinement (tracking/refine.py); with the defaults the output is the tracker's own."""
+    return max(args.interpolate_gap) > 0 or max(args.min_track_len) > 1 or args.track_score != 'keep'
+
+
+def refined(args, packed, out):
+    if not refines(args):
+        return out
+    from .refine import refine_one
+    return refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, len(args.iou_threshold))
 
 
 def main_native(args):
@@ -50,7 +72,7 @@ def main_native(args):
     out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
     T._GLOBAL_IDS['next'] += births
     print("duration: %.2fs" % (time.time() - start_time))
-    nat.write_tracks(args.output, out)
+    nat.write_tracks(args.output, refined(args, packed, out))
     nat.close()
     return 0
 
@@ -79,6 +101,7 @@ def main_sharded(args, world, rank):
     T._GLOBAL_IDS['next'] += births
     if rank == 0:
         print("duration: %.2fs" % (time.time() - start_time))
+        cols = refined(args, packed, cols)
         if args.segment_id:
             with open(args.output, 'wt') as fp:
                 json.dump(T.format_tracks(packed, cols), fp)
@@ -105,7 +128,14 @@ def main(argv=None):
     start_time = time.time()
     for segment_id in predictions.keys():
         print(segment_id)
-    tracked_predictions = track_all(predictions, args.iou_threshold, args.max_age, args.min_hits)
+    if refines(args):
+        from . import utils as T
+        packed = T.pack_streams(predictions)
+        out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
+        T._GLOBAL_IDS['next'] += births
+        tracked_predictions = T.format_tracks(packed, refined(args, packed, out))
+    else:
+        tracked_predictions = track_all(predictions, args.iou_threshold, args.max_age, args.min_hits)
     print("duration: %.2fs" % (time.time() - start_time))
     with open(args.output, 'wt') as fp:
         json.dump(tracked_predictions, fp)
