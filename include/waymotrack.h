@@ -519,6 +519,51 @@ int wt_refine_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                           int64_t* out_source, int64_t* out_frame_row_offsets, int64_t* job_row_offsets);
 
 /* =================================================================================================
+ * Track stitching (the second association pass: tracklets linked across gaps; the definition is DESIGN.md section 21)
+ * ================================================================================================= */
+
+/* Stitches R >= 1 tracking results under J jobs: job j names a result, job_result[j], and its parameters.  Results, trajectories
+ * and local indices are those of the track refinement above, with one more requirement: the local indices of a (result, stream)
+ * number its trajectories by first appearance, none missing.  Tail i (last observation at slot e, box x, y, w, h; the one before
+ * at slot p) and head j of the same stream and class (first observation at slot s) are a candidate when n = s - e lies in
+ * 1..max_link[class] and the affinity a satisfies a >= link_iou[class] and a > 0 (a NaN never does).  a = iou_dd of
+ * [px, py, px + w, py + h] and the head's first box, with px = x + ((x - x_p) / (double)(e - p)) * (double)n, py alike, when
+ * motion is 1 (linear) and the tail has two observations, and px = x, py = y otherwise (motion 0 = hold); every operation rounded
+ * on its own in float64.  The candidates are walked in the strict order (-a, n, i, j) and one is accepted when i is not yet a tail
+ * and j not yet a head: the links form chains, and every row takes the identity of its chain's earliest trajectory (the root).
+ *
+ * Jobs: job_result (J) int32, job_max_link (J, n_classes) int32 >= 0 (0: the class is never linked), job_link_iou (J, n_classes)
+ * float64 not NaN, job_motion (J) int32.
+ * Outputs, sized up front: out_pred, out_root (J, n_traj_total) int32 and out_affinity (J, n_traj_total) float64, indexed like
+ * traj_offsets - the local index linked into the trajectory or -1, its root's local index, the accepted link's a or -1.0;
+ * out_row_root (J, n_rows) int32 = per row of the job's result the root's local index; out_links (J, n_streams) int64 = the links
+ * made.  Entries of results the job does not name are -1 (-1.0).  A job whose max_link is all 0 has pred -1 and root = the index.
+ *
+ * wt_stitch_tracks_dev: device pointers, stream-ordered, no allocation, no synchronisation; it reports in status_dev (device
+ * int32) 0 or WT_ERR_CAPACITY (counts, indices or offsets that do not fit the rows).  A workspace smaller than
+ * wt_stitch_tracks_workspace() says is WT_ERR_CAPACITY.  The device form does not check the layout; the host form does
+ * (WT_ERR_INVALID names the result and the row or frame slot, or the job), stages and launches; it takes n_traj (R, n_streams)
+ * int32 where the device form takes the running sum traj_offsets, n_traj_total and max_traj.
+ * wt_stitch_tracks_limits: the trajectory count of one (result, stream) up to which the tables of the matching stay in LDS;
+ * above it they live in the workspace. */
+void wt_stitch_tracks_limits(int32_t* lds_trajectories);
+size_t wt_stitch_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_stitch_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                         const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                         int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_link, const double* job_link_iou,
+                         const int32_t* job_motion, int32_t n_classes,
+                         int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_row_root, int64_t* out_links,
+                         int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_stitch_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                          int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                          const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                          const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_link,
+                          const double* job_link_iou, const int32_t* job_motion, int32_t n_classes,
+                          int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_row_root, int64_t* out_links);
+
+/* =================================================================================================
  * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

@@ -1,0 +1,454 @@
+// Track stitching on gfx950 (include/waymotrack.h, "Track stitching"; DESIGN.md section 21 has the definition): the second
+// association pass.  A trajectory that ends (tail) is linked to one of the same stream and class that begins up to max_link slots
+// later (head) when the tail's extrapolated box overlaps the head's first box; the linked pieces take the id of the earliest one.
+// R tracking results come in once; J jobs each name a result and their parameters.  No row is added, removed or moved.
+//
+// Two launches, one 64-lane wavefront per independent problem:
+//   1. summary: per (result, stream), walk the slots once: per trajectory the first slot and row, the last slot and row, the slot
+//               and row before the last, and the class.  Shared by all jobs of the result.
+//   2. match:   per (job, stream).  The answer is the greedy walk of all candidate pairs in the strict order (-a, n, i, j); it is
+//               computed in rounds of locally dominant pairs, without a table of pairs: a lane owns a free tail and scans its heads -
+//               local indices are by first appearance, so the heads whose first slot lies in [e + 1, e + max_link] are a contiguous
+//               range found by two binary searches.  Scan A gives every head the highest affinity any free tail offers it (64-bit
+//               atomic max on the bits of a positive double) and every tail its best head; scan B gives every head the smallest
+//               (n, i) among the tails that offer exactly that affinity; a pair that is its tail's best and its head's best is
+//               accepted.  The smallest free pair always is one, so a round without an acceptance ends the matching.  The same
+//               wavefront then resolves the roots, counts the links and labels its rows.
+// The tables of the match (36 bytes per trajectory) live in LDS up to kLdsTraj trajectories, in the workspace beyond.
+// Compile with -ffp-contract=off: the extrapolation is x + ((x - xp) / (e - p)) * n with every operation rounded on its own, and
+// iou_dd is the IoU the metrics use.
+#include "eval_device.h"
+#include "eval_host.h"
+#include "stitch_host.h"
+
+using namespace wtdev;
+
+namespace {
+
+constexpr int kLdsTraj = 1024;                // trajectories of one (result, stream) up to which the match tables stay in LDS
+constexpr int kTableBytes = 36;               // per trajectory: two uint64, one double, three int32
+
+struct Layout {                               // device pointers
+    long long n_frames, n_rows, n_traj_total, max_traj;
+    int n_streams, r_sets, n_jobs, n_classes, lds_traj;
+    const int64_t *stream_frame_offsets, *set_row_offsets, *frame_row_offsets, *traj_offsets;
+    const int32_t *category, *local;
+    const int32_t *job_result, *job_max_link, *job_motion;
+    const double* job_link_iou;
+};
+
+struct Summary {                              // [n_traj_total] each; slots relative to the stream's first, rows to the stream's first row; -1 none
+    int32_t *first_slot, *first_row, *last_slot, *last_row, *prev_slot, *prev_row, *cls;
+};
+
+struct Workspace {
+    Summary sum;
+    unsigned long long *head_a, *head_k;      // [J * n_traj_total] the tables of the problems above kLdsTraj (all five)
+    double* tail_a;
+    int32_t *tail_j, *succ, *pred;
+    size_t bytes;
+};
+
+Workspace carve(void* base, size_t n_jobs, size_t n_traj_total, size_t max_traj) {
+    wt::Carver cv(base);
+    Workspace w;
+    const size_t big = max_traj > (size_t)kLdsTraj ? n_jobs * n_traj_total : 0;
+    int32_t** cols[7] = {&w.sum.first_slot, &w.sum.first_row, &w.sum.last_slot, &w.sum.last_row, &w.sum.prev_slot, &w.sum.prev_row, &w.sum.cls};
+    for (auto c : cols) *c = cv.take<int32_t>(n_traj_total + 1);
+    w.head_a = cv.take<unsigned long long>(big + 1);
+    w.head_k = cv.take<unsigned long long>(big + 1);
+    w.tail_a = cv.take<double>(big + 1);
+    w.tail_j = cv.take<int32_t>(big + 1);
+    w.succ = cv.take<int32_t>(big + 1);
+    w.pred = cv.take<int32_t>(big + 1);
+    w.bytes = cv.off;
+    return w;
+}
+
+// The rows and trajectories of one (result r, stream s).  ok = false: the caller's numbers do not fit (status).
+struct Span {
+    int T;
+    long long f0, f1, base, rend, rs0, t0;
+    const int64_t* fro;
+    bool ok;
+};
+
+__device__ __forceinline__ Span span_of(const Layout& L, int r, int s) {
+    Span q;
+    q.ok = r >= 0 && r < L.r_sets;
+    if (!q.ok) return q;
+    const size_t rs = (size_t)r * L.n_streams + s;
+    const long long t0 = L.traj_offsets[rs], t1 = L.traj_offsets[rs + 1];
+    q.f0 = L.stream_frame_offsets[s];
+    q.f1 = L.stream_frame_offsets[s + 1];
+    q.base = L.set_row_offsets[r];
+    q.rend = L.set_row_offsets[r + 1];
+    q.fro = L.frame_row_offsets + (size_t)r * (size_t)(L.n_frames + 1);
+    q.ok = t0 >= 0 && t1 >= t0 && t1 - t0 <= L.max_traj && t1 <= L.n_traj_total && q.f0 >= 0 && q.f1 >= q.f0 && q.f1 <= L.n_frames &&
+           q.f1 - q.f0 < 0x3fffffffll && q.base >= 0 && q.rend >= q.base && q.rend <= L.n_rows;
+    if (!q.ok) return q;
+    q.T = (int)(t1 - t0);
+    q.t0 = t0;
+    q.rs0 = q.f1 > q.f0 ? q.base + q.fro[q.f0] : q.base;
+    q.ok = q.rs0 >= q.base && q.rs0 <= q.rend;
+    return q;
+}
+
+// rows [r0, r1) of slot f, or false when they leave the result's rows
+__device__ __forceinline__ bool slot_rows(const Span& q, long long f, long long* r0, long long* r1) {
+    *r0 = q.base + q.fro[f];
+    *r1 = q.base + q.fro[f + 1];
+    return *r0 >= q.rs0 && *r1 >= *r0 && *r1 <= q.rend && *r1 - q.rs0 < 0x7fffffffll;
+}
+
+__global__ __launch_bounds__(kWave) void stitch_summary_kernel(Layout L, Summary S, int* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int r = (int)(blockIdx.x / (unsigned)L.n_streams), s = (int)(blockIdx.x % (unsigned)L.n_streams);
+    const Span q = span_of(L, r, s);
+    if (!q.ok) {
+        if (lane == 0) atomicMax(status, kErrCapacity);
+        return;
+    }
+    const int T = q.T;
+    for (int t = lane; t < T; t += kWave) {
+        const size_t g = (size_t)q.t0 + t;
+        S.first_slot[g] = -1; S.first_row[g] = -1; S.last_slot[g] = -1; S.last_row[g] = -1; S.prev_slot[g] = -1; S.prev_row[g] = -1; S.cls[g] = 0;
+    }
+    wsync();
+    int err = 0;
+    for (long long f = q.f0; f < q.f1; ++f) {
+        const int fo = (int)(f - q.f0);
+        long long r0, r1;
+        if (!slot_rows(q, f, &r0, &r1)) { err = kErrCapacity; break; }
+        for (long long b = r0; b < r1; b += kWave) {                  // local indices are unique inside a slot: lanes never collide
+            const long long d = b + lane;
+            if (d >= r1) continue;
+            const int t = L.local[d];
+            if (t < 0 || t >= T) { err = kErrCapacity; continue; }
+            const size_t g = (size_t)q.t0 + t;
+            const int row = (int)(d - q.rs0);
+            if (S.first_slot[g] < 0) { S.first_slot[g] = fo; S.first_row[g] = row; S.cls[g] = L.category[d]; }
+            S.prev_slot[g] = S.last_slot[g];
+            S.prev_row[g] = S.last_row[g];
+            S.last_slot[g] = fo;
+            S.last_row[g] = row;
+        }
+        wsync();
+    }
+    if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
+}
+
+struct Outputs {
+    int32_t *pred, *root;                     // [J * n_traj_total]
+    double* affinity;                         // [J * n_traj_total]
+    int32_t* row_root;                        // [J * n_rows]
+    int64_t* links;                           // [J * n_streams]
+};
+
+// every entry: no link, no root; the match kernel fills those of its job's result
+__global__ void stitch_init_kernel(Outputs O, long long n_traj, long long n_row) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_traj) { O.pred[i] = -1; O.root[i] = -1; O.affinity[i] = -1.0; }
+    if (i < n_row) O.row_root[i] = -1;
+}
+
+// first t in [0, T) with slot[t] >= v (slot is non-decreasing where the local indices are by first appearance); always inside [0, T]
+__device__ __forceinline__ int lower_bound_slot(const int32_t* __restrict__ slot, int T, int v) {
+    int lo = 0, hi = T;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (slot[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The candidate heads of one free tail, in ascending index: visit(j, n, a) for every free head j of the tail's class, n = its gap,
+// a = the affinity, when the pair is a candidate (rule 1 of the definition).
+struct Tail {
+    int e, lo, hi, cls, max_link;
+    double px0, py0, vx, vy, w, h, thr;
+    bool linear;
+};
+
+template <class Visit>
+__device__ __forceinline__ void scan_heads(const Tail& t, const Summary& S, size_t g0, const Boxes& B, long long rs0, long long n_stream_rows,
+                                           const int32_t* pred, Visit visit) {
+    for (int j = t.lo; j < t.hi; ++j) {
+        if (pred[j] >= 0 || S.cls[g0 + j] != t.cls) continue;
+        const int n = S.first_slot[g0 + j] - t.e, fr = S.first_row[g0 + j];
+        if (n < 1 || n > t.max_link || fr < 0 || fr >= n_stream_rows) continue;
+        double px = t.px0, py = t.py0;
+        if (t.linear) { px = t.px0 + t.vx * (double)n; py = t.py0 + t.vy * (double)n; }
+        const double pb[4] = {px, py, px + t.w, py + t.h};
+        double hb[4];
+        B.get(rs0 + fr, hb);
+        const double a = iou_dd(pb, hb);
+        if (a >= t.thr && a > 0.) visit(j, n, a);
+    }
+}
+
+__global__ __launch_bounds__(kWave) void stitch_match_kernel(Layout L, Boxes B, Workspace ws, Outputs O, int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const size_t p = blockIdx.x;
+    int j_, s_;
+    decode_job_stream(p, L.n_streams, &j_, &s_);
+    const int job = j_, s = s_;
+    const Span q = span_of(L, L.job_result[job], s);
+    if (!q.ok) {
+        if (lane == 0) { atomicMax(status, kErrCapacity); O.links[p] = 0; }
+        return;
+    }
+    const int T = q.T, C = L.n_classes;
+    const Summary S = ws.sum;
+    const size_t g0 = (size_t)q.t0;
+    const size_t tbase = (size_t)job * (size_t)L.n_traj_total + g0;
+    const size_t lbase = (size_t)job * (size_t)L.n_rows;
+    const bool in_lds = T <= L.lds_traj;
+    const size_t stride = (size_t)L.lds_traj;
+    unsigned long long* head_a = in_lds ? reinterpret_cast<unsigned long long*>(smem) : ws.head_a + tbase;
+    unsigned long long* head_k = in_lds ? head_a + stride : ws.head_k + tbase;
+    double* tail_a = in_lds ? reinterpret_cast<double*>(head_k + stride) : ws.tail_a + tbase;
+    int32_t* tail_j = in_lds ? reinterpret_cast<int32_t*>(tail_a + stride) : ws.tail_j + tbase;   // after the matching: the root
+    int32_t* succ = in_lds ? tail_j + stride : ws.succ + tbase;                                      // the head linked to this tail, -1 free, -2 no candidate left
+    int32_t* pred = in_lds ? succ + stride : ws.pred + tbase;                                        // the tail linked to this head, -1 free
+    const int32_t* links = L.job_max_link + (size_t)job * C;
+    const double* thrs = L.job_link_iou + (size_t)job * C;
+    const bool linear = L.job_motion[job] == 1;
+    int err = 0;
+    long long stream_end = q.rs0;
+    if (q.f1 > q.f0) {
+        stream_end = q.base + q.fro[q.f1];
+        if (stream_end < q.rs0 || stream_end > q.rend || stream_end - q.rs0 >= 0x7fffffffll) { err = kErrCapacity; stream_end = q.rs0; }
+    }
+    const long long n_stream_rows = stream_end - q.rs0;
+    for (int t = lane; t < T; t += kWave) { succ[t] = -1; pred[t] = -1; }
+    wsync();
+
+    // what a free tail needs for its scans; valid = false: it can never link
+    auto make_tail = [&](int i, Tail* t) {
+        const int c = S.cls[g0 + i];
+        if (c < 1 || c > C) return false;
+        const int max_link = links[c - 1];
+        const int e = S.last_slot[g0 + i], row = S.last_row[g0 + i];
+        if (max_link < 1 || e < 0 || row < 0 || row >= n_stream_rows) return false;
+        t->e = e; t->cls = c; t->max_link = max_link; t->thr = thrs[c - 1];
+        const long long hi_slot = (long long)e + max_link + 1;
+        t->lo = lower_bound_slot(S.first_slot + g0, T, e + 1);
+        t->hi = lower_bound_slot(S.first_slot + g0, T, hi_slot > 0x7fffffffll ? 0x7fffffff : (int)hi_slot);
+        const long long d = q.rs0 + row;
+        t->px0 = B.x[d]; t->py0 = B.y[d]; t->w = B.w[d]; t->h = B.h[d];
+        const int ps = S.prev_slot[g0 + i], prow = S.prev_row[g0 + i];
+        t->linear = linear && ps >= 0 && prow >= 0 && prow < n_stream_rows && e > ps;
+        t->vx = 0.; t->vy = 0.;
+        if (t->linear) {
+            const long long dp = q.rs0 + prow;
+            t->vx = (t->px0 - B.x[dp]) / (double)(e - ps);
+            t->vy = (t->py0 - B.y[dp]) / (double)(e - ps);
+        }
+        return t->lo < t->hi;
+    };
+
+    for (int round = 0; round <= T; ++round) {                         // every round but the last accepts a pair: at most T rounds
+        for (int t = lane; t < T; t += kWave) { head_a[t] = 0ull; head_k[t] = ~0ull; }
+        wsync();
+        // ---- scan A: per head the highest affinity offered, per tail its best head ----
+        for (int ib = 0; ib < T; ib += kWave) {
+            const int i = ib + lane;
+            if (i >= T || succ[i] != -1) continue;
+            Tail t;
+            int bj = -1;
+            double ba = 0.;
+            if (make_tail(i, &t))
+                scan_heads(t, S, g0, B, q.rs0, n_stream_rows, pred, [&](int j, int n, double a) {
+                    atomicMax(&head_a[j], (unsigned long long)__double_as_longlong(a));
+                    if (a > ba) { ba = a; bj = j; }                    // ascending j is ascending n: the first of equal affinities is the best
+                });
+            tail_a[i] = ba;
+            tail_j[i] = bj;
+            if (bj < 0) succ[i] = -2;                                  // the free heads only get fewer
+        }
+        wsync();
+        // ---- scan B: per head the smallest (n, i) among the tails that offer exactly its highest affinity ----
+        for (int ib = 0; ib < T; ib += kWave) {
+            const int i = ib + lane;
+            if (i >= T || succ[i] != -1) continue;
+            Tail t;
+            if (make_tail(i, &t))
+                scan_heads(t, S, g0, B, q.rs0, n_stream_rows, pred, [&](int j, int n, double a) {
+                    if ((unsigned long long)__double_as_longlong(a) == head_a[j])
+                        atomicMin(&head_k[j], ((unsigned long long)(unsigned)n << 32) | (unsigned)i);
+                });
+        }
+        wsync();
+        // ---- accept the pairs that are best on both sides ----
+        bool any = false;
+        for (int ib = 0; ib < T; ib += kWave) {
+            const int i = ib + lane;
+            bool mine = false;
+            if (i < T && succ[i] == -1) {
+                const int j = tail_j[i];
+                const int n = S.first_slot[g0 + j] - S.last_slot[g0 + i];
+                mine = (unsigned long long)__double_as_longlong(tail_a[i]) == head_a[j] &&
+                       head_k[j] == (((unsigned long long)(unsigned)n << 32) | (unsigned)i);
+                if (mine) { succ[i] = j; pred[j] = i; O.affinity[tbase + j] = tail_a[i]; }
+            }
+            any = any || __ballot(mine) != 0ull;
+        }
+        wsync();
+        if (!any) break;
+        if (round == T) err = kErrCapacity;                            // cannot happen: a round that accepts uses up a tail
+    }
+
+    // ---- roots, link count, row labels ----
+    int32_t* root = tail_j;
+    long long n_links = 0;
+    for (int t = lane; t < T; t += kWave) {
+        int r = t, steps = 0;
+        while (pred[r] >= 0 && steps < T) { r = pred[r]; ++steps; }
+        if (pred[r] >= 0) err = kErrCapacity;                          // a cycle: links go forward in time, so there is none
+        root[t] = r;
+        O.pred[tbase + t] = pred[t];
+        O.root[tbase + t] = r;
+        n_links += pred[t] >= 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) n_links += __shfl_xor(n_links, o, kWave);
+    wsync();
+    for (long long d = q.rs0 + lane; d < stream_end; d += kWave) {
+        const int t = L.local[d];
+        if (t < 0 || t >= T) { err = kErrCapacity; continue; }
+        O.row_root[lbase + d] = root[t];
+    }
+    if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
+    if (lane == 0) O.links[p] = n_links;
+}
+
+int check_args(const char* entry, int64_t n_frames, int32_t n_streams, int32_t r_sets, int64_t n_rows, int64_t n_traj_total, int64_t max_traj,
+               int32_t n_jobs, int32_t n_classes, bool others_ok) {
+    if (n_frames < 0 || n_streams < 0 || r_sets < 1 || n_rows < 0 || n_traj_total < 0 || max_traj < 0 || n_jobs < 0 || n_classes < 1 || !others_ok) {
+        wt::set_error("%s: bad argument", entry);
+        return WT_ERR_INVALID;
+    }
+    if ((uint64_t)n_jobs * (uint64_t)n_streams > 0x7fffffffull || (uint64_t)r_sets * (uint64_t)n_streams > 0x7fffffffull) {
+        wt::set_error("%s: %d jobs, %d results x %d streams in one call", entry, (int)n_jobs, (int)r_sets, (int)n_streams);
+        return WT_ERR_CAPACITY;
+    }
+    return WT_OK;
+}
+
+int launch(const char* entry, Layout L, const Boxes& B, const Outputs& O, int32_t* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    WT_TRY(wt::ensure_device());
+    L.max_traj = L.max_traj > 0 ? L.max_traj : 1;
+    L.lds_traj = (int)(L.max_traj < kLdsTraj ? L.max_traj : kLdsTraj);
+    const Workspace ws = carve(wt::align_ptr(workspace), (size_t)L.n_jobs, (size_t)L.n_traj_total, (size_t)L.max_traj);
+    if (!workspace || workspace_bytes < ws.bytes + 256) {
+        wt::set_error("%s: workspace too small: need %zu bytes, have %zu", entry, ws.bytes + 256, workspace_bytes);
+        return WT_ERR_CAPACITY;
+    }
+    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
+    const size_t P = (size_t)L.n_jobs * (size_t)L.n_streams, RS = (size_t)L.r_sets * (size_t)L.n_streams;
+    const long long n_traj = (long long)L.n_jobs * L.n_traj_total, n_row = (long long)L.n_jobs * L.n_rows;
+    const long long n_init = n_traj > n_row ? n_traj : n_row;
+    if (n_init > 0x7fffffffll * 256) { wt::set_error("%s: %d jobs over %lld rows in one call", entry, (int)L.n_jobs, (long long)L.n_rows); return WT_ERR_CAPACITY; }
+    if (n_init) hipLaunchKernelGGL(stitch_init_kernel, dim3((unsigned)((n_init + 255) / 256)), dim3(256), 0, stream, O, n_traj, n_row);
+    if (P) {
+        hipLaunchKernelGGL(stitch_summary_kernel, dim3((unsigned)RS), dim3(kWave), 0, stream, L, ws.sum, (int*)status_dev);
+        hipLaunchKernelGGL(stitch_match_kernel, dim3((unsigned)P), dim3(kWave), (size_t)L.lds_traj * kTableBytes, stream, L, B, ws, O, (int*)status_dev);
+    }
+    WT_HIP(hipGetLastError());
+    return WT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void wt_stitch_tracks_limits(int32_t* lds_trajectories) {
+    if (lds_trajectories) *lds_trajectories = kLdsTraj;
+}
+
+size_t wt_stitch_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj) {
+    if (n_jobs < 0 || n_streams < 0 || n_rows < 0 || n_traj_total < 0 || max_traj < 0) return 0;
+    return carve(nullptr, (size_t)n_jobs, (size_t)n_traj_total, (size_t)(max_traj > 0 ? max_traj : 1)).bytes + 256;
+}
+
+int wt_stitch_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                         const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                         int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_link, const double* job_link_iou,
+                         const int32_t* job_motion, int32_t n_classes,
+                         int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_row_root, int64_t* out_links,
+                         int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    WT_TRY(check_args("wt_stitch_tracks_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
+                      stream_frame_offsets && set_row_offsets && frame_row_offsets && x && y && w && h && category && local && traj_offsets &&
+                          job_result && job_max_link && job_link_iou && job_motion && out_pred && out_root && out_affinity && out_row_root &&
+                          out_links && status_dev));
+    Layout L;
+    L.n_frames = n_frames; L.n_rows = n_rows; L.n_traj_total = n_traj_total; L.max_traj = max_traj;
+    L.n_streams = n_streams; L.r_sets = r_sets; L.n_jobs = n_jobs; L.n_classes = n_classes; L.lds_traj = 0;
+    L.stream_frame_offsets = stream_frame_offsets; L.set_row_offsets = set_row_offsets; L.frame_row_offsets = frame_row_offsets;
+    L.traj_offsets = traj_offsets; L.category = category; L.local = local;
+    L.job_result = job_result; L.job_max_link = job_max_link; L.job_motion = job_motion; L.job_link_iou = job_link_iou;
+    const Boxes B = {x, y, w, h};
+    const Outputs O = {out_pred, out_root, out_affinity, out_row_root, out_links};
+    return launch("wt_stitch_tracks_dev", L, B, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int wt_stitch_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                          int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                          const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                          const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_link,
+                          const double* job_link_iou, const int32_t* job_motion, int32_t n_classes,
+                          int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_row_root, int64_t* out_links) {
+    const wt::StitchInput in = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h,
+                                category, local, n_traj, n_jobs, job_result, job_max_link, job_link_iou, job_motion, n_classes};
+    int64_t max_traj = 0, n_traj_total = 0;
+    WT_TRY(wt::check_stitch_layout(in, &max_traj, &n_traj_total));
+    const size_t nr = (size_t)set_row_offsets[r_sets], nf = (size_t)(n_frames + 1), rs = (size_t)r_sets * (size_t)n_streams, J = (size_t)n_jobs;
+    const size_t nt = (size_t)n_traj_total;
+    if ((J * nt && !(out_pred && out_root && out_affinity)) || (J * nr && !out_row_root) || (J * (size_t)n_streams && !out_links)) {
+        wt::set_error("wt_stitch_tracks_host: bad argument");
+        return WT_ERR_INVALID;
+    }
+    WT_TRY(check_args("wt_stitch_tracks_host", n_frames, n_streams, r_sets, (int64_t)nr, n_traj_total, max_traj, n_jobs, n_classes, true));
+    WT_TRY(wt::ensure_device());
+    std::vector<int64_t> traj_offsets(rs + 1, 0);
+    for (size_t i = 0; i < rs; ++i) traj_offsets[i + 1] = traj_offsets[i] + n_traj[i];
+    wt::DevBuf so, sr, fr, dx, dy, dw, dh, dc, dl, dt, jr, jl, ji, jm, op, oo, oa, orr, ol, status, dws;
+    WT_TRY(so.upload(stream_frame_offsets, 8 * (size_t)(n_streams + 1))); WT_TRY(sr.upload(set_row_offsets, 8 * (size_t)(r_sets + 1)));
+    WT_TRY(fr.upload(frame_row_offsets, 8 * (size_t)r_sets * nf));
+    WT_TRY(dx.upload(x, 8 * nr)); WT_TRY(dy.upload(y, 8 * nr)); WT_TRY(dw.upload(w, 8 * nr)); WT_TRY(dh.upload(h, 8 * nr));
+    WT_TRY(dc.upload(category, 4 * nr)); WT_TRY(dl.upload(local, 4 * nr)); WT_TRY(dt.upload(traj_offsets.data(), 8 * (rs + 1)));
+    WT_TRY(jr.upload(job_result, 4 * J)); WT_TRY(jl.upload(job_max_link, 4 * J * (size_t)n_classes));
+    WT_TRY(ji.upload(job_link_iou, 8 * J * (size_t)n_classes)); WT_TRY(jm.upload(job_motion, 4 * J));
+    WT_TRY(op.alloc(4 * J * nt)); WT_TRY(oo.alloc(4 * J * nt)); WT_TRY(oa.alloc(8 * J * nt)); WT_TRY(orr.alloc(4 * J * nr));
+    WT_TRY(ol.alloc(8 * J * (size_t)n_streams)); WT_TRY(status.alloc(16));
+    const size_t wsb = wt_stitch_tracks_workspace(n_jobs, n_streams, (int64_t)nr, n_traj_total, max_traj);
+    WT_TRY(dws.alloc(wsb));
+    Layout L;
+    L.n_frames = n_frames; L.n_rows = (long long)nr; L.n_traj_total = n_traj_total; L.max_traj = max_traj;
+    L.n_streams = n_streams; L.r_sets = r_sets; L.n_jobs = n_jobs; L.n_classes = n_classes; L.lds_traj = 0;
+    L.stream_frame_offsets = so.as<int64_t>(); L.set_row_offsets = sr.as<int64_t>(); L.frame_row_offsets = fr.as<int64_t>();
+    L.traj_offsets = dt.as<int64_t>(); L.category = dc.as<int32_t>(); L.local = dl.as<int32_t>();
+    L.job_result = jr.as<int32_t>(); L.job_max_link = jl.as<int32_t>(); L.job_motion = jm.as<int32_t>(); L.job_link_iou = ji.as<double>();
+    const Boxes B = {dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>()};
+    const Outputs O = {op.as<int32_t>(), oo.as<int32_t>(), oa.as<double>(), orr.as<int32_t>(), ol.as<int64_t>()};
+    WT_TRY(launch("wt_stitch_tracks_host", L, B, O, status.as<int32_t>(), dws.p, wsb, nullptr));
+    WT_HIP(hipDeviceSynchronize());
+    int32_t st = 0;
+    WT_HIP(hipMemcpy(&st, status.p, sizeof(st), hipMemcpyDeviceToHost));
+    if (st) {
+        wt::set_error("stitch kernel reported status %d (4 = counts or offsets that do not fit the rows)", (int)st);
+        return (int)st;
+    }
+    if (J * nt) {
+        WT_HIP(hipMemcpy(out_pred, op.p, 4 * J * nt, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(out_root, oo.p, 4 * J * nt, hipMemcpyDeviceToHost));
+        WT_HIP(hipMemcpy(out_affinity, oa.p, 8 * J * nt, hipMemcpyDeviceToHost));
+    }
+    if (J * nr) WT_HIP(hipMemcpy(out_row_root, orr.p, 4 * J * nr, hipMemcpyDeviceToHost));
+    if (J * (size_t)n_streams) WT_HIP(hipMemcpy(out_links, ol.p, 8 * J * (size_t)n_streams, hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+}  // extern "C"

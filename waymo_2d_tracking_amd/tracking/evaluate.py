@@ -3,7 +3,7 @@
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
         [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
@@ -850,7 +850,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
 
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
-    and 'min_hits', and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
+    and 'min_hits', optionally 'link_gap', 'link_iou' and 'link_motion' (track stitching, tracking/stitch.py; defaults [0], [0.3], 'hold' = none:
+    every tracked result is stitched under all (link_gap, link_iou) pairs in one call, before it is refined; stitching is per class, so the
+    per-class pick ranges over these too), and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
     tracked result is refined under all (gap, min_len) pairs in one call, the pairs are the innermost axes of `settings`, and the
     per-class pick ranges over them too - refinement is per trajectory with per-class parameters, so it stays valid.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
     thresholds and on (max_age, min_hits): every tracked setting uses ONE (score, iou) grid point for all classes -
@@ -885,20 +887,33 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     gaps, lens = [int(v) for v in grid.get('gap', [0])], [int(v) for v in grid.get('min_len', [1])]
     refining = gaps != [0] or lens != [1]           # the two innermost axes: one tracked result refined under every (gap, length)
     jobs = [{'max_gap': g, 'min_len': n} for g in gaps for n in lens]
+    link_gaps, link_ious = [int(v) for v in grid.get('link_gap', [0])], [float(v) for v in grid.get('link_iou', [0.3])]
+    stitching = link_gaps != [0]                    # the two axes outside them: one tracked result stitched under every (link gap, link IoU)
+    link_motion = grid.get('link_motion', 'hold')
+    link_jobs = [{'max_link': g, 'link_iou': v, 'motion': link_motion} for g in link_gaps for v in link_ious] if stitching else [None]
     for max_age in grid['max_age']:
         for min_hits in grid['min_hits']:
             for score in grid['score']:
                 for iou in grid['iou']:
                     out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
-                    if refining:
+                    base = {'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)}
+                    linked = [out]
+                    if stitching:
+                        from .stitch import stitch_tracks
+                        linked = stitch_tracks(packed, [out], link_jobs, n_classes)
+                    if refining:                     # every stitched result under every (gap, length), in one call
                         from .refine import refine_tracks
-                        for job, refined in zip(jobs, refine_tracks(packed, [out], jobs, n_classes)):
-                            settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou),
-                                             'interp_gap': job['max_gap'], 'min_len': job['min_len']})
-                            tracks.append(tracks_from_packed(packed, refined))
-                        continue
-                    settings.append({'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)})
-                    tracks.append(tracks_from_packed(packed, out))
+                        every = [dict(job, result=k) for k in range(len(linked)) for job in jobs]
+                        refined = refine_tracks(packed, linked, every, n_classes)
+                    for k, link in enumerate(link_jobs):
+                        row = dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base
+                        if not refining:
+                            settings.append(row)
+                            tracks.append(tracks_from_packed(packed, linked[k]))
+                            continue
+                        for n, job in enumerate(jobs):
+                            settings.append(dict(row, interp_gap=job['max_gap'], min_len=job['min_len']))
+                            tracks.append(tracks_from_packed(packed, refined[k * len(jobs) + n]))
     if rank_by not in ('mota', 'idf1', 'hota'):
         raise ValueError("rank_by must be 'mota', 'idf1' or 'hota'")
     identity = identity or rank_by == 'idf1'
@@ -910,7 +925,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou']) * len(jobs)
+    per_mm = len(grid['score']) * len(grid['iou']) * len(link_jobs) * len(jobs)
     for lv in LEVELS:
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
@@ -950,6 +965,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 combos[-1]['interp_gap'], combos[-1]['min_len'] = [0] * n_classes, [1] * n_classes
                 for c in classes:
                     combos[-1]['interp_gap'][c - 1], combos[-1]['min_len'][c - 1] = settings[pick[c]]['interp_gap'], settings[pick[c]]['min_len']
+            if stitching:                                             # classes that are not evaluated are not stitched either
+                combos[-1]['link_gap'], combos[-1]['link_iou'], combos[-1]['link_motion'] = [0] * n_classes, [link_ious[0]] * n_classes, link_motion
+                for c in classes:
+                    combos[-1]['link_gap'][c - 1], combos[-1]['link_iou'][c - 1] = settings[pick[c]]['link_gap'], settings[pick[c]]['link_iou']
             if identity:
                 combos[-1]['IDF1'] = identity_row(id_total['idtp'], id_total['gt'], id_total['hyp'])['idf1']
                 combos[-1]['id_counts'] = id_total
@@ -974,6 +993,10 @@ def flag_line(setting):
     join = lambda v: ','.join(repr(float(x)) for x in v)
     line = '--score-threshold=%s --iou-threshold=%s --max-age=%d --min-hits=%d' % (
         join(setting['score_threshold']), join(setting['iou_threshold']), setting['max_age'], setting['min_hits'])
+    if 'link_gap' in setting:
+        line += ' --link-gap=%s --link-iou=%s' % (','.join('%d' % v for v in setting['link_gap']), join(setting['link_iou']))
+        if setting.get('link_motion', 'hold') != 'hold':
+            line += ' --link-motion=%s' % setting['link_motion']
     if 'interp_gap' in setting:
         line += ' --interpolate-gap=%s --min-track-len=%s' % (','.join('%d' % v for v in setting['interp_gap']),
                                                               ','.join('%d' % v for v in setting['min_len']))
@@ -1024,6 +1047,9 @@ def build_parser():
     parser.add_argument('--min-hits', default='0,1')
     parser.add_argument('--gap-grid', default='0', help='track refinement: gaps of up to this many frames are interpolated (tracking/refine.py)')
     parser.add_argument('--min-len-grid', default='1', help='track refinement: tracks observed in fewer frames are dropped')
+    parser.add_argument('--link-gap-grid', default='0', help='track stitching: tracks are linked across up to this many frames (tracking/stitch.py)')
+    parser.add_argument('--link-iou-grid', default='0.3', help='track stitching: lowest IoU of the extrapolated and the new box; read when --link-gap-grid is set')
+    parser.add_argument('--link-motion', choices=('hold', 'linear'), default='hold', help='track stitching: how an ended track is extrapolated')
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
     parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
@@ -1038,7 +1064,9 @@ def main(argv=None):
     if args.sweep:
         grid = {'score': _grid_values(args.score_grid), 'iou': _grid_values(args.iou_grid),
                 'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')],
-                'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')]}
+                'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')],
+                'link_gap': [int(v) for v in args.link_gap_grid.split(',')], 'link_iou': _grid_values(args.link_iou_grid),
+                'link_motion': args.link_motion}
         identity = args.identity or args.rank_by == 'idf1'
         hota = args.hota or args.rank_by == 'hota'
         res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota)

@@ -43,6 +43,12 @@ def build_parser():
                         help='drop tracks observed in fewer frames than this (one value, or one per class)')
     parser.add_argument("--track-score", choices=('keep', 'mean'), default='keep',
                         help='mean: every box of a track carries the mean score of its observed boxes')
+    parser.add_argument("--link-gap", type=_ints, default=[0],
+                        help='stitch tracks: link a track that ends to one of its class that starts up to this many frames later (one value, or one per class)')
+    parser.add_argument("--link-iou", type=_floats, default=[0.3],
+                        help='lowest IoU of the ended track\'s extrapolated box and the new track\'s first box (one value, or one per class); read when --link-gap is set')
+    parser.add_argument("--link-motion", choices=('hold', 'linear'), default='hold',
+                        help='how the ended track is extrapolated over the gap: its last box, or moved on by its last step')
     parser.add_argument("--segment-id", type=str, help='track only a single segment')
     parser.add_argument("--python-io", action='store_true',
                         help='parse / write JSON with the Python json module (default: native reader / writer of libwaymotrack)')
@@ -54,7 +60,17 @@ def refines(args):
     return max(args.interpolate_gap) > 0 or max(args.min_track_len) > 1 or args.track_score != 'keep'
 
 
+def stitches(args):
+    """Whether the flags ask for stitching (tracking/stitch.py)."""
+    return max(args.link_gap) > 0
+
+
 def refined(args, packed, out):
+    """The tracker's rows after the post-passes the flags ask for: stitching first, so that a merged track is length-filtered and
+    gap-filled as one."""
+    if stitches(args):
+        from .stitch import stitch_one
+        out = stitch_one(packed, out, args.link_gap, args.link_iou, args.link_motion, len(args.iou_threshold))
     if not refines(args):
         return out
     from .refine import refine_one
@@ -128,7 +144,7 @@ def main(argv=None):
     start_time = time.time()
     for segment_id in predictions.keys():
         print(segment_id)
-    if refines(args):
+    if refines(args) or stitches(args):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
