@@ -564,6 +564,51 @@ int wt_stitch_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                           int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_row_root, int64_t* out_links);
 
 /* =================================================================================================
+ * Track smoothing (a symmetric window filter per trajectory; the definition is DESIGN.md section 22)
+ * ================================================================================================= */
+
+#define WT_SMOOTH_MAX_WINDOW 32
+
+/* Smooths the boxes of R >= 1 tracking results under J jobs: job j names a result, job_result[j], a window per class and a weight
+ * table per class.  Results, frame slots, streams, trajectories, local indices and a trajectory's class (the category of its first
+ * observation) are those of the track refinement above.  For the row of trajectory T at slot f, W = window[class], k = the
+ * class's weights, and each of x, y, w, h on its own:
+ *     acc = k[0] * v(f), den = k[0]; for d = 1 .. W ascending, only when T has a row at slot f - d AND one at slot f + d:
+ *     acc = acc + k[d] * (v(f - d) + v(f + d)), den = den + (k[d] + k[d]); out = acc / den,
+ * every operation rounded on its own in float64, all reads from the input.  A row that no pair contributed to keeps its input
+ * bits.  No row is added, removed or moved; score, category and identity are not read or written.
+ *
+ * Jobs: job_result (J) int32, job_window (J, n_classes) int32 in 0..WT_SMOOTH_MAX_WINDOW (0: the class is untouched),
+ * job_weights (J, n_classes, n_weights) float64, finite, >= 0, [..][0] > 0, n_weights > every window.
+ * Outputs: job after job, each job owning the rows of its result in the result's row order: job_row_offsets (J + 1) int64 is the
+ * running sum of those row counts, computed by the caller, and n_out_rows its last entry.  out_bbox (n_out_rows, 4) float64 =
+ * x, y, w, h; out_pairs (n_out_rows) int32 = the pairs that contributed to the row.
+ *
+ * wt_smooth_tracks_dev: device pointers, stream-ordered, no allocation, no synchronisation; it reports in status_dev (device
+ * int32) 0 or WT_ERR_CAPACITY (counts, indices, offsets or windows that do not fit).  A workspace smaller than
+ * wt_smooth_tracks_workspace() says is WT_ERR_CAPACITY.  The device form does not check the layout; the host form does
+ * (WT_ERR_INVALID names the result and the row or frame slot, or the job), computes job_row_offsets, stages and launches; it takes
+ * n_traj (R, n_streams) int32 where the device form takes the running sum traj_offsets, n_traj_total and max_traj.
+ * wt_smooth_tracks_limits: the trajectory count of one (result, stream) up to which the table of the link walk stays in LDS;
+ * above it the table lives in the workspace. */
+void wt_smooth_tracks_limits(int32_t* lds_trajectories);
+size_t wt_smooth_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_smooth_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                         const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                         int32_t n_jobs, const int32_t* job_result, const int32_t* job_window, const double* job_weights,
+                         int32_t n_weights, int32_t n_classes, const int64_t* job_row_offsets, int64_t n_out_rows,
+                         double* out_bbox, int32_t* out_pairs,
+                         int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_smooth_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                          int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                          const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                          const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_window,
+                          const double* job_weights, int32_t n_weights, int32_t n_classes,
+                          double* out_bbox, int32_t* out_pairs);
+
+/* =================================================================================================
  * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

@@ -1,0 +1,125 @@
+"""Cost and effect of smoothing a tracking result next to producing and refining it (recorded in profiles/track_smooth.txt; not a gate).
+
+    python tools/smooth_bench.py [--segments 8] [--frames 198] [--objects 100] [--out profiles/track_smooth.txt]
+
+On the config-1 size input of tools/refine_bench.py and tools/stitch_bench.py (8 segments x 5 cameras x 198 frames), in ONE run on
+the same input:
+  (a) wt_smooth_tracks_dev for J = 1 and J = 64 jobs on one tracked result, device events around repeated calls (inputs resident
+      in HBM; the call never waits for the stream);
+  (b) wt_refine_tracks plan + emit, J = 1, on the same result;
+  (c) utils.track_packed on the same detections (wt_track_streams_host, staging included), wall clock;
+  (d) the rows moved, and ALL-level HOTA LocA, MOTP and HOTA of the result before and after smoothing.
+The expectation to report against: smoothing a result costs less than tracking it, (a, J = 1) < (c).
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--segments', type=int, default=8)
+    ap.add_argument('--frames', type=int, default=198)
+    ap.add_argument('--objects', type=int, default=100)
+    ap.add_argument('--repeats', type=int, default=20)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'track_smooth.txt'))
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    assert torch.cuda.is_available(), 'needs the GPU'
+    from waymo_2d_tracking_amd import _lib, synthetic as syn
+    from waymo_2d_tracking_amd.tracking import evaluate as E, refine as R, smooth as S, utils as T
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    dets, gt_json = syn.make_tracking_json(1, n_segments=args.segments, n_frames=args.frames, n_objects=args.objects)
+    predictions = {}
+    for e in dets:
+        seg, fr, cam = e['image_id'].split('/')
+        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
+            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
+    packed = T.pack_streams(predictions)
+    gt = E.load_ground_truth(gt_json)
+    say('device: %s' % (_lib.device_info(),))
+    say('input: %d segments x 5 cameras x %d frames, %d detections, %d ground-truth boxes, %d streams'
+        % (args.segments, args.frames, packed['x'].size, gt['x'].size, len(gt['stream_keys'])))
+
+    def events(fn):
+        """median, min, max over `rounds` windows of `repeats` calls each, in ms per call"""
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        per_call = []
+        for _ in range(args.rounds):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(args.repeats):
+                fn()
+            stop.record()
+            stop.synchronize()
+            per_call.append(start.elapsed_time(stop) / args.repeats)
+        return float(np.median(per_call)), min(per_call), max(per_call)
+
+    verdicts = []
+    for label, flags in (('max_age 1, score >= 0.3', (1, 0, [0.3] * 4, [0.01] * 4)),
+                         ('reference flags, max_age 2', (2, 0, [0.95, 0.6, 1.0, 0.9], [0.01, 0.01, 1.0, 0.0]))):
+        T.track_packed(packed, flags[3], flags[0], flags[1], flags[2])
+        times = []
+        for _ in range(7):
+            t0 = time.perf_counter()
+            out, _ = T.track_packed(packed, flags[3], flags[0], flags[1], flags[2])
+            times.append(time.perf_counter() - t0)
+        t_track = 1e3 * float(np.median(times))
+        say('%s:' % label)
+        say('(c) track_packed (host call, staging included): median %.2f ms of 7 (min %.2f, max %.2f), %d rows'
+            % (t_track, 1e3 * min(times), 1e3 * max(times), len(out['frame'])))
+        ref = R.DeviceRefine(packed, [out], [{'max_gap': 2, 'min_len': 3}])
+
+        def both():
+            ref.launch()
+            ref.emit()
+        ms_ref = events(both)
+        say('(b) wt_refine_tracks plan + emit J = 1 (max_gap 2, min_len 3): median %.3f ms per pair (min %.3f, max %.3f)' % ms_ref)
+        ms_one = None
+        for jobs, what in (([{'window': 2, 'sigma': 1.0}], 'window 2, gaussian sigma 1.0'),
+                           ([{'window': w, 'sigma': v} for w in range(1, 9) for v in (0.5, 0.75, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)],
+                            'window 1..8 x sigma 0.5, 0.75, 1, 1.5, 2, 3, 4, 6')):
+            dev = S.DeviceSmooth(packed, [out], jobs)
+            ms, lo, hi = events(dev.launch)
+            res = dev.results()
+            J = len(jobs)
+            moved = [int((r['pairs'] > 0).sum()) for r in res]
+            say('(a) wt_smooth_tracks_dev J = %d (%s): median %.3f ms per call = %.3f ms per job (min %.3f, max %.3f; %d windows of %d calls), '
+                '%d output rows, %d trajectories, most in one stream %d, workspace %.1f MiB, rows moved per job %d .. %d'
+                % (J, what, ms, ms / J, lo, hi, args.rounds, args.repeats, dev.n_out, dev.p['n_traj_total'], dev.max_traj,
+                   dev.ws_bytes / 2.0 ** 20, min(moved), max(moved)))
+            if J == 1:
+                ms_one = ms
+                tracks = [E.tracks_from_packed(packed, out), E.tracks_from_packed(packed, res[0])]
+                p = E.pack_results(gt, tracks, 4)
+                mot = E.evaluate_tracks(gt, tracks, packed=p)
+                hota = E.evaluate_hota(gt, tracks, packed=p)
+                say('(d) %d of %d rows moved; ALL LEVEL_2 before -> after smoothing:' % (moved[0], len(out['frame'])))
+                for k, name in ((0, 'tracked '), (1, 'smoothed')):
+                    say('    %s LocA %.5f, MOTP %.5f, HOTA %.5f, DetA %.5f, AssA %.5f, MOTA %.5f, tp %d'
+                        % (name, hota[k].table['ALL'][2]['LocA'], mot[k].table['ALL'][2]['MOTP'], hota[k].table['ALL'][2]['HOTA'],
+                           hota[k].table['ALL'][2]['DetA'], hota[k].table['ALL'][2]['AssA'], mot[k].table['ALL'][2]['MOTA'], mot[k].table['ALL'][2]['tp']))
+        verdicts.append('expectation "smoothing a result costs less than tracking it", %s, (a, J = 1) < (c): %s (%.3f ms vs %.2f ms)'
+                        % (label, 'HOLDS' if ms_one < t_track else 'DOES NOT HOLD', ms_one, t_track))
+    for v in verdicts:
+        say(v)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'wt') as fp:
+        fp.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -854,7 +854,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     every tracked result is stitched under all (link_gap, link_iou) pairs in one call, before it is refined; stitching is per class, so the
     per-class pick ranges over these too), and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
     tracked result is refined under all (gap, min_len) pairs in one call, the pairs are the innermost axes of `settings`, and the
-    per-class pick ranges over them too - refinement is per trajectory with per-class parameters, so it stays valid.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
+    per-class pick ranges over them too - refinement is per trajectory with per-class parameters, so it stays valid.  Optionally
+    'smooth_window', 'smooth_sigma' and 'smooth_kernel' (track smoothing, tracking/smooth.py; defaults [0], [1.0], 'gaussian' = none):
+    all refined results of a tracked result are smoothed under all (window, sigma) pairs in one call, the pairs become the
+    innermost axes, and the per-class pick ranges over them too - the pass is per trajectory with per-class parameters.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
     thresholds and on (max_age, min_hits): every tracked setting uses ONE (score, iou) grid point for all classes -
     K = |score| x |iou| x |max_age| x |min_hits| settings - and the best point is read off per class for each
     (max_age, min_hits); no product over classes is tracked.  Best = highest ALL MOTA at the level; ties go to the setting that
@@ -891,6 +894,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     stitching = link_gaps != [0]                    # the two axes outside them: one tracked result stitched under every (link gap, link IoU)
     link_motion = grid.get('link_motion', 'hold')
     link_jobs = [{'max_link': g, 'link_iou': v, 'motion': link_motion} for g in link_gaps for v in link_ious] if stitching else [None]
+    smooth_windows, smooth_sigmas = [int(v) for v in grid.get('smooth_window', [0])], [float(v) for v in grid.get('smooth_sigma', [1.0])]
+    smoothing = smooth_windows != [0]               # the innermost axes: every refined result smoothed under every (window, sigma)
+    smooth_kernel = grid.get('smooth_kernel', 'gaussian')
+    smooth_jobs = [{'window': w, 'sigma': v, 'kernel': smooth_kernel} for w in smooth_windows for v in smooth_sigmas] if smoothing else [None]
     for max_age in grid['max_age']:
         for min_hits in grid['min_hits']:
             for score in grid['score']:
@@ -905,15 +912,24 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                         from .refine import refine_tracks
                         every = [dict(job, result=k) for k in range(len(linked)) for job in jobs]
                         refined = refine_tracks(packed, linked, every, n_classes)
+                    rows, passed = [], []
                     for k, link in enumerate(link_jobs):
                         row = dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base
                         if not refining:
-                            settings.append(row)
-                            tracks.append(tracks_from_packed(packed, linked[k]))
+                            rows.append(row)
+                            passed.append(linked[k])
                             continue
                         for n, job in enumerate(jobs):
-                            settings.append(dict(row, interp_gap=job['max_gap'], min_len=job['min_len']))
-                            tracks.append(tracks_from_packed(packed, refined[k * len(jobs) + n]))
+                            rows.append(dict(row, interp_gap=job['max_gap'], min_len=job['min_len']))
+                            passed.append(refined[k * len(jobs) + n])
+                    if smoothing:                    # every result so far under every (window, sigma), in one call
+                        from .smooth import smooth_tracks
+                        every = [dict(job, result=k) for k in range(len(passed)) for job in smooth_jobs]
+                        rows = [dict(row, smooth_window=job['window'], smooth_sigma=job['sigma']) for row in rows for job in smooth_jobs]
+                        passed = smooth_tracks(packed, passed, every, n_classes)
+                    for row, result in zip(rows, passed):
+                        settings.append(row)
+                        tracks.append(tracks_from_packed(packed, result))
     if rank_by not in ('mota', 'idf1', 'hota'):
         raise ValueError("rank_by must be 'mota', 'idf1' or 'hota'")
     identity = identity or rank_by == 'idf1'
@@ -925,7 +941,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou']) * len(link_jobs) * len(jobs)
+    per_mm = len(grid['score']) * len(grid['iou']) * len(link_jobs) * len(jobs) * len(smooth_jobs)
     for lv in LEVELS:
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
@@ -969,6 +985,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 combos[-1]['link_gap'], combos[-1]['link_iou'], combos[-1]['link_motion'] = [0] * n_classes, [link_ious[0]] * n_classes, link_motion
                 for c in classes:
                     combos[-1]['link_gap'][c - 1], combos[-1]['link_iou'][c - 1] = settings[pick[c]]['link_gap'], settings[pick[c]]['link_iou']
+            if smoothing:                                             # classes that are not evaluated are not smoothed either
+                combos[-1]['smooth_window'], combos[-1]['smooth_sigma'], combos[-1]['smooth_kernel'] = [0] * n_classes, [smooth_sigmas[0]] * n_classes, smooth_kernel
+                for c in classes:
+                    combos[-1]['smooth_window'][c - 1], combos[-1]['smooth_sigma'][c - 1] = settings[pick[c]]['smooth_window'], settings[pick[c]]['smooth_sigma']
             if identity:
                 combos[-1]['IDF1'] = identity_row(id_total['idtp'], id_total['gt'], id_total['hyp'])['idf1']
                 combos[-1]['id_counts'] = id_total
@@ -1000,6 +1020,10 @@ def flag_line(setting):
     if 'interp_gap' in setting:
         line += ' --interpolate-gap=%s --min-track-len=%s' % (','.join('%d' % v for v in setting['interp_gap']),
                                                               ','.join('%d' % v for v in setting['min_len']))
+    if 'smooth_window' in setting:
+        line += ' --smooth-window=%s --smooth-sigma=%s' % (','.join('%d' % v for v in setting['smooth_window']), join(setting['smooth_sigma']))
+        if setting.get('smooth_kernel', 'gaussian') != 'gaussian':
+            line += ' --smooth-kernel=%s' % setting['smooth_kernel']
     return line
 
 
@@ -1050,6 +1074,9 @@ def build_parser():
     parser.add_argument('--link-gap-grid', default='0', help='track stitching: tracks are linked across up to this many frames (tracking/stitch.py)')
     parser.add_argument('--link-iou-grid', default='0.3', help='track stitching: lowest IoU of the extrapolated and the new box; read when --link-gap-grid is set')
     parser.add_argument('--link-motion', choices=('hold', 'linear'), default='hold', help='track stitching: how an ended track is extrapolated')
+    parser.add_argument('--smooth-window-grid', default='0', help='track smoothing: boxes are averaged over up to this many frames to either side (tracking/smooth.py)')
+    parser.add_argument('--smooth-sigma-grid', default='1.0', help='track smoothing: width of the gaussian weights; read when --smooth-window-grid is set')
+    parser.add_argument('--smooth-kernel', choices=('gaussian', 'box'), default='gaussian', help='track smoothing: the weights over the window')
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
     parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
@@ -1066,7 +1093,9 @@ def main(argv=None):
                 'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')],
                 'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')],
                 'link_gap': [int(v) for v in args.link_gap_grid.split(',')], 'link_iou': _grid_values(args.link_iou_grid),
-                'link_motion': args.link_motion}
+                'link_motion': args.link_motion,
+                'smooth_window': [int(v) for v in args.smooth_window_grid.split(',')], 'smooth_sigma': _grid_values(args.smooth_sigma_grid),
+                'smooth_kernel': args.smooth_kernel}
         identity = args.identity or args.rank_by == 'idf1'
         hota = args.hota or args.rank_by == 'hota'
         res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota)

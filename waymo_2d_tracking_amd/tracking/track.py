@@ -49,6 +49,13 @@ def build_parser():
                         help='lowest IoU of the ended track\'s extrapolated box and the new track\'s first box (one value, or one per class); read when --link-gap is set')
     parser.add_argument("--link-motion", choices=('hold', 'linear'), default='hold',
                         help='how the ended track is extrapolated over the gap: its last box, or moved on by its last step')
+    parser.add_argument("--smooth-window", type=_ints, default=[0],
+                        help='smooth tracks: every box becomes the weighted mean of its track\'s boxes up to this many frames to either side, '
+                             'both sides or neither (one value, or one per class)')
+    parser.add_argument("--smooth-sigma", type=_floats, default=[1.0],
+                        help='width of the gaussian weights in frames (one value, or one per class); read when --smooth-window is set')
+    parser.add_argument("--smooth-kernel", choices=('gaussian', 'box'), default='gaussian',
+                        help='the weights over the window: exp(-d^2 / (2 sigma^2)), or all equal')
     parser.add_argument("--segment-id", type=str, help='track only a single segment')
     parser.add_argument("--python-io", action='store_true',
                         help='parse / write JSON with the Python json module (default: native reader / writer of libwaymotrack)')
@@ -65,16 +72,24 @@ def stitches(args):
     return max(args.link_gap) > 0
 
 
+def smooths(args):
+    """Whether the flags ask for smoothing (tracking/smooth.py)."""
+    return max(args.smooth_window) > 0
+
+
 def refined(args, packed, out):
     """The tracker's rows after the post-passes the flags ask for: stitching first, so that a merged track is length-filtered and
-    gap-filled as one."""
+    gap-filled as one; smoothing last, so that filled rows are smoothed too."""
     if stitches(args):
         from .stitch import stitch_one
         out = stitch_one(packed, out, args.link_gap, args.link_iou, args.link_motion, len(args.iou_threshold))
-    if not refines(args):
-        return out
-    from .refine import refine_one
-    return refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, len(args.iou_threshold))
+    if refines(args):
+        from .refine import refine_one
+        out = refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, len(args.iou_threshold))
+    if smooths(args):
+        from .smooth import smooth_one
+        out = smooth_one(packed, out, args.smooth_window, args.smooth_sigma, args.smooth_kernel, len(args.iou_threshold))
+    return out
 
 
 def main_native(args):
@@ -144,7 +159,7 @@ def main(argv=None):
     start_time = time.time()
     for segment_id in predictions.keys():
         print(segment_id)
-    if refines(args) or stitches(args):
+    if refines(args) or stitches(args) or smooths(args):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
