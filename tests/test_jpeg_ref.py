@@ -35,23 +35,7 @@ def test_restatement_rejects_what_the_gpu_decoder_rejects():
 
 @pytest.fixture(scope='module')
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp('jpeg') / 'libjpeg_emul.so')
-    subprocess.run(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', so, os.path.join(ROOT, 'tests', 'native', 'jpeg_sync_emul.cpp')],
-                   check=True)
-    lib = ctypes.CDLL(so)
-
-    def run(data, group=256):
-        cap = 1 << 17
-        coef = np.zeros((cap, 64), np.int16)
-        rounds, total = ctypes.c_int(0), ctypes.c_int(0)
-        geo = (ctypes.c_int * 10)()
-        err = ctypes.create_string_buffer(256)
-        rc = lib.jpeg_emul_coefficients(data, ctypes.c_long(len(data)), group, coef.ctypes.data_as(ctypes.c_void_p), ctypes.c_long(cap),
-                                        ctypes.byref(rounds), ctypes.byref(total), geo, err, 256)
-        if rc:
-            raise RuntimeError(err.value.decode())
-        return coef[:total.value], rounds.value, list(geo)
-    return run
+    return JC.emulator(tmp_path_factory.mktemp('jpeg'))
 
 
 def scan_order(info, planes):
