@@ -609,7 +609,62 @@ int wt_smooth_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                           double* out_bbox, int32_t* out_pairs);
 
 /* =================================================================================================
- * Detection evaluation  (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
+ * Track deduplication (track-level non-maximum suppression; the definition is DESIGN.md section 23)
+ * ================================================================================================= */
+
+/* Suppresses duplicate trajectories of R >= 1 tracking results under J jobs: job j names a result, job_result[j], and its
+ * parameters.  Results, frame slots, streams, trajectories, local indices and a trajectory's class (the category of its first
+ * observation) are those of the track refinement above; as in stitching the local indices number the trajectories of a
+ * (result, stream) by first appearance.  For a trajectory t: n_t = its rows, c_t = its class, s_t = its score sum (0.0, then
+ * every row's score added one by one in slot order, float64).  t is stronger than u when n_t > n_u, or n_t == n_u and s_t > s_u,
+ * or both are equal and t < u by local index; scores must be finite, so the order is strict and total.
+ * m(t, u) = the frame slots in which both have a row and a = iou_dd([x, y, x + w, y + h]_t, [..]_u) satisfies a >= dup_iou[c]
+ * and a > 0 (a NaN never does).  t and u are duplicates when c_t == c_u == c, min_frames[c] > 0, m(t, u) >= min_frames[c] and
+ * (double)m(t, u) >= dup_frac[c] * (double)min(n_t, n_u) (one multiplication, rounded in float64).
+ * The trajectories of a (result, stream) are walked from strongest to weakest; one is suppressed when some stronger trajectory
+ * that was itself kept is its duplicate (greedy non-maximum suppression: a suppressed trajectory suppresses nothing).  All rows
+ * of a suppressed trajectory are removed; nothing else changes.
+ *
+ * Jobs: job_result (J) int32, job_min_frames (J, n_classes) int32 >= 0 (0: the class is untouched), job_dup_iou (J, n_classes)
+ * float64 not NaN, job_dup_frac (J, n_classes) float64 in [0, 1].
+ * Outputs, sized up front: out_keep, out_by, out_match (J, n_traj_total) int32, indexed like traj_offsets - 1 kept / 0
+ * suppressed, the local index of the strongest kept duplicate or -1, m with it or 0; out_row_keep (J, n_rows) int32 = per row
+ * of the job's result 1 or 0; out_dropped (J, n_streams) int64 = the trajectories suppressed.  Entries of results the job does
+ * not name are -1.  A job whose min_frames is all 0 keeps everything.
+ *
+ * wt_dedup_tracks_dev: device pointers, stream-ordered, no allocation, no synchronisation; it reports in status_dev (device
+ * int32) 0 or WT_ERR_CAPACITY (counts, indices or offsets that do not fit the rows).  A workspace smaller than
+ * wt_dedup_tracks_workspace() says is WT_ERR_CAPACITY; that size depends on its five arguments only, never on how many
+ * duplicates the data holds.  The device form does not check the layout; the host form does (WT_ERR_INVALID names the result
+ * and the row or frame slot, or the job and class; a score that is not finite is refused), stages and launches; it takes n_traj
+ * (R, n_streams) int32 where the device form takes the running sum traj_offsets, n_traj_total and max_traj.
+ * wt_dedup_tracks_limits: the trajectory count of one (result, stream) up to which the tables of the matching stay in LDS;
+ * above it they live in the workspace.
+ * wt_dedup_tracks_rounds: after a wt_dedup_tracks_dev call on `workspace` has finished, the sweeps over the slots that the
+ * matching of each (job, stream) took - 1 + the longest chain of duplicates it had to resolve - into out_rounds (J, n_streams)
+ * int32, a host pointer.  It synchronises; it is for measurements. */
+void wt_dedup_tracks_limits(int32_t* lds_trajectories);
+size_t wt_dedup_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_dedup_tracks_rounds(const void* workspace, int32_t n_jobs, int32_t n_streams, int32_t* out_rounds);
+int wt_dedup_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                        int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                        const double* x, const double* y, const double* w, const double* h, const double* score,
+                        const int32_t* category, const int32_t* local,
+                        const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                        int32_t n_jobs, const int32_t* job_result, const int32_t* job_min_frames,
+                        const double* job_dup_iou, const double* job_dup_frac, int32_t n_classes,
+                        int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped,
+                        int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_dedup_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const double* score,
+                         const int32_t* category, const int32_t* local,
+                         const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_min_frames,
+                         const double* job_dup_iou, const double* job_dup_frac, int32_t n_classes,
+                         int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped);
+
+/* =================================================================================================
+ * Detection evaluation (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 
 /* Scores K >= 1 detection results against one ground truth, as detnet/data/metric.py does on one host thread (match_class,

@@ -35,6 +35,7 @@ UNITS = {
     'track_refine.hip': ['-ffp-contract=off'],         # track refinement: a fill is va + (vb - va) * (j / n), every operation rounded on its own
     'track_stitch.hip': ['-ffp-contract=off'],         # track stitching: the extrapolation x + ((x - xp) / (e - p)) * n unfused, the same float64 IoU
     'track_smooth.hip': ['-ffp-contract=off'],         # track smoothing: acc + k[d] * (v(f - d) + v(f + d)) and the quotient, every operation rounded on its own
+    'track_dedup.hip': ['-ffp-contract=off'],          # track deduplication: the same float64 IoU, dup_frac * min(n) one multiplication
     'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_roialign.hip': [],
     'det_nms.hip': [],

@@ -3,7 +3,7 @@
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
         [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
@@ -852,7 +852,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
     and 'min_hits', optionally 'link_gap', 'link_iou' and 'link_motion' (track stitching, tracking/stitch.py; defaults [0], [0.3], 'hold' = none:
     every tracked result is stitched under all (link_gap, link_iou) pairs in one call, before it is refined; stitching is per class, so the
-    per-class pick ranges over these too), and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
+    per-class pick ranges over these too), optionally 'dedup_frames', 'dedup_iou' and the single value 'dedup_frac' (suppression of duplicate
+    tracks, tracking/dedup.py; defaults [0], [0.7], 0.5 = none: every stitched result is deduplicated under all (frames, IoU) pairs in one
+    call, before it is refined; the pass is per class, so the per-class pick ranges over these too), and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
     tracked result is refined under all (gap, min_len) pairs in one call, the pairs are the innermost axes of `settings`, and the
     per-class pick ranges over them too - refinement is per trajectory with per-class parameters, so it stays valid.  Optionally
     'smooth_window', 'smooth_sigma' and 'smooth_kernel' (track smoothing, tracking/smooth.py; defaults [0], [1.0], 'gaussian' = none):
@@ -894,6 +896,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     stitching = link_gaps != [0]                    # the two axes outside them: one tracked result stitched under every (link gap, link IoU)
     link_motion = grid.get('link_motion', 'hold')
     link_jobs = [{'max_link': g, 'link_iou': v, 'motion': link_motion} for g in link_gaps for v in link_ious] if stitching else [None]
+    dedup_frames, dedup_ious = [int(v) for v in grid.get('dedup_frames', [0])], [float(v) for v in grid.get('dedup_iou', [0.7])]
+    deduping = dedup_frames != [0]                  # between them: every stitched result deduplicated under every (frames, IoU)
+    dedup_frac = float(grid.get('dedup_frac', 0.5))
+    dedup_jobs = [{'min_frames': f, 'dup_iou': v, 'dup_frac': dedup_frac} for f in dedup_frames for v in dedup_ious] if deduping else [None]
     smooth_windows, smooth_sigmas = [int(v) for v in grid.get('smooth_window', [0])], [float(v) for v in grid.get('smooth_sigma', [1.0])]
     smoothing = smooth_windows != [0]               # the innermost axes: every refined result smoothed under every (window, sigma)
     smooth_kernel = grid.get('smooth_kernel', 'gaussian')
@@ -908,13 +914,18 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                     if stitching:
                         from .stitch import stitch_tracks
                         linked = stitch_tracks(packed, [out], link_jobs, n_classes)
+                    link_rows = [dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base for link in link_jobs]
+                    if deduping:                     # every stitched result under every (frames, IoU), in one call
+                        from .dedup import dedup_tracks
+                        every = [dict(job, result=k) for k in range(len(linked)) for job in dedup_jobs]
+                        link_rows = [dict(row, dedup_frames=job['min_frames'], dedup_iou=job['dup_iou']) for row in link_rows for job in dedup_jobs]
+                        linked = dedup_tracks(packed, linked, every, n_classes)
                     if refining:                     # every stitched result under every (gap, length), in one call
                         from .refine import refine_tracks
                         every = [dict(job, result=k) for k in range(len(linked)) for job in jobs]
                         refined = refine_tracks(packed, linked, every, n_classes)
                     rows, passed = [], []
-                    for k, link in enumerate(link_jobs):
-                        row = dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base
+                    for k, row in enumerate(link_rows):
                         if not refining:
                             rows.append(row)
                             passed.append(linked[k])
@@ -941,7 +952,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou']) * len(link_jobs) * len(jobs) * len(smooth_jobs)
+    per_mm = len(grid['score']) * len(grid['iou']) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
     for lv in LEVELS:
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
@@ -985,6 +996,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 combos[-1]['link_gap'], combos[-1]['link_iou'], combos[-1]['link_motion'] = [0] * n_classes, [link_ious[0]] * n_classes, link_motion
                 for c in classes:
                     combos[-1]['link_gap'][c - 1], combos[-1]['link_iou'][c - 1] = settings[pick[c]]['link_gap'], settings[pick[c]]['link_iou']
+            if deduping:                                              # classes that are not evaluated are not deduplicated either
+                combos[-1]['dedup_frames'], combos[-1]['dedup_iou'], combos[-1]['dedup_frac'] = [0] * n_classes, [dedup_ious[0]] * n_classes, dedup_frac
+                for c in classes:
+                    combos[-1]['dedup_frames'][c - 1], combos[-1]['dedup_iou'][c - 1] = settings[pick[c]]['dedup_frames'], settings[pick[c]]['dedup_iou']
             if smoothing:                                             # classes that are not evaluated are not smoothed either
                 combos[-1]['smooth_window'], combos[-1]['smooth_sigma'], combos[-1]['smooth_kernel'] = [0] * n_classes, [smooth_sigmas[0]] * n_classes, smooth_kernel
                 for c in classes:
@@ -1017,6 +1032,9 @@ def flag_line(setting):
         line += ' --link-gap=%s --link-iou=%s' % (','.join('%d' % v for v in setting['link_gap']), join(setting['link_iou']))
         if setting.get('link_motion', 'hold') != 'hold':
             line += ' --link-motion=%s' % setting['link_motion']
+    if 'dedup_frames' in setting:
+        line += ' --dedup-frames=%s --dedup-iou=%s --dedup-frac=%r' % (','.join('%d' % v for v in setting['dedup_frames']), join(setting['dedup_iou']),
+                                                                        float(setting.get('dedup_frac', 0.5)))
     if 'interp_gap' in setting:
         line += ' --interpolate-gap=%s --min-track-len=%s' % (','.join('%d' % v for v in setting['interp_gap']),
                                                               ','.join('%d' % v for v in setting['min_len']))
@@ -1074,6 +1092,9 @@ def build_parser():
     parser.add_argument('--link-gap-grid', default='0', help='track stitching: tracks are linked across up to this many frames (tracking/stitch.py)')
     parser.add_argument('--link-iou-grid', default='0.3', help='track stitching: lowest IoU of the extrapolated and the new box; read when --link-gap-grid is set')
     parser.add_argument('--link-motion', choices=('hold', 'linear'), default='hold', help='track stitching: how an ended track is extrapolated')
+    parser.add_argument('--dedup-frames-grid', default='0', help='track deduplication: a track is dropped when a stronger one overlaps it in this many frames (tracking/dedup.py)')
+    parser.add_argument('--dedup-iou-grid', default='0.7', help='track deduplication: lowest IoU of the two boxes that counts; read when --dedup-frames-grid is set')
+    parser.add_argument('--dedup-frac', type=float, default=0.5, help='track deduplication: lowest share of the shorter track\'s frames that must count')
     parser.add_argument('--smooth-window-grid', default='0', help='track smoothing: boxes are averaged over up to this many frames to either side (tracking/smooth.py)')
     parser.add_argument('--smooth-sigma-grid', default='1.0', help='track smoothing: width of the gaussian weights; read when --smooth-window-grid is set')
     parser.add_argument('--smooth-kernel', choices=('gaussian', 'box'), default='gaussian', help='track smoothing: the weights over the window')
@@ -1094,6 +1115,8 @@ def main(argv=None):
                 'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')],
                 'link_gap': [int(v) for v in args.link_gap_grid.split(',')], 'link_iou': _grid_values(args.link_iou_grid),
                 'link_motion': args.link_motion,
+                'dedup_frames': [int(v) for v in args.dedup_frames_grid.split(',')], 'dedup_iou': _grid_values(args.dedup_iou_grid),
+                'dedup_frac': args.dedup_frac,
                 'smooth_window': [int(v) for v in args.smooth_window_grid.split(',')], 'smooth_sigma': _grid_values(args.smooth_sigma_grid),
                 'smooth_kernel': args.smooth_kernel}
         identity = args.identity or args.rank_by == 'idf1'

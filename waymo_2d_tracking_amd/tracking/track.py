@@ -49,6 +49,13 @@ def build_parser():
                         help='lowest IoU of the ended track\'s extrapolated box and the new track\'s first box (one value, or one per class); read when --link-gap is set')
     parser.add_argument("--link-motion", choices=('hold', 'linear'), default='hold',
                         help='how the ended track is extrapolated over the gap: its last box, or moved on by its last step')
+    parser.add_argument("--dedup-frames", type=_ints, default=[0],
+                        help='suppress duplicate tracks: a track is dropped when a stronger one of its class overlaps it in at least this many frames '
+                             '(one value, or one per class; 0 = off)')
+    parser.add_argument("--dedup-iou", type=_floats, default=[0.7],
+                        help='lowest IoU of the two tracks\' boxes in a frame that counts (one value, or one per class); read when --dedup-frames is set')
+    parser.add_argument("--dedup-frac", type=_floats, default=[0.5],
+                        help='lowest share of the shorter track\'s frames that must count (one value, or one per class); read when --dedup-frames is set')
     parser.add_argument("--smooth-window", type=_ints, default=[0],
                         help='smooth tracks: every box becomes the weighted mean of its track\'s boxes up to this many frames to either side, '
                              'both sides or neither (one value, or one per class)')
@@ -72,6 +79,11 @@ def stitches(args):
     return max(args.link_gap) > 0
 
 
+def dedups(args):
+    """Whether the flags ask for the suppression of duplicate tracks (tracking/dedup.py)."""
+    return max(args.dedup_frames) > 0
+
+
 def smooths(args):
     """Whether the flags ask for smoothing (tracking/smooth.py)."""
     return max(args.smooth_window) > 0
@@ -79,10 +91,14 @@ def smooths(args):
 
 def refined(args, packed, out):
     """The tracker's rows after the post-passes the flags ask for: stitching first, so that a merged track is length-filtered and
-    gap-filled as one; smoothing last, so that filled rows are smoothed too."""
+    gap-filled as one; then the suppression of duplicates, which judges a stitched track at its full length and leaves gap filling
+    and the length filter the survivors only; smoothing last, so that filled rows are smoothed too."""
     if stitches(args):
         from .stitch import stitch_one
         out = stitch_one(packed, out, args.link_gap, args.link_iou, args.link_motion, len(args.iou_threshold))
+    if dedups(args):
+        from .dedup import dedup_one
+        out = dedup_one(packed, out, args.dedup_frames, args.dedup_iou, args.dedup_frac, len(args.iou_threshold))
     if refines(args):
         from .refine import refine_one
         out = refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, len(args.iou_threshold))
@@ -90,6 +106,9 @@ def refined(args, packed, out):
         from .smooth import smooth_one
         out = smooth_one(packed, out, args.smooth_window, args.smooth_sigma, args.smooth_kernel, len(args.iou_threshold))
     return out
+
+
+post_passes = refined
 
 
 def main_native(args):
@@ -159,7 +178,7 @@ def main(argv=None):
     start_time = time.time()
     for segment_id in predictions.keys():
         print(segment_id)
-    if refines(args) or stitches(args) or smooths(args):
+    if refines(args) or stitches(args) or dedups(args) or smooths(args):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
