@@ -137,6 +137,42 @@ int wt_track_streams_dev(int64_t n_dets, const double* x, const double* y, const
                          int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same batched tracking with a second association over low-score detections (ByteTrack, Zhang et al., ECCV 2022).
+ * Arguments as the wt_track_streams_* twins, plus low_score_threshold / low_iou_threshold: host arrays, n_classes entries
+ * indexed by category-1.  params->score_threshold stays the HIGH threshold.
+ *   A detection is valid when its category is in 1..n_classes, !(w < 1), !(h < 1) and !(score < low_score_threshold[c]);
+ *   a valid one is high when !(score < score_threshold[c]), otherwise low.
+ *   A class's tracker is created, and the class's place in the id order fixed, by its first valid detection, high or low.
+ *   Per frame and class: predict; associate the high detections with all tracks (iou_threshold[c]); associate the low ones
+ *   with the tracks left unmatched, in list order (low_iou_threshold[c]); both kinds of match update their track alike;
+ *   births from unmatched high detections only; emit and reap as before.  A low detection without a track is dropped.
+ * With low_score_threshold == score_threshold nothing is low and the rows are those of wt_track_streams_*.
+ * WT_ERR_INVALID (the message names the class) when low_score_threshold[c] > score_threshold[c], when a threshold is NaN or
+ * when low_iou_threshold[c] is outside [0, 1]; checked before any device call.  wt_track_streams_byte_workspace returns 0 then.
+ * Batch form only: the streaming entry points below, wt_sort_* and wt_mct_* have no second association. */
+int wt_track_streams_byte_host(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                               const double* score, const int32_t* category,
+                               int64_t n_frames, const int64_t* frame_det_offsets,
+                               int32_t n_streams, const int64_t* stream_frame_offsets,
+                               const double* clip_w, const double* clip_h,
+                               const wt_track_params* params, const double* low_score_threshold,
+                               const double* low_iou_threshold, int64_t id_base,
+                               int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                               int64_t* out_object_id, int64_t* n_out, int64_t* n_births);
+size_t wt_track_streams_byte_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets,
+                                       const wt_track_params* params, const double* low_score_threshold,
+                                       const double* low_iou_threshold);
+int wt_track_streams_byte_dev(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                              const double* score, const int32_t* category,
+                              int64_t n_frames, const int64_t* frame_det_offsets,
+                              int32_t n_streams, const int64_t* stream_frame_offsets,
+                              const double* clip_w, const double* clip_h, int64_t max_frame_dets,
+                              const wt_track_params* params, const double* low_score_threshold,
+                              const double* low_iou_threshold, int64_t id_base,
+                              int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                              int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Streaming form of the same tracker (online detect -> track: tracking/utils.py:29-36 keeps ONE MultiClassTrackerSort per
  * stream alive while the frames arrive).  The trackers of n_streams streams live in a caller-owned device block `state`;
  * every wt_track_chunk_dev call feeds the next frames of each stream (same SoA / CSR layout as wt_track_streams_dev; a

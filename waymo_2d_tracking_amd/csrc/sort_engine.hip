@@ -11,6 +11,7 @@
 // `finalize_kernel` scatters rows to their final position with their global id.
 #include "common.h"
 #include "sort_device.h"
+#include "sort_byte_device.h"
 #include <vector>
 
 using namespace wtdev;
@@ -111,6 +112,25 @@ Workspace carve_ws(void* base, int64_t n_dets, int64_t n_frames, int32_t n_strea
     w.totals = cv.take<long long>(2);
     w.bytes = cv.off;
     return w;
+}
+
+// Second association with low-score detections (wt_track_streams_byte_*): what it needs beyond Workspace and State, carved behind them
+struct ByteExtra {
+    int* rem;                            // per tracker: list positions left unmatched by the first association [cap]
+    double* low_score; double* low_iou;  // [C]
+    const double *h_low_score, *h_low_iou;   // the caller's host arrays
+    size_t bytes;
+};
+
+ByteExtra carve_byte(void* base, int32_t n_streams, int C, int cap) {
+    wt::Carver cv(base);
+    ByteExtra b;
+    b.rem = cv.take<int>((size_t)n_streams * (size_t)C * cap);
+    b.low_score = cv.take<double>((size_t)C);
+    b.low_iou = cv.take<double>((size_t)C);
+    b.h_low_score = b.h_low_iou = nullptr;
+    b.bytes = cv.off;
+    return b;
 }
 
 __device__ __forceinline__ TrackerMem tracker_mem(const State& st, const Workspace& w, size_t tk, int cap, int capN,
@@ -278,6 +298,94 @@ __global__ __launch_bounds__(HELP ? kHelpWaves * kWave : kWave) void sort_stream
     if constexpr (HELP) {                        // send the helper waves home
         if (lane == 0) L.help->cmd = HELP_EXIT;
         __syncthreads();
+    }
+}
+
+// The same wavefront-per-(stream, class) frame loop with a second association (sort_byte_device.h): a detection is valid from
+// low_score[c] on and high from thr_score[c] on; the class's valid detections are compacted into det_idx as the high ones, then
+// the low ones, both in input order.  `lower` counts VALID detections of lower classes, so the intermediate slots d0 + lower ..
+// still hold the class's rows: a frame emits at most |H| + |L| of them.  Plain one-wave form at every tracker count, batch form only.
+__global__ __launch_bounds__(kWave) void sort_streams_byte_kernel(
+    const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
+    const double* __restrict__ h, const double* __restrict__ score, const int32_t* __restrict__ category,
+    const int64_t* __restrict__ frame_det_offsets, const int64_t* __restrict__ stream_frame_offsets,
+    const double* __restrict__ clip_w, const double* __restrict__ clip_h, int C, int max_age, int min_hits,
+    int cap, int capN, int lds_cost_cap, bool have_cost_g, long long n_slots, Workspace ws, State st, ByteExtra bx) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lt = lanemask_lt();
+    const size_t tk = blockIdx.x;
+    const int s = (int)(tk / C);
+    const int c = (int)(tk % C) + 1;
+    float* lds_cost = reinterpret_cast<float*>(smem);
+    const size_t mk_off = (((size_t)lds_cost_cap * sizeof(float) + 15) / 16) * 16;
+    MunkresMem L = munkres_mem(smem + mk_off, capN, cap);
+    TrackerMem M = tracker_mem(st, ws, tk, cap, capN, have_cost_g);
+    int* det_idx = ws.det_idx + tk * capN;
+    int* rem = bx.rem + tk * cap;
+    TrackerState S = {0, cap, 0, 0};
+    bool created = false;
+    long long first_key = -1;
+    for (int i = lane; i < cap; i += kWave) M.freel[i] = cap - 1 - i;
+    wsync();
+    const double thr_iou = ws.thr_iou[c - 1], low_iou = bx.low_iou[c - 1], thr_high = ws.thr_score[c - 1];
+    const double cw = clip_w ? clip_w[s] : 0.0, ch = clip_h ? clip_h[s] : 0.0;
+    const long long f0 = stream_frame_offsets[s], f1 = stream_frame_offsets[s + 1];
+    for (long long f = f0; f < f1; ++f) {
+        const long long d0 = frame_det_offsets[f], d1 = frame_det_offsets[f + 1];
+        // one scan: the high detections go straight to det_idx, the low ones wait in `rem` (free between frames, cap >= capN ints)
+        int NH = 0, NL = 0, lower = 0, first_pos = -1;
+        for (long long base = d0; base < d1; base += kWave) {
+            const long long d = base + lane;
+            bool high = false, low = false, before = false;
+            if (d < d1) {
+                const int cat = category[d];
+                const bool valid = (cat >= 1 && cat <= C) && !(w[d] < 1) && !(h[d] < 1) && !(score[d] < bx.low_score[cat - 1]);
+                const bool mine = valid && cat == c;
+                high = mine && !(score[d] < thr_high);
+                low = mine && !high;
+                before = valid && cat < c;
+            }
+            const unsigned long long mh = __ballot(high), ml = __ballot(low);
+            if (high) {
+                const int k = NH + __popcll(mh & lt);
+                if (k < capN) det_idx[k] = (int)(d - d0);
+            }
+            if (low) {
+                const int k = NL + __popcll(ml & lt);
+                if (k < capN) rem[k] = (int)(d - d0);
+            }
+            if ((mh | ml) && first_pos < 0) first_pos = (int)(base - d0) + __builtin_ctzll(mh | ml);
+            NH += __popcll(mh);
+            NL += __popcll(ml);
+            lower += __popcll(__ballot(before));
+        }
+        const bool overflow = NH + NL > capN;
+        if (!created) {
+            if (NH + NL == 0) continue;
+            created = true;
+            first_key = ((f - f0) << 32) | (long long)first_pos;
+        }
+        wsync();
+        if (!overflow)
+            for (int k = lane; k < NL; k += kWave) det_idx[NH + k] = rem[k];
+        wsync();
+        StreamDets dets = {x, y, w, h, det_idx, d0};
+        StreamEmit emit = {cw, ch, ws.irow, ws.ifr, ws.isc, ws.ij, ws.ibf, ws.ibk, ws.igid, n_slots, d0 + lower, (int)f, (int)tk};
+        int nb = 0, nr = 0;
+        int rc = overflow ? WT_ERR_CAPACITY
+                          : tracker_step_byte(M, S, L, lds_cost, lds_cost_cap, dets, NH, NL, rem, thr_iou, low_iou, max_age, min_hits,
+                                              (int)f, 0ll, emit, &nb, &nr);
+        if (rc) {
+            if (lane == 0) atomicMax(ws.err, rc);
+            break;
+        }
+        if (lane == 0) { ws.cnt[f * C + c - 1] = nr; ws.births[f * C + c - 1] = nb; }
+    }
+    if (lane == 0) {
+        st.first_key[tk] = created ? first_key : -1;
+        st.hdr[tk * 4 + 0] = S.n_tracks; st.hdr[tk * 4 + 1] = S.n_free;
+        st.hdr[tk * 4 + 2] = S.frame_count; st.hdr[tk * 4 + 3] = S.next_local;
     }
 }
 
@@ -489,7 +597,7 @@ int run_tracking(int64_t n_dets, const double* x, const double* y, const double*
                  const wt_track_params* params, int64_t id_base, int64_t* out_frame, int32_t* out_category,
                  double* out_bbox4, double* out_score, int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
                  const Workspace& ws, const State& st, int resume, int cap, int capN, int lds_cost, bool cost_g, size_t lds,
-                 hipStream_t stream) {
+                 hipStream_t stream, const ByteExtra* byte = nullptr) {
     const int C = params->n_classes;
     WT_HIP(hipMemcpyAsync(ws.thr_score, params->score_threshold, sizeof(double) * C, hipMemcpyHostToDevice, stream));
     WT_HIP(hipMemcpyAsync(ws.thr_iou, params->iou_threshold, sizeof(double) * C, hipMemcpyHostToDevice, stream));
@@ -501,12 +609,20 @@ int run_tracking(int64_t n_dets, const double* x, const double* y, const double*
     WT_HIP(hipMemsetAsync(ws.rbirths, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
     const unsigned n_trackers = (unsigned)n_streams * (unsigned)C;
     // helper waves (three more waves per tracker for the data-parallel phases) when every tracker can have a CU to itself anyway
-    const bool helpers = n_trackers <= 256 && (lds + 15) / 16 * 16 + wtdev::help_lds_bytes() <= (size_t)160 * 1024 - 256;
+    const bool helpers = !byte && n_trackers <= 256 && (lds + 15) / 16 * 16 + wtdev::help_lds_bytes() <= (size_t)160 * 1024 - 256;
     if (helpers) lds = (lds + 15) / 16 * 16 + wtdev::help_lds_bytes();
-    if (lds > 48 * 1024)
+    if (!byte && lds > 48 * 1024)
         WT_HIP(hipFuncSetAttribute(helpers ? reinterpret_cast<const void*>(sort_streams_kernel<true>) : reinterpret_cast<const void*>(sort_streams_kernel<false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (helpers)
+    if (byte) {                                  // second association: the plain one-wave form at every tracker count
+        WT_HIP(hipMemcpyAsync(byte->low_score, byte->h_low_score, sizeof(double) * C, hipMemcpyHostToDevice, stream));
+        WT_HIP(hipMemcpyAsync(byte->low_iou, byte->h_low_iou, sizeof(double) * C, hipMemcpyHostToDevice, stream));
+        if (lds > 48 * 1024)
+            WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sort_streams_byte_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(sort_streams_byte_kernel, dim3(n_trackers), dim3(kWave), lds, stream, x, y, w, h, score, category,
+                           frame_det_offsets, stream_frame_offsets, clip_w, clip_h, C, (int)params->max_age,
+                           (int)params->min_hits, cap, capN, lds_cost, cost_g, (long long)n_dets, ws, st, *byte);
+    } else if (helpers)
         hipLaunchKernelGGL(sort_streams_kernel<true>, dim3(n_trackers), dim3(kHelpWaves * kWave), lds, stream, x, y, w, h, score, category,
                            frame_det_offsets, stream_frame_offsets, clip_w, clip_h, C, (int)params->max_age,
                            (int)params->min_hits, cap, capN, lds_cost, cost_g, (long long)n_dets, ws, st, resume);
@@ -576,6 +692,85 @@ int wt_track_streams_dev(int64_t n_dets, const double* x, const double* y, const
     return run_tracking(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
                         clip_w, clip_h, params, id_base, out_frame, out_category, out_bbox4, out_score, out_object_id,
                         n_out_dev, n_births_dev, ws, st, 0, cap, capN, lds_cost, cost_g, lds, stream);
+}
+
+/* ---- second association with low-score detections (batch form) ---- */
+}  // extern "C"
+
+namespace {
+// low_score[c] <= score_threshold[c], no NaN, low_iou[c] in [0, 1]
+int check_byte_thresholds(const wt_track_params* p, const double* low_score, const double* low_iou) {
+    if (!p || p->n_classes < 1 || !p->iou_threshold || !p->score_threshold || p->max_age < 0) {
+        wt::set_error("bad wt_track_params");
+        return WT_ERR_INVALID;
+    }
+    if (!low_score || !low_iou) { wt::set_error("low_score_threshold / low_iou_threshold is NULL"); return WT_ERR_INVALID; }
+    for (int c = 0; c < p->n_classes; ++c) {
+        const double lo = low_score[c], hi = p->score_threshold[c], li = low_iou[c];
+        if (lo != lo || hi != hi || li != li) {
+            wt::set_error("class %d: a threshold of the second association is NaN", c + 1);
+            return WT_ERR_INVALID;
+        }
+        if (lo > hi) {
+            wt::set_error("class %d: low_score_threshold %g above score_threshold %g", c + 1, lo, hi);
+            return WT_ERR_INVALID;
+        }
+        if (li < 0.0 || li > 1.0) {
+            wt::set_error("class %d: low_iou_threshold %g outside [0, 1]", c + 1, li);
+            return WT_ERR_INVALID;
+        }
+    }
+    return WT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t wt_track_streams_byte_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets,
+                                       const wt_track_params* params, const double* low_score_threshold,
+                                       const double* low_iou_threshold) {
+    int cap, capN, lds_cost; bool cost_g; size_t lds;
+    if (check_byte_thresholds(params, low_score_threshold, low_iou_threshold) != WT_OK) return 0;
+    if (pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams) != WT_OK) return 0;
+    return carve_ws(nullptr, n_dets, n_frames, n_streams, params->n_classes, cap, capN, cost_g).bytes +
+           carve_state(nullptr, n_streams, params->n_classes, cap).bytes +
+           carve_byte(nullptr, n_streams, params->n_classes, cap).bytes + 256;
+}
+
+int wt_track_streams_byte_dev(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                              const double* score, const int32_t* category,
+                              int64_t n_frames, const int64_t* frame_det_offsets,
+                              int32_t n_streams, const int64_t* stream_frame_offsets,
+                              const double* clip_w, const double* clip_h, int64_t max_frame_dets,
+                              const wt_track_params* params, const double* low_score_threshold,
+                              const double* low_iou_threshold, int64_t id_base,
+                              int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                              int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
+                              void* workspace, size_t workspace_bytes, void* stream_) {
+    WT_TRY(check_byte_thresholds(params, low_score_threshold, low_iou_threshold));
+    WT_TRY(wt::ensure_device());
+    hipStream_t stream = (hipStream_t)stream_;
+    int cap, capN, lds_cost; bool cost_g; size_t lds;
+    WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
+    const int C = params->n_classes;
+    if (n_streams <= 0 || n_frames <= 0) {
+        WT_HIP(hipMemsetAsync(n_out_dev, 0, sizeof(int64_t), stream));
+        WT_HIP(hipMemsetAsync(n_births_dev, 0, sizeof(int64_t), stream));
+        return WT_OK;
+    }
+    char* base = wt::align_ptr(workspace);
+    Workspace ws = carve_ws(base, n_dets, n_frames, n_streams, C, cap, capN, cost_g);
+    State st = carve_state(base + ws.bytes, n_streams, C, cap);
+    ByteExtra bx = carve_byte(base + ws.bytes + st.bytes, n_streams, C, cap);
+    if (!workspace || workspace_bytes < ws.bytes + st.bytes + bx.bytes + 256) {
+        wt::set_error("tracking workspace too small: need %zu bytes, have %zu", ws.bytes + st.bytes + bx.bytes + 256, workspace_bytes);
+        return WT_ERR_CAPACITY;
+    }
+    bx.h_low_score = low_score_threshold;
+    bx.h_low_iou = low_iou_threshold;
+    return run_tracking(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
+                        clip_w, clip_h, params, id_base, out_frame, out_category, out_bbox4, out_score, out_object_id,
+                        n_out_dev, n_births_dev, ws, st, 0, cap, capN, lds_cost, cost_g, lds, stream, &bx);
 }
 
 /* ---- streaming form: the trackers persist in `state` between chunks of frames ---- */
@@ -668,14 +863,15 @@ int wt_track_global_ids_dev(const void* state, size_t state_bytes, int32_t n_str
     return WT_OK;
 }
 
-int wt_track_streams_host(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
-                          const double* score, const int32_t* category,
-                          int64_t n_frames, const int64_t* frame_det_offsets,
-                          int32_t n_streams, const int64_t* stream_frame_offsets,
-                          const double* clip_w, const double* clip_h,
-                          const wt_track_params* params, int64_t id_base,
-                          int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
-                          int64_t* out_object_id, int64_t* n_out, int64_t* n_births) {
+// host form of wt_track_streams_dev (low_score == nullptr) or of wt_track_streams_byte_dev
+static int track_streams_host(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                              const double* score, const int32_t* category,
+                              int64_t n_frames, const int64_t* frame_det_offsets,
+                              int32_t n_streams, const int64_t* stream_frame_offsets,
+                              const double* clip_w, const double* clip_h,
+                              const wt_track_params* params, const double* low_score, const double* low_iou, int64_t id_base,
+                              int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                              int64_t* out_object_id, int64_t* n_out, int64_t* n_births) {
     WT_TRY(wt::ensure_device());
     *n_out = 0;
     *n_births = 0;
@@ -708,14 +904,22 @@ int wt_track_streams_host(int64_t n_dets, const double* x, const double* y, cons
     WT_TRY(dch.upload(clip_h ? clip_h : zeros.data(), 8 * (size_t)n_streams));
     WT_TRY(of.alloc(8 * (nd + 1))); WT_TRY(oc.alloc(4 * (nd + 1))); WT_TRY(ob.alloc(32 * (nd + 1)));
     WT_TRY(os.alloc(8 * (nd + 1))); WT_TRY(oi.alloc(8 * (nd + 1))); WT_TRY(dn.alloc(16));
-    const size_t wsb = wt_track_streams_workspace(n_dets, n_frames, n_streams, max_frame, params);
+    const size_t wsb = low_score ? wt_track_streams_byte_workspace(n_dets, n_frames, n_streams, max_frame, params, low_score, low_iou)
+                                 : wt_track_streams_workspace(n_dets, n_frames, n_streams, max_frame, params);
     if (!wsb) return WT_ERR_CAPACITY;
     WT_TRY(dws.alloc(wsb));
-    WT_TRY(wt_track_streams_dev(n_dets, dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>(),
-                                ds.as<double>(), dc.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams,
-                                dso.as<int64_t>(), dcw.as<double>(), dch.as<double>(), max_frame, params, id_base,
-                                of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(), oi.as<int64_t>(),
-                                dn.as<int64_t>(), dn.as<int64_t>() + 1, dws.p, wsb, nullptr));
+    if (low_score)
+        WT_TRY(wt_track_streams_byte_dev(n_dets, dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>(),
+                                         ds.as<double>(), dc.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams,
+                                         dso.as<int64_t>(), dcw.as<double>(), dch.as<double>(), max_frame, params, low_score, low_iou,
+                                         id_base, of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(),
+                                         oi.as<int64_t>(), dn.as<int64_t>(), dn.as<int64_t>() + 1, dws.p, wsb, nullptr));
+    else
+        WT_TRY(wt_track_streams_dev(n_dets, dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>(),
+                                    ds.as<double>(), dc.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams,
+                                    dso.as<int64_t>(), dcw.as<double>(), dch.as<double>(), max_frame, params, id_base,
+                                    of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(), oi.as<int64_t>(),
+                                    dn.as<int64_t>(), dn.as<int64_t>() + 1, dws.p, wsb, nullptr));
     WT_HIP(hipDeviceSynchronize());
     int64_t res[2] = {0, 0};
     WT_HIP(hipMemcpy(res, dn.p, 16, hipMemcpyDeviceToHost));
@@ -734,6 +938,34 @@ int wt_track_streams_host(int64_t n_dets, const double* x, const double* y, cons
         WT_HIP(hipMemcpy(out_object_id, oi.p, 8 * k, hipMemcpyDeviceToHost));
     }
     return WT_OK;
+}
+
+int wt_track_streams_host(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                          const double* score, const int32_t* category,
+                          int64_t n_frames, const int64_t* frame_det_offsets,
+                          int32_t n_streams, const int64_t* stream_frame_offsets,
+                          const double* clip_w, const double* clip_h,
+                          const wt_track_params* params, int64_t id_base,
+                          int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                          int64_t* out_object_id, int64_t* n_out, int64_t* n_births) {
+    return track_streams_host(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
+                              clip_w, clip_h, params, nullptr, nullptr, id_base, out_frame, out_category, out_bbox4, out_score,
+                              out_object_id, n_out, n_births);
+}
+
+int wt_track_streams_byte_host(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                               const double* score, const int32_t* category,
+                               int64_t n_frames, const int64_t* frame_det_offsets,
+                               int32_t n_streams, const int64_t* stream_frame_offsets,
+                               const double* clip_w, const double* clip_h,
+                               const wt_track_params* params, const double* low_score_threshold,
+                               const double* low_iou_threshold, int64_t id_base,
+                               int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                               int64_t* out_object_id, int64_t* n_out, int64_t* n_births) {
+    WT_TRY(check_byte_thresholds(params, low_score_threshold, low_iou_threshold));      // before any device call
+    return track_streams_host(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
+                              clip_w, clip_h, params, low_score_threshold, low_iou_threshold, id_base, out_frame, out_category,
+                              out_bbox4, out_score, out_object_id, n_out, n_births);
 }
 
 }  // extern "C"

@@ -74,6 +74,36 @@ class DeviceTracker(object):
                     object_id=self.out_id[:n_out].cpu().numpy()), births
 
 
+class DeviceTrackerByte(DeviceTracker):
+    """wt_track_streams_byte_dev (second association with low-score detections) on tensors already in HBM; `score_threshold` is
+    the high threshold, and `packed` holds the detections down to `low_score_threshold`."""
+
+    def __init__(self, packed, iou_threshold, max_age, min_hits, score_threshold, low_score_threshold, low_iou_threshold, device='cuda'):
+        DeviceTracker.__init__(self, packed, iou_threshold, max_age, min_hits, score_threshold, device)
+        from .tracking.utils import per_class
+        self.low_score = _lib.as_f64(per_class(low_score_threshold, self.params.n_classes, 'low_score_threshold'))
+        self.low_iou = _lib.as_f64(per_class(low_iou_threshold, self.params.n_classes, 'low_iou_threshold'))
+        ws = self.lib.wt_track_streams_byte_workspace(C.c_int64(self.n_dets), C.c_int64(self.n_frames), C.c_int32(self.n_streams),
+                                                      C.c_int64(self.max_frame), C.byref(self.params), _lib.ptr(self.low_score),
+                                                      _lib.ptr(self.low_iou))
+        if ws == 0:
+            raise _lib.WaymoTrackError('wt_track_streams_byte_workspace: ' + self.lib.wt_last_error().decode())
+        self.ws_bytes = int(ws)
+        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=torch.device(device))
+
+    def run(self, id_base=0):
+        """Enqueue one tracking pass on the current stream (no host synchronisation)."""
+        rc = self.lib.wt_track_streams_byte_dev(
+            C.c_int64(self.n_dets), _dp(self.x), _dp(self.y), _dp(self.w), _dp(self.h), _dp(self.score),
+            _dp(self.category), C.c_int64(self.n_frames), _dp(self.frame_off), C.c_int32(self.n_streams),
+            _dp(self.stream_off), _dp(self.clip_w), _dp(self.clip_h), C.c_int64(self.max_frame), C.byref(self.params),
+            _lib.ptr(self.low_score), _lib.ptr(self.low_iou),
+            C.c_int64(id_base), _dp(self.out_frame), _dp(self.out_category), _dp(self.out_bbox), _dp(self.out_score),
+            _dp(self.out_id), _dp(self.counts), C.c_void_p(self.counts.data_ptr() + 8), _dp(self.workspace),
+            C.c_size_t(self.ws_bytes), _stream())
+        _lib.check(rc, 'wt_track_streams_byte_dev')
+
+
 class DeviceEnsemble(object):
     """wt_ensemble_groups_dev on tensors already in HBM."""
 

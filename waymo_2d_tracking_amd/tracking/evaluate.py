@@ -3,7 +3,7 @@
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
         [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--low-score-grid 0.2,0.4 --low-iou-grid 0.3,0.5] [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
@@ -864,6 +864,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     K = |score| x |iou| x |max_age| x |min_hits| settings - and the best point is read off per class for each
     (max_age, min_hits); no product over classes is tracked.  Best = highest ALL MOTA at the level; ties go to the setting that
     comes first in grid order (max_age, min_hits, then per class score, iou).
+    Optionally 'low_score' and 'low_iou' (the tracker's second association, utils.track_packed_byte; defaults [] = off and [0.5]): every
+    (score, iou) point is tracked under all (low_score, low_iou) pairs, a low score above the point's score clamped to it (that point is
+    plain tracking); the pairs are the axes just inside (score, iou), every setting row carries 'low_score' and 'low_iou', and the
+    per-class pick ranges over them too - the second association is per class like the first.
     identity=True scores every setting with evaluate_identity as well and adds 'IDF1' (with 'id_counts') to every ranked setting.
     rank_by='idf1' (implies identity): per (max_age, min_hits) each class takes the grid point with its own highest class IDF1, the
     combined row reports ALL from the summed identity counts and the rows are ranked by it (this is not the
@@ -904,12 +908,21 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     smoothing = smooth_windows != [0]               # the innermost axes: every refined result smoothed under every (window, sigma)
     smooth_kernel = grid.get('smooth_kernel', 'gaussian')
     smooth_jobs = [{'window': w, 'sigma': v, 'kernel': smooth_kernel} for w in smooth_windows for v in smooth_sigmas] if smoothing else [None]
+    low_scores, low_ious = [float(v) for v in grid.get('low_score', [])], [float(v) for v in grid.get('low_iou', [0.5])]
+    second = bool(low_scores)                       # the axes just inside (score, iou): the tracker's second association (utils.track_packed_byte)
+    low_jobs = [(s, v) for s in low_scores for v in low_ious] if second else [None]
     for max_age in grid['max_age']:
         for min_hits in grid['min_hits']:
             for score in grid['score']:
-                for iou in grid['iou']:
-                    out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
+                for iou, low_job in ((v, j) for v in grid['iou'] for j in low_jobs):
                     base = {'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)}
+                    if second:                       # a low score above the point's high score is clamped to it: that point is plain tracking
+                        low = min(low_job[0], float(score))
+                        out, _ = T.track_packed_byte(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes,
+                                                     [low] * n_classes, [low_job[1]] * n_classes)
+                        base.update(low_score=low, low_iou=low_job[1])
+                    else:
+                        out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
                     linked = [out]
                     if stitching:
                         from .stitch import stitch_tracks
@@ -952,7 +965,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou']) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
+    per_mm = len(grid['score']) * len(grid['iou']) * len(low_jobs) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
     for lv in LEVELS:
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
@@ -988,6 +1001,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 score_thr[c - 1], iou_thr[c - 1] = settings[pick[c]]['score'], settings[pick[c]]['iou']
             combos.append({'max_age': settings[g]['max_age'], 'min_hits': settings[g]['min_hits'], 'score_threshold': score_thr,
                            'iou_threshold': iou_thr, 'MOTA': mota, 'counts': total})
+            if second:                                                # classes that are not evaluated have nothing between low and high
+                combos[-1]['low_score_threshold'], combos[-1]['low_iou_threshold'] = list(score_thr), [low_ious[0]] * n_classes
+                for c in classes:
+                    combos[-1]['low_score_threshold'][c - 1], combos[-1]['low_iou_threshold'][c - 1] = settings[pick[c]]['low_score'], settings[pick[c]]['low_iou']
             if refining:                                              # classes that are not evaluated are not refined either
                 combos[-1]['interp_gap'], combos[-1]['min_len'] = [0] * n_classes, [1] * n_classes
                 for c in classes:
@@ -1028,6 +1045,8 @@ def flag_line(setting):
     join = lambda v: ','.join(repr(float(x)) for x in v)
     line = '--score-threshold=%s --iou-threshold=%s --max-age=%d --min-hits=%d' % (
         join(setting['score_threshold']), join(setting['iou_threshold']), setting['max_age'], setting['min_hits'])
+    if 'low_score_threshold' in setting:
+        line += ' --low-score-threshold=%s --low-iou-threshold=%s' % (join(setting['low_score_threshold']), join(setting['low_iou_threshold']))
     if 'link_gap' in setting:
         line += ' --link-gap=%s --link-iou=%s' % (','.join('%d' % v for v in setting['link_gap']), join(setting['link_iou']))
         if setting.get('link_motion', 'hold') != 'hold':
@@ -1087,6 +1106,9 @@ def build_parser():
     parser.add_argument('--iou-grid', default='0.0,0.01,0.1,0.3')
     parser.add_argument('--max-age', default='1,2,3')
     parser.add_argument('--min-hits', default='0,1')
+    parser.add_argument('--low-score-grid', default='', help='second association of the tracker: detections from this score on may continue an unmatched track '
+                                                             '(tracking/track.py --low-score-threshold; a value above the point\'s score is clamped to it; empty = off)')
+    parser.add_argument('--low-iou-grid', default='0.5', help='second association: lowest IoU of a low-score detection and its track; read when --low-score-grid is set')
     parser.add_argument('--gap-grid', default='0', help='track refinement: gaps of up to this many frames are interpolated (tracking/refine.py)')
     parser.add_argument('--min-len-grid', default='1', help='track refinement: tracks observed in fewer frames are dropped')
     parser.add_argument('--link-gap-grid', default='0', help='track stitching: tracks are linked across up to this many frames (tracking/stitch.py)')
@@ -1118,7 +1140,8 @@ def main(argv=None):
                 'dedup_frames': [int(v) for v in args.dedup_frames_grid.split(',')], 'dedup_iou': _grid_values(args.dedup_iou_grid),
                 'dedup_frac': args.dedup_frac,
                 'smooth_window': [int(v) for v in args.smooth_window_grid.split(',')], 'smooth_sigma': _grid_values(args.smooth_sigma_grid),
-                'smooth_kernel': args.smooth_kernel}
+                'smooth_kernel': args.smooth_kernel,
+                'low_score': _grid_values(args.low_score_grid) if args.low_score_grid else [], 'low_iou': _grid_values(args.low_iou_grid)}
         identity = args.identity or args.rank_by == 'idf1'
         hota = args.hota or args.rank_by == 'hota'
         res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota)

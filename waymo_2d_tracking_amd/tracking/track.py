@@ -6,6 +6,10 @@
 All (segment, camera) streams are tracked in one GPU call (utils.track_all) instead of the sequential loop of
 track.py:43-47; `--ground-truth` is accepted but, like in the reference, its content is never used (the file
 is not required to exist).
+
+Beyond the reference: `--low-score-threshold=0.3,0.3,1.0,0.3 [--low-iou-threshold 0.5]` lets detections between the two score
+thresholds continue tracks that no detection above `--score-threshold` matched (second association; one
+process only), and the post-passes of refine.py, stitch.py, dedup.py and smooth.py follow when their flags ask for them.
 """
 import argparse
 import json
@@ -63,6 +67,12 @@ def build_parser():
                         help='width of the gaussian weights in frames (one value, or one per class); read when --smooth-window is set')
     parser.add_argument("--smooth-kernel", choices=('gaussian', 'box'), default='gaussian',
                         help='the weights over the window: exp(-d^2 / (2 sigma^2)), or all equal')
+    parser.add_argument("--low-score-threshold", type=_floats, default=None,
+                        help='second association: detections from this score on (one value per class, none above --score-threshold) may continue '
+                             'a track that no detection above --score-threshold matched; they never start one (absent = off)')
+    parser.add_argument("--low-iou-threshold", type=_floats, default=[0.5],
+                        help='lowest IoU of a low-score detection and the track it continues (one value, or one per class); '
+                             'read when --low-score-threshold is set')
     parser.add_argument("--segment-id", type=str, help='track only a single segment')
     parser.add_argument("--python-io", action='store_true',
                         help='parse / write JSON with the Python json module (default: native reader / writer of libwaymotrack)')
@@ -111,16 +121,38 @@ def refined(args, packed, out):
 post_passes = refined
 
 
+def second_association(args):
+    """Whether the flags ask for the second association with low-score detections (utils.track_packed_byte)."""
+    return args.low_score_threshold is not None
+
+
+def read_threshold(args):
+    """The score thresholds the detections file is read with: the low ones when the second association is on."""
+    return args.low_score_threshold if second_association(args) else args.score_threshold
+
+
+def tracked_byte(args, packed):
+    """The tracker's rows with the second association; the id counter moves on as in track_all."""
+    from . import utils as T
+    out, births = T.track_packed_byte(packed, args.iou_threshold, args.max_age, args.min_hits, args.score_threshold,
+                                      args.low_score_threshold, args.low_iou_threshold, T._GLOBAL_IDS['next'])
+    T._GLOBAL_IDS['next'] += births
+    return out
+
+
 def main_native(args):
     """file -> SoA in HBM -> file without per-row Python objects (wt_detfile_read / wt_tracks_write_json)."""
     from . import utils as T
-    nat = T.NativeDetFile(args.input, args.score_threshold)
+    nat = T.NativeDetFile(args.input, read_threshold(args))
     packed = nat.packed()
     start_time = time.time()
     for segment_id in dict.fromkeys(s for s, _ in packed['stream_keys']):
         print(segment_id)
-    out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
-    T._GLOBAL_IDS['next'] += births
+    if second_association(args):
+        out = tracked_byte(args, packed)
+    else:
+        out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
+        T._GLOBAL_IDS['next'] += births
     print("duration: %.2fs" % (time.time() - start_time))
     nat.write_tracks(args.output, refined(args, packed, out))
     nat.close()
@@ -168,17 +200,31 @@ def main(argv=None):
     print(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    if second_association(args):
+        if world > 1:
+            raise SystemExit('--low-score-threshold is not available under torchrun (world size %d): the second association '
+                             'has no sharded form yet; run it in one process' % world)
+        from .utils import per_class
+        n_classes = len(args.iou_threshold)
+        if len(args.score_threshold) != n_classes:
+            raise SystemExit('--score-threshold and --iou-threshold need one value per class')
+        args.low_score_threshold = per_class(args.low_score_threshold, n_classes, '--low-score-threshold')
+        args.low_iou_threshold = per_class(args.low_iou_threshold, n_classes, '--low-iou-threshold')
     if world > 1:
         return main_sharded(args, world, rank)
     if not args.python_io and not args.segment_id:
         return main_native(args)
-    predictions = read_data_file(args.input, args.score_threshold)
+    predictions = read_data_file(args.input, read_threshold(args))
     if args.segment_id:
         predictions = {k: v for k, v in predictions.items() if k in [args.segment_id]}
     start_time = time.time()
     for segment_id in predictions.keys():
         print(segment_id)
-    if refines(args) or stitches(args) or dedups(args) or smooths(args):
+    if second_association(args):
+        from . import utils as T
+        packed = T.pack_streams(predictions)
+        tracked_predictions = T.format_tracks(packed, refined(args, packed, tracked_byte(args, packed)))
+    elif refines(args) or stitches(args) or dedups(args) or smooths(args):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])

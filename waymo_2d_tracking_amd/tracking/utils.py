@@ -151,6 +151,50 @@ def track_packed(packed, iou_thresholds, max_age, min_hits, score_threshold=None
                 object_id=out_id[:k]), n_births.value
 
 
+def per_class(values, n_classes, name):
+    """One value for every class, or one per class."""
+    values = list(values)
+    if len(values) == 1:
+        values = values * n_classes
+    if len(values) != n_classes:
+        raise ValueError('%s needs one value or one per class (%d)' % (name, n_classes))
+    return values
+
+
+def track_packed_byte(packed, iou_thresholds, max_age, min_hits, score_threshold, low_score_threshold, low_iou_thresholds, id_base=0):
+    """track_packed with a second association over low-score detections (wt_track_streams_byte_host): detections from
+    `low_score_threshold` on are valid, those from `score_threshold` on associate first and found tracks, the ones between
+    may only continue a track the first association left unmatched (IoU at least `low_iou_thresholds`).  `packed` must hold the
+    detections down to the low threshold.  Returns what track_packed returns."""
+    lib = _lib.lib()
+    n = int(packed['x'].size)
+    params, keep = make_params(max_age, min_hits, score_threshold, iou_thresholds)
+    low_score = _lib.as_f64(per_class(low_score_threshold, params.n_classes, 'low_score_threshold'))
+    low_iou = _lib.as_f64(per_class(low_iou_thresholds, params.n_classes, 'low_iou_thresholds'))
+    if n and (packed['category'].min() < 1 or packed['category'].max() > params.n_classes):
+        raise IndexError('category_id outside 1..%d (thresholds are indexed by category_id-1)' % params.n_classes)
+    out_frame = np.zeros(n + 1, np.int64)
+    out_cat = np.zeros(n + 1, np.int32)
+    out_bbox = np.zeros((n + 1, 4), np.float64)
+    out_score = np.zeros(n + 1, np.float64)
+    out_id = np.zeros(n + 1, np.int64)
+    n_out = C.c_int64(0)
+    n_births = C.c_int64(0)
+    rc = lib.wt_track_streams_byte_host(
+        C.c_int64(n), _lib.ptr(packed['x']), _lib.ptr(packed['y']), _lib.ptr(packed['w']), _lib.ptr(packed['h']),
+        _lib.ptr(packed['score']), _lib.ptr(packed['category']),
+        C.c_int64(packed['frame_det_offsets'].size - 1), _lib.ptr(packed['frame_det_offsets']),
+        C.c_int32(packed['stream_frame_offsets'].size - 1), _lib.ptr(packed['stream_frame_offsets']),
+        _lib.ptr(packed['clip_w']), _lib.ptr(packed['clip_h']), C.byref(params), _lib.ptr(low_score), _lib.ptr(low_iou),
+        C.c_int64(id_base),
+        _lib.ptr(out_frame), _lib.ptr(out_cat), _lib.ptr(out_bbox), _lib.ptr(out_score), _lib.ptr(out_id),
+        C.byref(n_out), C.byref(n_births))
+    _lib.check(rc, 'wt_track_streams_byte_host')
+    k = n_out.value
+    return dict(frame=out_frame[:k], category=out_cat[:k], bbox=out_bbox[:k], score=out_score[:k],
+                object_id=out_id[:k]), n_births.value
+
+
 def format_tracks(packed, out):
     """Output arrays -> the list of dicts of utils.py:52-58 (tracking JSON rows)."""
     frame_ids = packed['frame_ids']
