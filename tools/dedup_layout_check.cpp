@@ -6,19 +6,7 @@
 // returns 0 when every answer is the expected one.  No device is touched.
 #include "../waymo_2d_tracking_amd/csrc/dedup_host.h"
 
-#include <cmath>
-#include <string>
-
-namespace wt {
-static char g_error[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-int hip_fail(hipError_t, const char* what) { set_error("%s", what); return WT_ERR_HIP; }
-}  // namespace wt
+#include "layout_check_common.h"
 
 namespace {
 
@@ -30,24 +18,12 @@ struct Case {                                   // two results over two streams 
     std::vector<int32_t> job_result = {0, 1}, min_frames = {0, 1, 2, 3, 0, 0, 0, 0};
     std::vector<double> iou = {0.7, 0.0, -1.0, 2.0, 0.5, 0.5, 0.5, INFINITY}, frac = {0.0, 1.0, 0.5, 5e-324, 0.5, 0.5, 0.5, -0.0};
     wt::DedupInput in() const {
-        return {5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), score.data(), cat.data(), local.data(),
-                n_traj.data(), 2, job_result.data(), min_frames.data(), iou.data(), frac.data(), 4};
+        return {{5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), score.data(), cat.data(), local.data(),
+                 n_traj.data(), 4}, 2, job_result.data(), min_frames.data(), iou.data(), frac.data()};
     }
 };
 
-int failures = 0;
-
-void report(const char* name, int rc, bool ok) {
-    printf("%-34s rc %d  %s%s\n", name, rc, wt::g_error, ok ? "" : "   <-- UNEXPECTED");
-    failures += !ok;
-}
-
-void expect(const char* name, const Case& c, int want, const char* text) {
-    int64_t max_traj = -1, total = -1;
-    wt::g_error[0] = 0;
-    const int rc = wt::check_dedup_layout(c.in(), &max_traj, &total);
-    report(name, rc, rc == want && (want == WT_OK ? (max_traj == 2 && total == 6) : std::string(wt::g_error).find(text) != std::string::npos));
-}
+void expect(const char* name, const Case& c, int want, const char* text) { expect_input(name, c.in(), wt::check_dedup_layout, want, text); }
 
 }  // namespace
 
@@ -83,30 +59,20 @@ int main() {
         Case d;
         wt::DedupInput in = d.in();
         in.job_dup_frac = nullptr;
-        int64_t a, b;
-        wt::g_error[0] = 0;
-        const int rc = wt::check_dedup_layout(in, &a, &b);
-        report("jobs without dup_frac", rc, rc == WT_ERR_INVALID && std::string(wt::g_error).find("wt_dedup_tracks_host: bad argument") != std::string::npos);
+        expect_input("jobs without dup_frac", in, wt::check_dedup_layout, WT_ERR_INVALID, "wt_dedup_tracks_host: bad argument");
     }
     {
         Case d;
         wt::DedupInput in = d.in();
         in.score = nullptr;
-        int64_t a, b;
-        wt::g_error[0] = 0;
-        const int rc = wt::check_dedup_layout(in, &a, &b);
-        report("rows without scores", rc, rc == WT_ERR_INVALID && std::string(wt::g_error).find("wt_dedup_tracks_host: bad argument") != std::string::npos);
+        expect_input("rows without scores", in, wt::check_dedup_layout, WT_ERR_INVALID, "wt_dedup_tracks_host: bad argument");
     }
     {
         Case d;
         wt::DedupInput in = d.in();
         in.n_jobs = 0;
         in.job_result = nullptr; in.job_min_frames = nullptr; in.job_dup_iou = nullptr; in.job_dup_frac = nullptr;
-        int64_t a = -1, b = -1;
-        wt::g_error[0] = 0;
-        const int rc = wt::check_dedup_layout(in, &a, &b);
-        report("no jobs", rc, rc == WT_OK && a == 2 && b == 6);
+        expect_input("no jobs", in, wt::check_dedup_layout, WT_OK, "");
     }
-    printf("%d unexpected\n", failures);
-    return failures ? 1 : 0;
+    return summary();
 }

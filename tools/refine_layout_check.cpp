@@ -6,18 +6,7 @@
 // returns 0 when every answer is the expected one.  No device is touched.
 #include "../waymo_2d_tracking_amd/csrc/refine_host.h"
 
-#include <string>
-
-namespace wt {
-static char g_error[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-int hip_fail(hipError_t, const char* what) { set_error("%s", what); return WT_ERR_HIP; }
-}  // namespace wt
+#include "layout_check_common.h"
 
 namespace {
 
@@ -28,21 +17,12 @@ struct Case {                                   // two results over two streams 
     std::vector<int32_t> cat = {1, 2, 1, 4, 1, 3, 3}, local = {0, 1, 0, 0, 1, 0, 0}, n_traj = {2, 2, 1, 1};
     std::vector<int32_t> job_result = {0, 1}, gap = {0, 1, 2, 3, 0, 0, 0, 0}, len = {1, 1, 2, 2, 1, 1, 1, 1}, mode = {0, 1};
     wt::RefineInput in() const {
-        return {5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), v.data(), cat.data(), local.data(),
-                n_traj.data(), 2, job_result.data(), gap.data(), len.data(), mode.data(), 4};
+        return {{5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), v.data(), cat.data(), local.data(),
+                 n_traj.data(), 4}, 2, job_result.data(), gap.data(), len.data(), mode.data()};
     }
 };
 
-int failures = 0;
-
-void expect(const char* name, const Case& c, int want, const char* text) {
-    int64_t max_traj = -1, total = -1;
-    wt::g_error[0] = 0;
-    const int rc = wt::check_refine_layout(c.in(), &max_traj, &total);
-    const bool ok = rc == want && (want == WT_OK ? (max_traj == 2 && total == 6) : std::string(wt::g_error).find(text) != std::string::npos);
-    printf("%-28s rc %d  %s%s\n", name, rc, wt::g_error, ok ? "" : "   <-- UNEXPECTED");
-    failures += !ok;
-}
+void expect(const char* name, const Case& c, int want, const char* text) { expect_input(name, c.in(), wt::check_refine_layout, want, text); }
 
 }  // namespace
 
@@ -65,6 +45,5 @@ int main() {
     { Case d; d.len[0] = 0; expect("min_len 0", d, WT_ERR_INVALID, "min_len of class 1"); }
     { Case d; d.mode[0] = 2; expect("unknown score mode", d, WT_ERR_INVALID, "score_mode"); }
     { Case d; d.n_traj = {0, 0, 0, 0}; expect("no trajectories declared", d, WT_ERR_INVALID, "trajectory index 0 outside"); }
-    printf("%d unexpected\n", failures);
-    return failures ? 1 : 0;
+    return summary();
 }

@@ -6,19 +6,7 @@
 // returns 0 when every answer is the expected one.  No device is touched.
 #include "../waymo_2d_tracking_amd/csrc/stitch_host.h"
 
-#include <cmath>
-#include <string>
-
-namespace wt {
-static char g_error[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-int hip_fail(hipError_t, const char* what) { set_error("%s", what); return WT_ERR_HIP; }
-}  // namespace wt
+#include "layout_check_common.h"
 
 namespace {
 
@@ -30,21 +18,12 @@ struct Case {                                   // two results over two streams 
     std::vector<int32_t> job_result = {0, 1}, link = {0, 1, 2, 3, 0, 0, 0, 0}, motion = {0, 1};
     std::vector<double> iou = {0.3, 0.0, -1.0, 2.0, 0.5, 0.5, 0.5, 0.5};
     wt::StitchInput in() const {
-        return {5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), cat.data(), local.data(),
-                n_traj.data(), 2, job_result.data(), link.data(), iou.data(), motion.data(), 4};
+        return {{5, 2, sfo.data(), 2, sro.data(), fro.data(), v.data(), v.data(), v.data(), v.data(), nullptr, cat.data(), local.data(),
+                 n_traj.data(), 4}, 2, job_result.data(), link.data(), iou.data(), motion.data()};
     }
 };
 
-int failures = 0;
-
-void expect(const char* name, const Case& c, int want, const char* text) {
-    int64_t max_traj = -1, total = -1;
-    wt::g_error[0] = 0;
-    const int rc = wt::check_stitch_layout(c.in(), &max_traj, &total);
-    const bool ok = rc == want && (want == WT_OK ? (max_traj == 2 && total == 6) : std::string(wt::g_error).find(text) != std::string::npos);
-    printf("%-32s rc %d  %s%s\n", name, rc, wt::g_error, ok ? "" : "   <-- UNEXPECTED");
-    failures += !ok;
-}
+void expect(const char* name, const Case& c, int want, const char* text) { expect_input(name, c.in(), wt::check_stitch_layout, want, text); }
 
 }  // namespace
 
@@ -73,13 +52,7 @@ int main() {
         Case d;
         wt::StitchInput in = d.in();
         in.job_link_iou = nullptr;
-        int64_t a, b;
-        wt::g_error[0] = 0;
-        const int rc = wt::check_stitch_layout(in, &a, &b);
-        const bool ok = rc == WT_ERR_INVALID && std::string(wt::g_error).find("wt_stitch_tracks_host: bad argument") != std::string::npos;
-        printf("%-32s rc %d  %s%s\n", "jobs without link_iou", rc, wt::g_error, ok ? "" : "   <-- UNEXPECTED");
-        failures += !ok;
+        expect_input("jobs without link_iou", in, wt::check_stitch_layout, WT_ERR_INVALID, "wt_stitch_tracks_host: bad argument");
     }
-    printf("%d unexpected\n", failures);
-    return failures ? 1 : 0;
+    return summary();
 }

@@ -20,7 +20,7 @@
 // The tables of the match (12 bytes per trajectory) live in LDS up to kLdsTraj trajectories, in the workspace beyond.
 // Compile with -ffp-contract=off: iou_dd is the IoU the metrics use, and dup_frac * min(n) is one multiplication.
 #include "eval_device.h"
-#include "eval_host.h"
+#include "tracks_device.h"
 #include "dedup_host.h"
 
 using namespace wtdev;
@@ -31,13 +31,9 @@ constexpr int kLdsTraj = 1024;                // trajectories of one (result, st
 constexpr int kTableBytes = 12;               // per trajectory: three int32
 constexpr int kUndecided = 0, kKept = 1, kSuppressed = 2;
 
-struct Layout {                               // device pointers
-    long long n_frames, n_rows, n_traj_total, max_traj;
-    int n_streams, r_sets, n_jobs, n_classes, lds_traj;
-    const int64_t *stream_frame_offsets, *set_row_offsets, *frame_row_offsets, *traj_offsets;
+struct Layout : TrackLayout {                 // device pointers
     const double* score;
-    const int32_t *category, *local;
-    const int32_t *job_result, *job_min_frames;
+    const int32_t* job_min_frames;
     const double *job_dup_iou, *job_dup_frac;
 };
 
@@ -74,42 +70,6 @@ Workspace carve(void* base, size_t n_jobs, size_t n_streams, size_t n_rows, size
     return w;
 }
 
-// The rows and trajectories of one (result r, stream s).  ok = false: the caller's numbers do not fit (status).
-struct Span {
-    int T;
-    long long f0, f1, base, rend, rs0, t0;
-    const int64_t* fro;
-    bool ok;
-};
-
-__device__ __forceinline__ Span span_of(const Layout& L, int r, int s) {
-    Span q;
-    q.ok = r >= 0 && r < L.r_sets;
-    if (!q.ok) return q;
-    const size_t rs = (size_t)r * L.n_streams + s;
-    const long long t0 = L.traj_offsets[rs], t1 = L.traj_offsets[rs + 1];
-    q.f0 = L.stream_frame_offsets[s];
-    q.f1 = L.stream_frame_offsets[s + 1];
-    q.base = L.set_row_offsets[r];
-    q.rend = L.set_row_offsets[r + 1];
-    q.fro = L.frame_row_offsets + (size_t)r * (size_t)(L.n_frames + 1);
-    q.ok = t0 >= 0 && t1 >= t0 && t1 - t0 <= L.max_traj && t1 <= L.n_traj_total && q.f0 >= 0 && q.f1 >= q.f0 && q.f1 <= L.n_frames &&
-           q.f1 - q.f0 < 0x3fffffffll && q.base >= 0 && q.rend >= q.base && q.rend <= L.n_rows;
-    if (!q.ok) return q;
-    q.T = (int)(t1 - t0);
-    q.t0 = t0;
-    q.rs0 = q.f1 > q.f0 ? q.base + q.fro[q.f0] : q.base;
-    q.ok = q.rs0 >= q.base && q.rs0 <= q.rend;
-    return q;
-}
-
-// rows [r0, r1) of slot f, or false when they leave the result's rows
-__device__ __forceinline__ bool slot_rows(const Span& q, long long f, long long* r0, long long* r1) {
-    *r0 = q.base + q.fro[f];
-    *r1 = q.base + q.fro[f + 1];
-    return *r0 >= q.rs0 && *r1 >= *r0 && *r1 <= q.rend && *r1 - q.rs0 < 0x7fffffffll;
-}
-
 __global__ __launch_bounds__(kWave) void dedup_summary_kernel(Layout L, Summary S, int* __restrict__ status) {
     const int lane = threadIdx.x & 63;
     const int r = (int)(blockIdx.x / (unsigned)L.n_streams), s = (int)(blockIdx.x % (unsigned)L.n_streams);
@@ -125,30 +85,21 @@ __global__ __launch_bounds__(kWave) void dedup_summary_kernel(Layout L, Summary 
     }
     wsync();
     int err = 0;
-    for (long long f = q.f0; f < q.f1; ++f) {
-        long long r0, r1;
-        if (!slot_rows(q, f, &r0, &r1)) { err = kErrCapacity; break; }
-        for (long long b = r0; b < r1; b += kWave) {                  // local indices are unique inside a slot: lanes never collide
-            const long long d = b + lane;
-            if (d >= r1) continue;
-            S.back[d] = 0; S.fwd[d] = 0; S.slot[d] = (int)(f - q.f0);
-            const int t = L.local[d];
-            if (t < 0 || t >= T) { err = kErrCapacity; continue; }
-            const size_t g = (size_t)q.t0 + t;
-            const int row = (int)(d - q.rs0), prev = S.last_row[g];
-            if (prev < 0) {
-                S.first_row[g] = row;
-                S.cls[g] = L.category[d];
-            } else {
-                S.back[d] = row - prev;
-                S.fwd[q.rs0 + prev] = row - prev;
-            }
-            S.last_row[g] = row;
-            S.n[g] = S.n[g] + 1;
-            S.ssum[g] = S.ssum[g] + L.score[d];                        // one by one in slot order
+    for_stream_rows(q, L.local, &err, [&](long long d, int t, int fo) {
+        S.back[d] = 0; S.fwd[d] = 0; S.slot[d] = fo;
+        const size_t g = (size_t)q.t0 + t;
+        const int row = (int)(d - q.rs0), prev = S.last_row[g];
+        if (prev < 0) {
+            S.first_row[g] = row;
+            S.cls[g] = L.category[d];
+        } else {
+            S.back[d] = row - prev;
+            S.fwd[q.rs0 + prev] = row - prev;
         }
-        wsync();
-    }
+        S.last_row[g] = row;
+        S.n[g] = S.n[g] + 1;
+        S.ssum[g] = S.ssum[g] + L.score[d];                            // one by one in slot order
+    });
     if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
 }
 
@@ -250,12 +201,8 @@ __global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, W
     const double* dup_iou = L.job_dup_iou + (size_t)job * C;
     const double* dup_frac = L.job_dup_frac + (size_t)job * C;
     int err = 0;
-    long long stream_end = q.rs0;
-    if (q.f1 > q.f0) {
-        stream_end = q.base + q.fro[q.f1];
-        if (stream_end < q.rs0 || stream_end > q.rend || stream_end - q.rs0 >= 0x7fffffffll) { err = kErrCapacity; stream_end = q.rs0; }
-    }
-    const Chains ch = {S.back, S.fwd, S.slot, q.rs0, stream_end};
+    const long long end = stream_end(q, &err);
+    const Chains ch = {S.back, S.fwd, S.slot, q.rs0, end};
     for (int t = lane; t < T; t += kWave) { state[t] = kUndecided; prop[t] = -1; pend[t] = 0; }
     wsync();
 
@@ -280,7 +227,7 @@ __global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, W
         ++rounds;
         for (long long f = q.f0; f < q.f1; ++f) {
             long long r0, r1;
-            if (!slot_rows(q, f, &r0, &r1) || r1 > stream_end) { err = kErrCapacity; break; }
+            if (!slot_rows(q, f, &r0, &r1) || r1 > end) { err = kErrCapacity; break; }
             for (long long b = r0; b + 1 < r1; b += kWave) {
                 const long long di = b + lane;
                 int ti = -1, ci = 0, si = kSuppressed;
@@ -359,7 +306,7 @@ __global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, W
             by = prop[t];
             const int c = S.cls[g0 + t];
             const int fa = S.first_row[g0 + t], fb = by >= 0 && by < T ? S.first_row[g0 + by] : -1;
-            if (c >= 1 && c <= C && fa >= 0 && fb >= 0 && q.rs0 + fa < stream_end && q.rs0 + fb < stream_end)
+            if (c >= 1 && c <= C && fa >= 0 && fb >= 0 && q.rs0 + fa < end && q.rs0 + fb < end)
                 m = count_matches(ch, B, q.rs0 + fa, q.rs0 + fb, dup_iou[c - 1]);
             else
                 err = kErrCapacity;
@@ -370,7 +317,7 @@ __global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, W
         n_dropped += gone;
     }
     for (int o = 32; o > 0; o >>= 1) n_dropped += __shfl_xor(n_dropped, o, kWave);
-    for (long long d = q.rs0 + lane; d < stream_end; d += kWave) {
+    for (long long d = q.rs0 + lane; d < end; d += kWave) {
         const int t = L.local[d];
         if (t < 0 || t >= T) { err = kErrCapacity; continue; }
         O.row_keep[lbase + d] = state[t] == kSuppressed ? 0 : 1;
@@ -379,28 +326,12 @@ __global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, W
     if (lane == 0) { O.dropped[p] = n_dropped; ws.rounds[p] = rounds; }
 }
 
-int check_args(const char* entry, int64_t n_frames, int32_t n_streams, int32_t r_sets, int64_t n_rows, int64_t n_traj_total, int64_t max_traj,
-               int32_t n_jobs, int32_t n_classes, bool others_ok) {
-    if (n_frames < 0 || n_streams < 0 || r_sets < 1 || n_rows < 0 || n_traj_total < 0 || max_traj < 0 || n_jobs < 0 || n_classes < 1 || !others_ok) {
-        wt::set_error("%s: bad argument", entry);
-        return WT_ERR_INVALID;
-    }
-    if ((uint64_t)n_jobs * (uint64_t)n_streams > 0x7fffffffull || (uint64_t)r_sets * (uint64_t)n_streams > 0x7fffffffull) {
-        wt::set_error("%s: %d jobs, %d results x %d streams in one call", entry, (int)n_jobs, (int)r_sets, (int)n_streams);
-        return WT_ERR_CAPACITY;
-    }
-    return WT_OK;
-}
+constexpr const char* kGridText = "%s: %d jobs, %d results x %d streams in one call";
 
-int launch(const char* entry, Layout L, const Boxes& B, const Outputs& O, int32_t* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+int launch(const char* entry, const Layout& L, const Boxes& B, const Outputs& O, int32_t* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     WT_TRY(wt::ensure_device());
-    L.max_traj = L.max_traj > 0 ? L.max_traj : 1;
-    L.lds_traj = (int)(L.max_traj < kLdsTraj ? L.max_traj : kLdsTraj);
     const Workspace ws = carve(wt::align_ptr(workspace), (size_t)L.n_jobs, (size_t)L.n_streams, (size_t)L.n_rows, (size_t)L.n_traj_total, (size_t)L.max_traj);
-    if (!workspace || workspace_bytes < ws.bytes + 256) {
-        wt::set_error("%s: workspace too small: need %zu bytes, have %zu", entry, ws.bytes + 256, workspace_bytes);
-        return WT_ERR_CAPACITY;
-    }
+    WT_TRY(wt::check_workspace_fits(entry, workspace, workspace_bytes, ws.bytes, WT_ERR_CAPACITY));
     WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
     const size_t P = (size_t)L.n_jobs * (size_t)L.n_streams, RS = (size_t)L.r_sets * (size_t)L.n_streams;
     const long long n_traj = (long long)L.n_jobs * L.n_traj_total, n_row = (long long)L.n_jobs * L.n_rows;
@@ -447,16 +378,16 @@ int wt_dedup_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stre
                         const double* job_dup_iou, const double* job_dup_frac, int32_t n_classes,
                         int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped,
                         int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
-    WT_TRY(check_args("wt_dedup_tracks_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
-                      stream_frame_offsets && set_row_offsets && frame_row_offsets && x && y && w && h && score && category && local && traj_offsets &&
-                          job_result && job_min_frames && job_dup_iou && job_dup_frac && out_keep && out_by && out_match && out_row_keep &&
-                          out_dropped && status_dev));
+    WT_TRY(wt::check_track_args("wt_dedup_tracks_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
+                                stream_frame_offsets && set_row_offsets && frame_row_offsets && x && y && w && h && score && category && local &&
+                                    traj_offsets && job_result && job_min_frames && job_dup_iou && job_dup_frac && out_keep && out_by && out_match &&
+                                    out_row_keep && out_dropped && status_dev,
+                                wt::grid_fits(n_jobs, n_streams) && wt::grid_fits(r_sets, n_streams), kGridText, (int)n_jobs, (int)r_sets, (int)n_streams));
+    const wt::TrackSet dev = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h, score,
+                              category, local, nullptr, n_classes};
     Layout L;
-    L.n_frames = n_frames; L.n_rows = n_rows; L.n_traj_total = n_traj_total; L.max_traj = max_traj;
-    L.n_streams = n_streams; L.r_sets = r_sets; L.n_jobs = n_jobs; L.n_classes = n_classes; L.lds_traj = 0;
-    L.stream_frame_offsets = stream_frame_offsets; L.set_row_offsets = set_row_offsets; L.frame_row_offsets = frame_row_offsets;
-    L.traj_offsets = traj_offsets; L.score = score; L.category = category; L.local = local;
-    L.job_result = job_result; L.job_min_frames = job_min_frames; L.job_dup_iou = job_dup_iou; L.job_dup_frac = job_dup_frac;
+    wt::fill_track_layout(&L, dev, n_rows, traj_offsets, n_traj_total, max_traj, n_jobs, job_result, kLdsTraj);
+    L.score = score; L.job_min_frames = job_min_frames; L.job_dup_iou = job_dup_iou; L.job_dup_frac = job_dup_frac;
     const Boxes B = {x, y, w, h};
     const Outputs O = {out_keep, out_by, out_match, out_row_keep, out_dropped};
     return launch("wt_dedup_tracks_dev", L, B, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
@@ -469,48 +400,33 @@ int wt_dedup_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* str
                          const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_min_frames,
                          const double* job_dup_iou, const double* job_dup_frac, int32_t n_classes,
                          int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped) {
-    const wt::DedupInput in = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h, score,
-                               category, local, n_traj, n_jobs, job_result, job_min_frames, job_dup_iou, job_dup_frac, n_classes};
+    const wt::DedupInput in = {{n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h, score,
+                                category, local, n_traj, n_classes}, n_jobs, job_result, job_min_frames, job_dup_iou, job_dup_frac};
     int64_t max_traj = 0, n_traj_total = 0;
     WT_TRY(wt::check_dedup_layout(in, &max_traj, &n_traj_total));
-    const size_t nr = (size_t)set_row_offsets[r_sets], nf = (size_t)(n_frames + 1), rs = (size_t)r_sets * (size_t)n_streams, J = (size_t)n_jobs;
-    const size_t nt = (size_t)n_traj_total, jc = J * (size_t)n_classes;
+    const size_t nr = (size_t)set_row_offsets[r_sets], J = (size_t)n_jobs, nt = (size_t)n_traj_total, jc = J * (size_t)n_classes;
     if ((J * nt && !(out_keep && out_by && out_match)) || (J * nr && !out_row_keep) || (J * (size_t)n_streams && !out_dropped)) {
         wt::set_error("wt_dedup_tracks_host: bad argument");
         return WT_ERR_INVALID;
     }
-    WT_TRY(check_args("wt_dedup_tracks_host", n_frames, n_streams, r_sets, (int64_t)nr, n_traj_total, max_traj, n_jobs, n_classes, true));
+    WT_TRY(wt::check_track_args("wt_dedup_tracks_host", n_frames, n_streams, r_sets, (int64_t)nr, n_traj_total, max_traj, n_jobs, n_classes, true,
+                                wt::grid_fits(n_jobs, n_streams) && wt::grid_fits(r_sets, n_streams), kGridText, (int)n_jobs, (int)r_sets, (int)n_streams));
     WT_TRY(wt::ensure_device());
-    std::vector<int64_t> traj_offsets(rs + 1, 0);
-    for (size_t i = 0; i < rs; ++i) traj_offsets[i + 1] = traj_offsets[i] + n_traj[i];
-    wt::DevBuf so, sr, fr, dx, dy, dw, dh, ds, dc, dl, dt, jr, jm, ji, jf, ok, ob, om, orr, od, status, dws;
-    WT_TRY(so.upload(stream_frame_offsets, 8 * (size_t)(n_streams + 1))); WT_TRY(sr.upload(set_row_offsets, 8 * (size_t)(r_sets + 1)));
-    WT_TRY(fr.upload(frame_row_offsets, 8 * (size_t)r_sets * nf));
-    WT_TRY(dx.upload(x, 8 * nr)); WT_TRY(dy.upload(y, 8 * nr)); WT_TRY(dw.upload(w, 8 * nr)); WT_TRY(dh.upload(h, 8 * nr));
-    WT_TRY(ds.upload(score, 8 * nr));
-    WT_TRY(dc.upload(category, 4 * nr)); WT_TRY(dl.upload(local, 4 * nr)); WT_TRY(dt.upload(traj_offsets.data(), 8 * (rs + 1)));
-    WT_TRY(jr.upload(job_result, 4 * J)); WT_TRY(jm.upload(job_min_frames, 4 * jc));
-    WT_TRY(ji.upload(job_dup_iou, 8 * jc)); WT_TRY(jf.upload(job_dup_frac, 8 * jc));
+    wt::StagedTrackSet st;
+    wt::DevBuf jm, ji, jf, ok, ob, om, orr, od, dws;
+    WT_TRY(st.upload(in, n_jobs, job_result));
+    WT_TRY(jm.upload(job_min_frames, 4 * jc)); WT_TRY(ji.upload(job_dup_iou, 8 * jc)); WT_TRY(jf.upload(job_dup_frac, 8 * jc));
     WT_TRY(ok.alloc(4 * J * nt)); WT_TRY(ob.alloc(4 * J * nt)); WT_TRY(om.alloc(4 * J * nt)); WT_TRY(orr.alloc(4 * J * nr));
-    WT_TRY(od.alloc(8 * J * (size_t)n_streams)); WT_TRY(status.alloc(16));
+    WT_TRY(od.alloc(8 * J * (size_t)n_streams));
     const size_t wsb = wt_dedup_tracks_workspace(n_jobs, n_streams, (int64_t)nr, n_traj_total, max_traj);
     WT_TRY(dws.alloc(wsb));
     Layout L;
-    L.n_frames = n_frames; L.n_rows = (long long)nr; L.n_traj_total = n_traj_total; L.max_traj = max_traj;
-    L.n_streams = n_streams; L.r_sets = r_sets; L.n_jobs = n_jobs; L.n_classes = n_classes; L.lds_traj = 0;
-    L.stream_frame_offsets = so.as<int64_t>(); L.set_row_offsets = sr.as<int64_t>(); L.frame_row_offsets = fr.as<int64_t>();
-    L.traj_offsets = dt.as<int64_t>(); L.score = ds.as<double>(); L.category = dc.as<int32_t>(); L.local = dl.as<int32_t>();
-    L.job_result = jr.as<int32_t>(); L.job_min_frames = jm.as<int32_t>(); L.job_dup_iou = ji.as<double>(); L.job_dup_frac = jf.as<double>();
-    const Boxes B = {dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>()};
+    st.fill(&L, n_traj_total, max_traj, n_jobs, kLdsTraj);
+    L.score = st.dev.score; L.job_min_frames = jm.as<int32_t>(); L.job_dup_iou = ji.as<double>(); L.job_dup_frac = jf.as<double>();
+    const Boxes B = {st.dev.x, st.dev.y, st.dev.w, st.dev.h};
     const Outputs O = {ok.as<int32_t>(), ob.as<int32_t>(), om.as<int32_t>(), orr.as<int32_t>(), od.as<int64_t>()};
-    WT_TRY(launch("wt_dedup_tracks_host", L, B, O, status.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_HIP(hipDeviceSynchronize());
-    int32_t st = 0;
-    WT_HIP(hipMemcpy(&st, status.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (st) {
-        wt::set_error("dedup kernel reported status %d (4 = counts or offsets that do not fit the rows)", (int)st);
-        return (int)st;
-    }
+    WT_TRY(launch("wt_dedup_tracks_host", L, B, O, st.status.as<int32_t>(), dws.p, wsb, nullptr));
+    WT_TRY(st.finish("dedup", "counts or offsets"));
     if (J * nt) {
         WT_HIP(hipMemcpy(out_keep, ok.p, 4 * J * nt, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(out_by, ob.p, 4 * J * nt, hipMemcpyDeviceToHost));
         WT_HIP(hipMemcpy(out_match, om.p, 4 * J * nt, hipMemcpyDeviceToHost));

@@ -12,7 +12,7 @@
 //             fillable gap at this slot in ascending index (ballot + popcount over chunks of 64 trajectories).
 // Compile with -ffp-contract=off: a fill is va + (vb - va) * (j / n) with every operation rounded on its own.
 #include "eval_device.h"
-#include "eval_host.h"
+#include "tracks_device.h"
 #include "refine_host.h"
 
 using namespace wtdev;
@@ -21,12 +21,8 @@ namespace {
 
 constexpr int kLdsTraj = 1024;                // trajectories of one (result, stream) up to which the tables stay in LDS
 
-struct Layout {                               // device pointers; what both walks read
-    long long n_frames, n_rows, n_traj_total, max_traj;
-    int n_streams, r_sets, n_jobs, n_classes, lds_traj;
-    const int64_t *stream_frame_offsets, *set_row_offsets, *frame_row_offsets, *traj_offsets;
-    const int32_t *category, *local;
-    const int32_t *job_result, *job_max_gap, *job_min_len;
+struct Layout : TrackLayout {                 // device pointers; what both walks read
+    const int32_t *job_max_gap, *job_min_len;
 };
 
 struct Workspace {                            // device pointers carved from one block
@@ -55,55 +51,19 @@ Workspace carve(void* base, size_t n_jobs, size_t n_streams, size_t n_rows, size
     return w;
 }
 
-// What one problem walks: its job, result, trajectory count and rows.  ok = false: the caller's numbers do not fit (status).
-struct Problem {
-    int j, s, r, T;
-    long long f0, f1, base, rend, rs0;
-    const int64_t* fro;
-    size_t tbase, lbase;
-    bool ok;
-};
-
-__device__ __forceinline__ Problem decode(const Layout& L, size_t p) {
-    Problem q;
-    decode_job_stream(p, L.n_streams, &q.j, &q.s);
-    q.r = L.job_result[q.j];
-    q.ok = q.r >= 0 && q.r < L.r_sets;
-    if (!q.ok) return q;
-    const size_t rs = (size_t)q.r * L.n_streams + q.s;
-    const long long t0 = L.traj_offsets[rs], t1 = L.traj_offsets[rs + 1];
-    q.f0 = L.stream_frame_offsets[q.s];
-    q.f1 = L.stream_frame_offsets[q.s + 1];
-    q.base = L.set_row_offsets[q.r];
-    q.rend = L.set_row_offsets[q.r + 1];
-    q.fro = L.frame_row_offsets + (size_t)q.r * (size_t)(L.n_frames + 1);
-    q.ok = t0 >= 0 && t1 >= t0 && t1 - t0 <= L.max_traj && t1 <= L.n_traj_total && q.f0 >= 0 && q.f1 >= q.f0 && q.f1 <= L.n_frames &&
-           q.base >= 0 && q.rend >= q.base && q.rend <= L.n_rows;
-    if (!q.ok) return q;
-    q.T = (int)(t1 - t0);
-    q.tbase = (size_t)q.j * (size_t)L.n_traj_total + (size_t)t0;
-    q.lbase = (size_t)q.j * (size_t)L.n_rows;
-    q.rs0 = q.f1 > q.f0 ? q.base + q.fro[q.f0] : q.base;
-    return q;
-}
-
-// rows [r0, r1) of slot f, or false when they leave the result's rows
-__device__ __forceinline__ bool slot_rows(const Problem& q, long long f, long long* r0, long long* r1) {
-    *r0 = q.base + q.fro[f];
-    *r1 = q.base + q.fro[f + 1];
-    return *r0 >= q.rs0 && *r1 >= *r0 && *r1 <= q.rend && *r1 - q.rs0 < 0x7fffffffll;
-}
-
 __global__ __launch_bounds__(kWave) void refine_link_kernel(Layout L, const double* __restrict__ score, Workspace ws, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const size_t p = blockIdx.x;
-    const Problem q = decode(L, p);
+    int j, s;
+    decode_job_stream(p, L.n_streams, &j, &s);
+    const Span q = span_of(L, L.job_result[j], s);
     if (!q.ok) {
         if (lane == 0) { atomicMax(status, kErrCapacity); ws.emitted[p] = 0; }
         return;
     }
     const int T = q.T, C = L.n_classes;
+    const size_t tbase = (size_t)j * (size_t)L.n_traj_total + (size_t)q.t0, lbase = (size_t)j * (size_t)L.n_rows;
     const bool in_lds = T <= L.lds_traj;
     const size_t stride = in_lds ? (size_t)L.lds_traj : (size_t)L.max_traj;
     double* sum = in_lds ? reinterpret_cast<double*>(smem) : ws.tab_d + p * stride;
@@ -114,45 +74,35 @@ __global__ __launch_bounds__(kWave) void refine_link_kernel(Layout L, const doub
     int* cls = last + 4 * stride;
     for (int t = lane; t < T; t += kWave) { sum[t] = 0.; last[t] = -1; last_slot[t] = -1; cnt[t] = 0; fill[t] = 0; cls[t] = 0; }
     wsync();
-    const int32_t* gaps = L.job_max_gap + (size_t)q.j * C;
-    const int32_t* lens = L.job_min_len + (size_t)q.j * C;
+    const int32_t* gaps = L.job_max_gap + (size_t)j * C;
+    const int32_t* lens = L.job_min_len + (size_t)j * C;
     int err = 0;
-    for (long long f = q.f0; f < q.f1; ++f) {
-        const int fo = (int)(f - q.f0);
-        long long r0, r1;
-        if (!slot_rows(q, f, &r0, &r1)) { err = kErrCapacity; break; }
-        for (long long b = r0; b < r1; b += kWave) {                  // local indices are unique inside a slot: lanes never collide
-            const long long d = b + lane;
-            if (d >= r1) continue;
-            ws.nxt_row[q.lbase + d] = -1;
-            ws.nxt_slot[q.lbase + d] = -1;
-            const int t = L.local[d];
-            if (t < 0 || t >= T) { err = kErrCapacity; continue; }
-            const int prev = last[t];
-            if (prev < 0) {
-                cls[t] = L.category[d];
-                sum[t] = score[d];
-            } else {
-                ws.nxt_row[q.lbase + q.rs0 + prev] = (int)(d - q.rs0);
-                ws.nxt_slot[q.lbase + q.rs0 + prev] = fo;
-                const int c = cls[t], holes = fo - last_slot[t] - 1;
-                if (c >= 1 && c <= C && holes >= 1 && holes <= gaps[c - 1]) fill[t] += holes;
-                sum[t] = sum[t] + score[d];                           // ascending slot order: part of the definition
-            }
-            last[t] = (int)(d - q.rs0);
-            last_slot[t] = fo;
-            cnt[t] += 1;
+    for_stream_rows(q, L.local, &err, [&](long long d, int t, int fo) {
+        ws.nxt_row[lbase + d] = -1;
+        ws.nxt_slot[lbase + d] = -1;
+        const int prev = last[t];
+        if (prev < 0) {
+            cls[t] = L.category[d];
+            sum[t] = score[d];
+        } else {
+            ws.nxt_row[lbase + q.rs0 + prev] = (int)(d - q.rs0);
+            ws.nxt_slot[lbase + q.rs0 + prev] = fo;
+            const int c = cls[t], holes = fo - last_slot[t] - 1;
+            if (c >= 1 && c <= C && holes >= 1 && holes <= gaps[c - 1]) fill[t] += holes;
+            sum[t] = sum[t] + score[d];                               // ascending slot order: part of the definition
         }
-        wsync();
-    }
+        last[t] = (int)(d - q.rs0);
+        last_slot[t] = fo;
+        cnt[t] += 1;
+    });
     long long emit = 0;
     for (int t = lane; t < T; t += kWave) {
         const int c = cls[t], n = cnt[t];
         const bool known = c >= 1 && c <= C;
         if (n > 0 && !known) err = kErrCapacity;
         const bool kept = n > 0 && known && n >= lens[c - 1];
-        ws.tgap[q.tbase + t] = kept ? gaps[c - 1] : -1;
-        ws.tmean[q.tbase + t] = n > 0 ? sum[t] / (double)n : 0.;
+        ws.tgap[tbase + t] = kept ? gaps[c - 1] : -1;
+        ws.tmean[tbase + t] = n > 0 ? sum[t] / (double)n : 0.;
         if (kept) emit += (long long)n + fill[t];
     }
     for (int o = 32; o > 0; o >>= 1) emit += __shfl_xor(emit, o, kWave);
@@ -199,12 +149,15 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
     const int lane = threadIdx.x & 63;
     const unsigned long long lt = lanemask_lt();
     const size_t p = blockIdx.x;
-    const Problem q = decode(L, p);
+    int j, s;
+    decode_job_stream(p, L.n_streams, &j, &s);
+    const Span q = span_of(L, L.job_result[j], s);
     if (!q.ok) {
         if (lane == 0) atomicMax(status, kErrCapacity);
         return;
     }
     const int T = q.T;
+    const size_t tbase = (size_t)j * (size_t)L.n_traj_total + (size_t)q.t0, lbase = (size_t)j * (size_t)L.n_rows;
     const bool in_lds = T <= L.lds_traj;
     const size_t stride = in_lds ? (size_t)L.lds_traj : (size_t)L.max_traj;
     int* idx = reinterpret_cast<int*>(smem);                           // [kWave] the chunk's surviving rows
@@ -212,15 +165,17 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
     int* cur_slot = cur + stride;
     int* nxt_slot = cur + 2 * stride;                                  // the slot of the observation after it, -1 none
     int* gap = cur + 3 * stride;
-    for (int t = lane; t < T; t += kWave) { cur[t] = -1; cur_slot[t] = -1; nxt_slot[t] = -1; gap[t] = ws.tgap[q.tbase + t]; }
+    for (int t = lane; t < T; t += kWave) { cur[t] = -1; cur_slot[t] = -1; nxt_slot[t] = -1; gap[t] = ws.tgap[tbase + t]; }
     wsync();
-    const bool mean = job_score_mode[q.j] == 1;
-    const long long jb = job_row_offsets[q.j];
+    const bool mean = job_score_mode[j] == 1;
+    const long long jb = job_row_offsets[j];
     long long pos = ws.out_base[p];                                    // wave-uniform
     long long pend = pos + ws.emitted[p];                              // nothing is written at or beyond it
     if (pend > out_cap) pend = out_cap;
     int err = 0;
-    int64_t* ofro = O.frame_row_offsets + (size_t)q.j * (size_t)(L.n_frames + 1);
+    int64_t* ofro = O.frame_row_offsets + (size_t)j * (size_t)(L.n_frames + 1);
+    // Not for_stream_rows: the whole wavefront compacts every chunk, rows with an index outside [0, T) included, advances pos
+    // between the chunks, and the gap pass follows the rows of a slot before the next slot begins.
     for (long long f = q.f0; f < q.f1; ++f) {
         const int fo = (int)(f - q.f0);
         long long r0, r1;
@@ -236,7 +191,7 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
                 O.frame[o] = f;
                 O.category[o] = L.category[d];
                 O.bbox[o * 4 + 0] = B.x[d]; O.bbox[o * 4 + 1] = B.y[d]; O.bbox[o * 4 + 2] = B.w[d]; O.bbox[o * 4 + 3] = B.h[d];
-                O.score[o] = mean ? ws.tmean[q.tbase + L.local[d]] : score[d];
+                O.score[o] = mean ? ws.tmean[tbase + L.local[d]] : score[d];
                 O.local[o] = L.local[d];
                 O.source[o] = d - q.base;
             }
@@ -244,7 +199,7 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
             const long long d = b + lane;
             if (d < hi) {
                 const int t = L.local[d];
-                if (t >= 0 && t < T) { cur[t] = (int)(d - q.rs0); cur_slot[t] = fo; nxt_slot[t] = ws.nxt_slot[q.lbase + d]; }
+                if (t >= 0 && t < T) { cur[t] = (int)(d - q.rs0); cur_slot[t] = fo; nxt_slot[t] = ws.nxt_slot[lbase + d]; }
             }
             wsync();
         }
@@ -263,7 +218,7 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
             if (in_gap) {
                 const long long o = pos + __popcll(m & lt);
                 const long long a = q.rs0 + cur[t];
-                const long long nb = ws.nxt_row[q.lbase + a];
+                const long long nb = ws.nxt_row[lbase + a];
                 if (o < pend && nb >= 0 && q.rs0 + nb < q.rend) {
                     const long long b = q.rs0 + nb;
                     const double w = (double)(fo - cs) / (double)(ns - cs);
@@ -273,7 +228,7 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
                     O.bbox[o * 4 + 1] = B.y[a] + (B.y[b] - B.y[a]) * w;
                     O.bbox[o * 4 + 2] = B.w[a] + (B.w[b] - B.w[a]) * w;
                     O.bbox[o * 4 + 3] = B.h[a] + (B.h[b] - B.h[a]) * w;
-                    O.score[o] = mean ? ws.tmean[q.tbase + t] : score[a] + (score[b] - score[a]) * w;
+                    O.score[o] = mean ? ws.tmean[tbase + t] : score[a] + (score[b] - score[a]) * w;
                     O.local[o] = t;
                     O.source[o] = -1 - (b - q.base);
                 }
@@ -284,40 +239,22 @@ __global__ __launch_bounds__(kWave) void refine_emit_kernel(Layout L, Boxes B, c
     }
     if (pos != ws.out_base[p] + ws.emitted[p]) err = kErrCapacity;      // the plan and the walk disagree, or out_cap cut it
     if (err && lane == 0) atomicMax(status, err);
-    if (q.s == L.n_streams - 1 && lane == 0) ofro[L.n_frames] = job_row_offsets[q.j + 1] - jb;
+    if (s == L.n_streams - 1 && lane == 0) ofro[L.n_frames] = job_row_offsets[j + 1] - jb;
 }
 
-int check_args(const char* entry, int64_t n_frames, int32_t n_streams, int32_t r_sets, int64_t n_rows, int64_t n_traj_total, int64_t max_traj,
-               int32_t n_jobs, int32_t n_classes, bool others_ok) {
-    if (n_frames < 0 || n_streams < 0 || r_sets < 1 || n_rows < 0 || n_traj_total < 0 || max_traj < 0 || n_jobs < 0 || n_classes < 1 || !others_ok) {
-        wt::set_error("%s: bad argument", entry);
-        return WT_ERR_INVALID;
-    }
-    if ((uint64_t)n_jobs * (uint64_t)n_streams > 0x7fffffffull) { wt::set_error("%s: %d jobs x %d streams in one call", entry, (int)n_jobs, (int)n_streams); return WT_ERR_CAPACITY; }
-    return WT_OK;
-}
+constexpr const char* kGridText = "%s: %d jobs x %d streams in one call";
 
-Layout make_layout(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets, int32_t r_sets, int64_t n_rows,
-                   const int64_t* set_row_offsets, const int64_t* frame_row_offsets, const int32_t* category, const int32_t* local,
-                   const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj, int32_t n_jobs, const int32_t* job_result,
-                   const int32_t* job_max_gap, const int32_t* job_min_len, int32_t n_classes) {
+Layout make_layout(const wt::TrackSet& dev, int64_t n_rows, const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj, int32_t n_jobs,
+                   const int32_t* job_result, const int32_t* job_max_gap, const int32_t* job_min_len) {
     Layout L;
-    L.n_frames = n_frames; L.n_rows = n_rows; L.n_traj_total = n_traj_total; L.max_traj = max_traj > 0 ? max_traj : 1;
-    L.n_streams = n_streams; L.r_sets = r_sets; L.n_jobs = n_jobs; L.n_classes = n_classes;
-    L.lds_traj = (int)(L.max_traj < kLdsTraj ? L.max_traj : kLdsTraj);
-    L.stream_frame_offsets = stream_frame_offsets; L.set_row_offsets = set_row_offsets; L.frame_row_offsets = frame_row_offsets;
-    L.traj_offsets = traj_offsets; L.category = category; L.local = local;
-    L.job_result = job_result; L.job_max_gap = job_max_gap; L.job_min_len = job_min_len;
+    wt::fill_track_layout(&L, dev, n_rows, traj_offsets, n_traj_total, max_traj, n_jobs, job_result, kLdsTraj);
+    L.job_max_gap = job_max_gap; L.job_min_len = job_min_len;
     return L;
 }
 
 int get_workspace(const char* entry, const Layout& L, void* workspace, size_t workspace_bytes, Workspace* ws) {
     *ws = carve(wt::align_ptr(workspace), (size_t)L.n_jobs, (size_t)L.n_streams, (size_t)L.n_rows, (size_t)L.n_traj_total, (size_t)L.max_traj);
-    if (!workspace || workspace_bytes < ws->bytes + 256) {
-        wt::set_error("%s: workspace too small: need %zu bytes, have %zu", entry, ws->bytes + 256, workspace_bytes);
-        return WT_ERR_INVALID;
-    }
-    return WT_OK;
+    return wt::check_workspace_fits(entry, workspace, workspace_bytes, ws->bytes, WT_ERR_INVALID);
 }
 
 int launch_plan(const Layout& L, const double* score, int64_t* job_row_offsets, int32_t* status_dev, void* workspace, size_t workspace_bytes,
@@ -378,11 +315,13 @@ int wt_refine_tracks_plan_dev(int64_t n_frames, int32_t n_streams, const int64_t
                               const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
                               int32_t n_jobs, const int32_t* job_result, const int32_t* job_max_gap, const int32_t* job_min_len, int32_t n_classes,
                               int64_t* job_row_offsets, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
-    WT_TRY(check_args("wt_refine_tracks_plan_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
-                      stream_frame_offsets && set_row_offsets && frame_row_offsets && score && category && local && traj_offsets && job_result &&
-                          job_max_gap && job_min_len && job_row_offsets && status_dev));
-    const Layout L = make_layout(n_frames, n_streams, stream_frame_offsets, r_sets, n_rows, set_row_offsets, frame_row_offsets, category, local,
-                                 traj_offsets, n_traj_total, max_traj, n_jobs, job_result, job_max_gap, job_min_len, n_classes);
+    WT_TRY(wt::check_track_args("wt_refine_tracks_plan_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
+                                stream_frame_offsets && set_row_offsets && frame_row_offsets && score && category && local && traj_offsets &&
+                                    job_result && job_max_gap && job_min_len && job_row_offsets && status_dev,
+                                wt::grid_fits(n_jobs, n_streams), kGridText, (int)n_jobs, (int)n_streams));
+    const wt::TrackSet dev = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, nullptr, nullptr, nullptr, nullptr,
+                              score, category, local, nullptr, n_classes};
+    const Layout L = make_layout(dev, n_rows, traj_offsets, n_traj_total, max_traj, n_jobs, job_result, job_max_gap, job_min_len);
     return launch_plan(L, score, job_row_offsets, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -396,12 +335,14 @@ int wt_refine_tracks_emit_dev(int64_t n_frames, int32_t n_streams, const int64_t
                               int64_t* out_frame, int32_t* out_category, double* out_bbox, double* out_score, int32_t* out_local,
                               int64_t* out_source, int64_t* out_frame_row_offsets,
                               int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
-    WT_TRY(check_args("wt_refine_tracks_emit_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
-                      stream_frame_offsets && set_row_offsets && frame_row_offsets && x && y && w && h && score && category && local && traj_offsets &&
-                          job_result && job_max_gap && job_min_len && job_score_mode && job_row_offsets && out_cap >= 0 && out_frame &&
-                          out_category && out_bbox && out_score && out_local && out_source && out_frame_row_offsets && status_dev));
-    const Layout L = make_layout(n_frames, n_streams, stream_frame_offsets, r_sets, n_rows, set_row_offsets, frame_row_offsets, category, local,
-                                 traj_offsets, n_traj_total, max_traj, n_jobs, job_result, job_max_gap, job_min_len, n_classes);
+    WT_TRY(wt::check_track_args("wt_refine_tracks_emit_dev", n_frames, n_streams, r_sets, n_rows, n_traj_total, max_traj, n_jobs, n_classes,
+                                stream_frame_offsets && set_row_offsets && frame_row_offsets && x && y && w && h && score && category && local &&
+                                    traj_offsets && job_result && job_max_gap && job_min_len && job_score_mode && job_row_offsets && out_cap >= 0 &&
+                                    out_frame && out_category && out_bbox && out_score && out_local && out_source && out_frame_row_offsets && status_dev,
+                                wt::grid_fits(n_jobs, n_streams), kGridText, (int)n_jobs, (int)n_streams));
+    const wt::TrackSet dev = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h,
+                              score, category, local, nullptr, n_classes};
+    const Layout L = make_layout(dev, n_rows, traj_offsets, n_traj_total, max_traj, n_jobs, job_result, job_max_gap, job_min_len);
     const Boxes B = {x, y, w, h};
     const Outputs O = {out_frame, out_category, out_bbox, out_score, out_local, out_source, out_frame_row_offsets};
     return launch_emit(L, B, score, job_score_mode, job_row_offsets, out_cap, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
@@ -415,41 +356,30 @@ int wt_refine_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                           const int32_t* job_score_mode, int32_t n_classes, int64_t out_cap,
                           int64_t* out_frame, int32_t* out_category, double* out_bbox, double* out_score, int32_t* out_local,
                           int64_t* out_source, int64_t* out_frame_row_offsets, int64_t* job_row_offsets) {
-    const wt::RefineInput in = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h, score,
-                                category, local, n_traj, n_jobs, job_result, job_max_gap, job_min_len, job_score_mode, n_classes};
+    const wt::RefineInput in = {{n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h, score,
+                                 category, local, n_traj, n_classes}, n_jobs, job_result, job_max_gap, job_min_len, job_score_mode};
     if (!job_row_offsets || out_cap < 0 || (out_cap > 0 && !(out_frame && out_category && out_bbox && out_score && out_local && out_source && out_frame_row_offsets))) {
         wt::set_error("wt_refine_tracks_host: bad argument");
         return WT_ERR_INVALID;
     }
     int64_t max_traj = 0, n_traj_total = 0;
     WT_TRY(wt::check_refine_layout(in, &max_traj, &n_traj_total));
-    WT_TRY(check_args("wt_refine_tracks_host", n_frames, n_streams, r_sets, set_row_offsets[r_sets], n_traj_total, max_traj, n_jobs, n_classes, true));
+    WT_TRY(wt::check_track_args("wt_refine_tracks_host", n_frames, n_streams, r_sets, set_row_offsets[r_sets], n_traj_total, max_traj, n_jobs, n_classes,
+                                true, wt::grid_fits(n_jobs, n_streams), kGridText, (int)n_jobs, (int)n_streams));
     WT_TRY(wt::ensure_device());
-    const size_t nr = (size_t)set_row_offsets[r_sets], nf = (size_t)(n_frames + 1), rs = (size_t)r_sets * (size_t)n_streams, J = (size_t)n_jobs;
-    std::vector<int64_t> traj_offsets(rs + 1, 0);
-    for (size_t i = 0; i < rs; ++i) traj_offsets[i + 1] = traj_offsets[i] + n_traj[i];
-    wt::DevBuf so, sr, fr, dx, dy, dw, dh, ds, dc, dl, dt, jr, jg, jl, jm, djo, status, dws;
-    WT_TRY(so.upload(stream_frame_offsets, 8 * (size_t)(n_streams + 1))); WT_TRY(sr.upload(set_row_offsets, 8 * (size_t)(r_sets + 1)));
-    WT_TRY(fr.upload(frame_row_offsets, 8 * (size_t)r_sets * nf));
-    WT_TRY(dx.upload(x, 8 * nr)); WT_TRY(dy.upload(y, 8 * nr)); WT_TRY(dw.upload(w, 8 * nr)); WT_TRY(dh.upload(h, 8 * nr)); WT_TRY(ds.upload(score, 8 * nr));
-    WT_TRY(dc.upload(category, 4 * nr)); WT_TRY(dl.upload(local, 4 * nr)); WT_TRY(dt.upload(traj_offsets.data(), 8 * (rs + 1)));
-    WT_TRY(jr.upload(job_result, 4 * J)); WT_TRY(jg.upload(job_max_gap, 4 * J * (size_t)n_classes)); WT_TRY(jl.upload(job_min_len, 4 * J * (size_t)n_classes));
+    const size_t nf = (size_t)(n_frames + 1), J = (size_t)n_jobs;
+    wt::StagedTrackSet st;
+    wt::DevBuf jg, jl, jm, djo, dws;
+    WT_TRY(st.upload(in, n_jobs, job_result));
+    WT_TRY(jg.upload(job_max_gap, 4 * J * (size_t)n_classes)); WT_TRY(jl.upload(job_min_len, 4 * J * (size_t)n_classes));
     WT_TRY(jm.upload(job_score_mode, 4 * J));
-    WT_TRY(djo.alloc(8 * (J + 1))); WT_TRY(status.alloc(16));
-    const size_t wsb = wt_refine_tracks_workspace(n_jobs, n_streams, (int64_t)nr, n_traj_total, max_traj);
+    WT_TRY(djo.alloc(8 * (J + 1)));
+    const size_t wsb = wt_refine_tracks_workspace(n_jobs, n_streams, st.n_rows, n_traj_total, max_traj);
     WT_TRY(dws.alloc(wsb));
-    const Layout L = make_layout(n_frames, n_streams, so.as<int64_t>(), r_sets, (int64_t)nr, sr.as<int64_t>(), fr.as<int64_t>(), dc.as<int32_t>(),
-                                 dl.as<int32_t>(), dt.as<int64_t>(), n_traj_total, max_traj, n_jobs, jr.as<int32_t>(), jg.as<int32_t>(),
-                                 jl.as<int32_t>(), n_classes);
-    auto finish = [&](const char* what) {
-        WT_HIP(hipDeviceSynchronize());
-        int32_t st = 0;
-        WT_HIP(hipMemcpy(&st, status.p, sizeof(st), hipMemcpyDeviceToHost));
-        if (st) wt::set_error("%s kernel reported status %d (4 = counts or offsets that do not fit the rows)", what, (int)st);
-        return (int)st;
-    };
-    WT_TRY(launch_plan(L, ds.as<double>(), djo.as<int64_t>(), status.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_TRY(finish("refine plan"));
+    const Layout L = make_layout(st.dev, st.n_rows, st.dt.as<int64_t>(), n_traj_total, max_traj, n_jobs, st.jr.as<int32_t>(), jg.as<int32_t>(),
+                                 jl.as<int32_t>());
+    WT_TRY(launch_plan(L, st.dev.score, djo.as<int64_t>(), st.status.as<int32_t>(), dws.p, wsb, nullptr));
+    WT_TRY(st.finish("refine plan", "counts or offsets"));
     WT_HIP(hipMemcpy(job_row_offsets, djo.p, 8 * (J + 1), hipMemcpyDeviceToHost));
     if (out_cap == 0) return WT_OK;                                    // the sizing call
     const int64_t n_out = job_row_offsets[J];
@@ -461,10 +391,10 @@ int wt_refine_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
     wt::DevBuf of, oc, ob, os, ol, osrc, ofro;
     WT_TRY(of.alloc(8 * no)); WT_TRY(oc.alloc(4 * no)); WT_TRY(ob.alloc(32 * no)); WT_TRY(os.alloc(8 * no)); WT_TRY(ol.alloc(4 * no));
     WT_TRY(osrc.alloc(8 * no)); WT_TRY(ofro.alloc(8 * J * nf));
-    const Boxes B = {dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>()};
+    const Boxes B = {st.dev.x, st.dev.y, st.dev.w, st.dev.h};
     const Outputs O = {of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(), ol.as<int32_t>(), osrc.as<int64_t>(), ofro.as<int64_t>()};
-    WT_TRY(launch_emit(L, B, ds.as<double>(), jm.as<int32_t>(), djo.as<int64_t>(), n_out, O, status.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_TRY(finish("refine emit"));
+    WT_TRY(launch_emit(L, B, st.dev.score, jm.as<int32_t>(), djo.as<int64_t>(), n_out, O, st.status.as<int32_t>(), dws.p, wsb, nullptr));
+    WT_TRY(st.finish("refine emit", "counts or offsets"));
     if (no) {
         WT_HIP(hipMemcpy(out_frame, of.p, 8 * no, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(out_category, oc.p, 4 * no, hipMemcpyDeviceToHost));
         WT_HIP(hipMemcpy(out_bbox, ob.p, 32 * no, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(out_score, os.p, 8 * no, hipMemcpyDeviceToHost));

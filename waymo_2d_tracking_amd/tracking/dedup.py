@@ -15,34 +15,22 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from . import refine as R
+from . import _trackset as TS
+from ._trackset import COLUMNS as _COLUMNS
 
-_COLUMNS = ('x', 'y', 'w', 'h', 'score', 'category', 'local')
 _JOB = ('job_result', 'job_min_frames', 'job_dup_iou', 'job_dup_frac')
 _OUT = ('keep', 'by', 'match', 'row_keep', 'dropped')
 
 
 def _per_class(value, n_classes, kind):
-    v = [kind(x) for x in value] if isinstance(value, (list, tuple, np.ndarray)) else [kind(value)] * n_classes
-    if len(v) == 1:
-        v = v * n_classes
-    if len(v) != n_classes:
-        raise ValueError('min_frames / dup_iou / dup_frac need one value, or one per class (%d)' % n_classes)
-    return v
+    return TS.per_class(value, n_classes, kind, 'min_frames / dup_iou / dup_frac')
 
 
 def _prepare(packed, outs, jobs, n_classes):
-    """Everything wt_dedup_tracks_* takes, as numpy arrays (include/waymotrack.h): the layout refinement prepares, the jobs of the
+    """Everything wt_dedup_tracks_* takes, as numpy arrays (include/waymotrack.h): the shared layout, the jobs of the
     deduplication, and per trajectory the object id it has in the caller's rows."""
-    try:
-        p = R._prepare(packed, outs, [], n_classes)
-    except _lib.WaymoTrackError as e:                # the duplicate in a slot, named with its image
-        raise _lib.WaymoTrackError(str(e).replace('wt_refine_tracks failed', 'wt_dedup_tracks failed'))
-    J = len(jobs)
-    p['J'] = J
-    p['job_result'] = np.asarray([int(j.get('result', 0)) for j in jobs], dtype=np.int32).reshape(J)
-    if J and (p['job_result'].min() < 0 or p['job_result'].max() >= len(outs)):
-        raise ValueError('a job names a result outside 0..%d' % (len(outs) - 1))
+    p = TS.prepare(packed, outs, jobs, n_classes, 'dedup')
+    J = p['J']
     p['job_min_frames'] = np.asarray([_per_class(j.get('min_frames', 0), n_classes, int) for j in jobs], dtype=np.int32).reshape(J, n_classes)
     p['job_dup_iou'] = np.asarray([_per_class(j.get('dup_iou', 0.7), n_classes, float) for j in jobs], dtype=np.float64).reshape(J, n_classes)
     p['job_dup_frac'] = np.asarray([_per_class(j.get('dup_frac', 0.5), n_classes, float) for j in jobs], dtype=np.float64).reshape(J, n_classes)
@@ -52,22 +40,7 @@ def _prepare(packed, outs, jobs, n_classes):
         raise ValueError('dup_iou must not be NaN')
     if not ((p['job_dup_frac'] >= 0) & (p['job_dup_frac'] <= 1)).all():
         raise ValueError('dup_frac must be in 0..1')
-    p['n_rows'] = int(p['set_row_offsets'][-1])
-    p['n_traj_total'] = int(p['traj_offsets'][-1])
-    # per row its trajectory's place in the (J, n_traj_total) outputs, per trajectory its object id
-    sfo, S = p['stream_frame_offsets'], p['n_streams']
-    ids = []
-    for r in range(p['R']):
-        lo, hi = int(p['set_row_offsets'][r]), int(p['set_row_offsets'][r + 1])
-        frame = np.asarray(outs[r]['frame'], dtype=np.int64)[p['orders'][r]]
-        stream = np.searchsorted(sfo, frame, side='right') - 1
-        base = p['traj_offsets'][r * S + stream] if frame.size else np.zeros(0, np.int64)
-        t0, t1 = int(p['traj_offsets'][r * S]), int(p['traj_offsets'][(r + 1) * S])
-        oid = p['object_ids'][r]
-        of_traj = np.zeros(t1 - t0, dtype=oid.dtype)
-        of_traj[base + p['local'][lo:hi] - t0] = oid
-        ids.append(of_traj)
-    p['traj_ids'] = ids
+    p['traj_ids'] = TS.traj_ids(p, outs)[1]
     return p
 
 
@@ -96,21 +69,11 @@ def _job_dicts(p, outs, keep, by, match, row_keep, dropped):
     return results
 
 
-def _leading_args(p, a, ptr, host):
-    args = [C.c_int64(p['n_frames']), C.c_int32(p['n_streams']), ptr(a['stream_frame_offsets']), C.c_int32(p['R'])]
-    if not host:
-        args.append(C.c_int64(p['n_rows']))
-    return args + [ptr(a['set_row_offsets']), ptr(a['frame_row_offsets'])] + [ptr(a[n]) for n in _COLUMNS]
-
-
-def _job_args(p, a, ptr):
-    return [C.c_int32(p['J'])] + [ptr(a[n]) for n in _JOB] + [C.c_int32(p['n_classes'])]
-
-
 def _host_call(p, outputs):
     """wt_dedup_tracks_host on _prepare() output; outputs: keep, by, match, row_keep, dropped, each exactly (J, n) C-contiguous."""
     ptr = _lib.ptr
-    return _lib.lib().wt_dedup_tracks_host(*_leading_args(p, p, ptr, True), ptr(p['n_traj']), *_job_args(p, p, ptr), *[ptr(x) for x in outputs])
+    return _lib.lib().wt_dedup_tracks_host(*TS.leading_args(p, p, ptr, True, _COLUMNS), ptr(p['n_traj']), *TS.job_args(p, p, ptr, _JOB),
+                                           *[ptr(x) for x in outputs])
 
 
 def dedup_tracks(packed, outs, jobs, n_classes=4):
@@ -128,54 +91,26 @@ def dedup_tracks(packed, outs, jobs, n_classes=4):
     return _job_dicts(p, outs, *o)
 
 
-class DeviceDedup(object):
+class DeviceDedup(TS.DeviceStage):
     """The same deduplication with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues
     wt_dedup_tracks_dev on the current torch stream and returns at once - the output sizes are known up front, nothing is read
     back in between; ``results()`` synchronises and reads the outputs.  ``self.out`` holds the output tensors."""
+    stage = 'dedup'
     name = 'wt_dedup_tracks_dev'
 
     def __init__(self, packed, outs, jobs, n_classes=4, workspace_bytes=None):
-        import torch
-        self.torch = torch
-        self.lib = _lib.lib()
+        TS.DeviceStage.__init__(self, _prepare(packed, outs, jobs, n_classes), _COLUMNS + _JOB, workspace_bytes)
+        torch, p = self.torch, self.p
         self.outs = outs
-        self.p = p = _prepare(packed, outs, jobs, n_classes)
-        self.device = torch.device('cuda', torch.cuda.current_device())
-        self.status = self.zeros(1, torch.int32)
-        names = _COLUMNS + _JOB + ('stream_frame_offsets', 'set_row_offsets', 'frame_row_offsets', 'traj_offsets')
-        self.t = dict((n, self.up(p[n])) for n in names)
-        self.max_traj = int(p['n_traj'].max()) if p['n_traj'].size else 0
         J, nt, nr, S = p['J'], p['n_traj_total'], p['n_rows'], p['n_streams']
         self.shapes = dict(keep=(J, nt), by=(J, nt), match=(J, nt), row_keep=(J, nr), dropped=(J, S))
         self.out = dict((k, self.zeros(max(1, s[0] * s[1]), torch.int64 if k == 'dropped' else torch.int32)) for k, s in self.shapes.items())
-        self.ws_bytes = int(self.lib.wt_dedup_tracks_workspace(C.c_int32(J), C.c_int32(S), C.c_int64(nr), C.c_int64(nt), C.c_int64(self.max_traj)))
-        if not self.ws_bytes:
-            _lib.check(4, 'wt_dedup_tracks_workspace')
-        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
-
-    def up(self, a):
-        t = self.torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(self.device) if a.size else self.zeros(1, t.dtype)
-
-    def zeros(self, shape, dtype):
-        return self.torch.zeros(shape, dtype=dtype, device=self.device)
-
-    def d(self, t):
-        return C.c_void_p(t.data_ptr())
 
     def launch(self):
-        p, t, d, o = self.p, self.t, self.d, self.out
-        rc = self.lib.wt_dedup_tracks_dev(
-            *_leading_args(p, t, d, False), d(t['traj_offsets']), C.c_int64(p['n_traj_total']), C.c_int64(self.max_traj), *_job_args(p, t, d),
-            *[d(o[k]) for k in _OUT], d(self.status), d(self.ws), C.c_size_t(int(self.ws.numel())),
-            C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
+        p, t, d = self.p, self.t, self.d
+        rc = self.lib.wt_dedup_tracks_dev(*TS.leading_args(p, t, d, False, _COLUMNS), *self.traj_args(), *TS.job_args(p, t, d, _JOB),
+                                          *[d(self.out[k]) for k in _OUT], *self.tail_args())
         _lib.check(rc, self.name)
-
-    def wait(self):
-        self.torch.cuda.current_stream().synchronize()
-        st = int(self.status.item())
-        if st:
-            raise _lib.WaymoTrackError('%s failed: %s (status reported by the kernel)' % (self.name, _lib._STATUS.get(st, st)))
 
     def rounds(self):
         """(J, n_streams): the sweeps over the slots the matching of each problem took, after a launch (a measurement)."""

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from .. import _lib
-from . import refine as R
+from . import _trackset as TS
 
 MAX_WINDOW = 32                                      # WT_SMOOTH_MAX_WINDOW
 KERNELS = ('gaussian', 'box')
@@ -25,12 +25,7 @@ _JOB = ('job_result', 'job_window', 'job_weights')
 
 
 def _per_class(value, n_classes, kind):
-    v = [kind(x) for x in value] if isinstance(value, (list, tuple, np.ndarray)) else [kind(value)] * n_classes
-    if len(v) == 1:
-        v = v * n_classes
-    if len(v) != n_classes:
-        raise ValueError('window / sigma need one value, or one per class (%d)' % n_classes)
-    return v
+    return TS.per_class(value, n_classes, kind, 'window / sigma')
 
 
 def kernel_weights(kernel, sigma, n):
@@ -59,17 +54,10 @@ def _job_weights(job, window, n_classes):
 
 
 def _prepare(packed, outs, jobs, n_classes):
-    """Everything wt_smooth_tracks_* takes, as numpy arrays (include/waymotrack.h): the layout refinement prepares and the jobs of
-    the smoothing, their weight tables padded with zeros to one length."""
-    try:
-        p = R._prepare(packed, outs, [], n_classes)
-    except _lib.WaymoTrackError as e:                # the duplicate in a slot, named with its image
-        raise _lib.WaymoTrackError(str(e).replace('wt_refine_tracks failed', 'wt_smooth_tracks failed'))
-    J = len(jobs)
-    p['J'] = J
-    p['job_result'] = np.asarray([int(j.get('result', 0)) for j in jobs], dtype=np.int32).reshape(J)
-    if J and (p['job_result'].min() < 0 or p['job_result'].max() >= len(outs)):
-        raise ValueError('a job names a result outside 0..%d' % (len(outs) - 1))
+    """Everything wt_smooth_tracks_* takes, as numpy arrays (include/waymotrack.h): the shared layout and the jobs of the
+    smoothing, their weight tables padded with zeros to one length."""
+    p = TS.prepare(packed, outs, jobs, n_classes, 'smooth')
+    J = p['J']
     windows = [_per_class(j.get('window', 0), n_classes, int) for j in jobs]
     p['job_window'] = np.asarray(windows, dtype=np.int32).reshape(J, n_classes)
     if J and (p['job_window'].min() < 0 or p['job_window'].max() > MAX_WINDOW):
@@ -85,8 +73,6 @@ def _prepare(packed, outs, jobs, n_classes):
     p['job_weights'] = np.zeros((J, n_classes, n), np.float64)
     for j, k in enumerate(tables):
         p['job_weights'][j, :, :k.shape[1]] = k
-    p['n_rows'] = int(p['set_row_offsets'][-1])
-    p['n_traj_total'] = int(p['traj_offsets'][-1])
     rows = np.diff(p['set_row_offsets'])
     p['job_row_offsets'] = np.concatenate([[0], np.cumsum(rows[p['job_result']])]).astype(np.int64)
     return p
@@ -111,21 +97,11 @@ def _job_dicts(p, outs, bbox, pairs):
     return results
 
 
-def _leading_args(p, a, ptr, host):
-    args = [C.c_int64(p['n_frames']), C.c_int32(p['n_streams']), ptr(a['stream_frame_offsets']), C.c_int32(p['R'])]
-    if not host:
-        args.append(C.c_int64(p['n_rows']))
-    return args + [ptr(a['set_row_offsets']), ptr(a['frame_row_offsets'])] + [ptr(a[n]) for n in _COLUMNS]
-
-
-def _job_args(p, a, ptr):
-    return [C.c_int32(p['J'])] + [ptr(a[n]) for n in _JOB] + [C.c_int32(p['n_weights']), C.c_int32(p['n_classes'])]
-
-
 def _host_call(p, outputs):
     """wt_smooth_tracks_host on _prepare() output; outputs: bbox (n, 4) float64 and pairs (n) int32, n = job_row_offsets[-1]."""
     ptr = _lib.ptr
-    return _lib.lib().wt_smooth_tracks_host(*_leading_args(p, p, ptr, True), ptr(p['n_traj']), *_job_args(p, p, ptr), *[ptr(x) for x in outputs])
+    return _lib.lib().wt_smooth_tracks_host(*TS.leading_args(p, p, ptr, True, _COLUMNS), ptr(p['n_traj']),
+                                            *TS.job_args(p, p, ptr, _JOB, ('n_weights',)), *[ptr(x) for x in outputs])
 
 
 def smooth_tracks(packed, outs, jobs, n_classes=4):
@@ -142,54 +118,28 @@ def smooth_tracks(packed, outs, jobs, n_classes=4):
     return _job_dicts(p, outs, *o)
 
 
-class DeviceSmooth(object):
+class DeviceSmooth(TS.DeviceStage):
     """The same smoothing with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues
     wt_smooth_tracks_dev on the current torch stream and returns at once - the output sizes are known up front, nothing is read
     back in between; ``results()`` synchronises and reads the outputs.  ``self.out`` holds the output tensors."""
+    stage = 'smooth'
     name = 'wt_smooth_tracks_dev'
 
     def __init__(self, packed, outs, jobs, n_classes=4, workspace_bytes=None):
-        import torch
-        self.torch = torch
-        self.lib = _lib.lib()
+        TS.DeviceStage.__init__(self, _prepare(packed, outs, jobs, n_classes), _COLUMNS + _JOB + ('job_row_offsets',), workspace_bytes)
         self.outs = outs
-        self.p = p = _prepare(packed, outs, jobs, n_classes)
-        self.device = torch.device('cuda', torch.cuda.current_device())
-        self.status = self.zeros(1, torch.int32)
-        names = _COLUMNS + _JOB + ('stream_frame_offsets', 'set_row_offsets', 'frame_row_offsets', 'traj_offsets', 'job_row_offsets')
-        self.t = dict((n, self.up(p[n])) for n in names)
-        self.max_traj = int(p['n_traj'].max()) if p['n_traj'].size else 0
-        self.n_out = int(p['job_row_offsets'][-1])
-        self.out = dict(bbox=self.zeros((max(1, self.n_out), 4), torch.float64), pairs=self.zeros(max(1, self.n_out), torch.int32))
-        self.ws_bytes = int(self.lib.wt_smooth_tracks_workspace(C.c_int32(p['J']), C.c_int32(p['n_streams']), C.c_int64(p['n_rows']),
-                                                                C.c_int64(p['n_traj_total']), C.c_int64(self.max_traj)))
-        if not self.ws_bytes:
-            _lib.check(4, 'wt_smooth_tracks_workspace')
-        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
-
-    def up(self, a):
-        t = self.torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(self.device) if a.size else self.zeros(1, t.dtype)
-
-    def zeros(self, shape, dtype):
-        return self.torch.zeros(shape, dtype=dtype, device=self.device)
-
-    def d(self, t):
-        return C.c_void_p(t.data_ptr())
+        self.n_out = int(self.p['job_row_offsets'][-1])
+        self.out = dict(bbox=self.zeros((max(1, self.n_out), 4), self.torch.float64), pairs=self.zeros(max(1, self.n_out), self.torch.int32))
 
     def launch(self):
         p, t, d, o = self.p, self.t, self.d, self.out
         rc = self.lib.wt_smooth_tracks_dev(
-            *_leading_args(p, t, d, False), d(t['traj_offsets']), C.c_int64(p['n_traj_total']), C.c_int64(self.max_traj), *_job_args(p, t, d),
-            d(t['job_row_offsets']), C.c_int64(self.n_out), d(o['bbox']), d(o['pairs']), d(self.status), d(self.ws),
-            C.c_size_t(int(self.ws.numel())), C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
+            *TS.leading_args(p, t, d, False, _COLUMNS), *self.traj_args(), *TS.job_args(p, t, d, _JOB, ('n_weights',)),
+            d(t['job_row_offsets']), C.c_int64(self.n_out), d(o['bbox']), d(o['pairs']), *self.tail_args())
         _lib.check(rc, self.name)
 
     def results(self):
-        self.torch.cuda.current_stream().synchronize()
-        st = int(self.status.item())
-        if st:
-            raise _lib.WaymoTrackError('%s failed: %s (status reported by the kernel)' % (self.name, _lib._STATUS.get(st, st)))
+        self.wait()
         return _job_dicts(self.p, self.outs, self.out['bbox'].cpu().numpy()[:self.n_out], self.out['pairs'].cpu().numpy()[:self.n_out])
 
 
