@@ -600,6 +600,55 @@ int wt_stitch_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                           int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_row_root, int64_t* out_links);
 
 /* =================================================================================================
+ * Track splitting (impure tracks cut at motion jumps and long gaps; the definition is DESIGN.md section 25)
+ * ================================================================================================= */
+
+/* Splits the trajectories of R >= 1 tracking results under J jobs: job j names a result, job_result[j], and its parameters.
+ * Results, frame slots, streams, trajectories, local indices (in any order) and a trajectory's class are those of the track
+ * refinement above.  A trajectory has its observations at slots f_0 < f_1 < ...; the pair (i - 1, i), n = f_i - f_{i-1}, breaks
+ * when split_gap[class] > 0 and n > split_gap[class], or - when split_iou[class] > 0 - when every test that exists for it gives
+ * a < split_iou[class] (a NaN never does):
+ *   forward  (motion 1 = linear and i >= 2):     p = f_{i-1} - f_{i-2}, px = x_{i-1} + ((x_{i-1} - x_{i-2}) / (double)p) * (double)n, py
+ *            alike, w and h of row i - 1; a_f = iou_dd([px, py, px + w, py + h], box_i);
+ *   backward (motion 1 and row i + 1 exists):    q = f_{i+1} - f_i, px = x_i + ((x_i - x_{i+1}) / (double)q) * (double)n, py alike,
+ *            w and h of row i; a_b = iou_dd([px, py, px + w, py + h], box_{i-1});
+ *   hold     (neither exists; motion 0 = hold):  a_h = iou_dd(box_{i-1}, box_i);
+ * every operation rounded on its own in float64.  piece(row) = the breaking pairs of its trajectory at or before the row; piece 0
+ * keeps the identity, and the other pieces of a result are numbered from 0 in the order (stream, local index, piece).
+ *
+ * Jobs: job_result (J) int32, job_split_iou (J, n_classes) float64 not NaN (<= 0: the rule is off for the class), job_split_gap
+ * (J, n_classes) int32 >= 0 (0: off), job_motion (J) int32.
+ * Outputs, sized up front: out_piece (J, n_rows) int32; out_new (J, n_rows) int64 = the number of the row's new piece, -1 for
+ * piece 0 (the caller gives the row the id first_new_id + out_new); out_test (J, n_rows, 2) float64 = for the pair that ends at
+ * the row [a_f, or a_h when the hold test was used, or -1.0; a_b or -1.0], both -1.0 for a trajectory's first row and when the
+ * class's IoU rule is off; out_breaks (J, n_traj_total) int32, indexed like traj_offsets; out_new_pieces (J, n_streams) int64 =
+ * the breaks of the stream.  Entries of results the job does not name are -1 (-1.0).
+ *
+ * wt_split_tracks_dev: device pointers, stream-ordered, no allocation, no synchronisation; it reports in status_dev (device
+ * int32) 0 or WT_ERR_CAPACITY (counts, indices or offsets that do not fit the rows).  A workspace smaller than
+ * wt_split_tracks_workspace() says is WT_ERR_CAPACITY.  The device form does not check the layout; the host form does
+ * (WT_ERR_INVALID names the result and the row or frame slot, or the job and class), stages and launches; it takes n_traj
+ * (R, n_streams) int32 where the device form takes the running sum traj_offsets, n_traj_total and max_traj.
+ * wt_split_tracks_limits: the trajectory count of one (result, stream) up to which the per-trajectory tables stay in LDS; above
+ * it they live in the workspace. */
+void wt_split_tracks_limits(int32_t* lds_trajectories);
+size_t wt_split_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_split_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                        int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                        const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                        const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                        int32_t n_jobs, const int32_t* job_result, const double* job_split_iou, const int32_t* job_split_gap,
+                        const int32_t* job_motion, int32_t n_classes,
+                        int32_t* out_piece, int64_t* out_new, double* out_test, int32_t* out_breaks, int64_t* out_new_pieces,
+                        int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_split_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                         const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const double* job_split_iou,
+                         const int32_t* job_split_gap, const int32_t* job_motion, int32_t n_classes,
+                         int32_t* out_piece, int64_t* out_new, double* out_test, int32_t* out_breaks, int64_t* out_new_pieces);
+
+/* =================================================================================================
  * Track smoothing (a symmetric window filter per trajectory; the definition is DESIGN.md section 22)
  * ================================================================================================= */
 

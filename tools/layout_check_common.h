@@ -1,4 +1,4 @@
-// What the four tools/*_layout_check.cpp share: the two functions of the library that the host headers call, kept in the program
+// What the five tools/*_layout_check.cpp share: the two functions of the library that the host headers call, kept in the program
 // itself so that no device is needed, and the harness that feeds a check one input and compares what it gave.
 // Include it after the stage's csrc/*_host.h.
 #pragma once

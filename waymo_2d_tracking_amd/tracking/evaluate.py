@@ -850,7 +850,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
 
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
-    and 'min_hits', optionally 'link_gap', 'link_iou' and 'link_motion' (track stitching, tracking/stitch.py; defaults [0], [0.3], 'hold' = none:
+    and 'min_hits', optionally 'split_iou' and the single values 'split_gap' and 'split_motion' (track splitting, tracking/split.py; defaults
+    [0.0], 0, 'linear' = none: every tracked result is split under all split IoUs in one call, before it is stitched; the values are the outermost
+    post-pass axis, and the pass is per trajectory with per-class parameters, so the per-class pick ranges over them too), optionally 'link_gap', 'link_iou' and 'link_motion' (track stitching, tracking/stitch.py; defaults [0], [0.3], 'hold' = none:
     every tracked result is stitched under all (link_gap, link_iou) pairs in one call, before it is refined; stitching is per class, so the
     per-class pick ranges over these too), optionally 'dedup_frames', 'dedup_iou' and the single value 'dedup_frac' (suppression of duplicate
     tracks, tracking/dedup.py; defaults [0], [0.7], 0.5 = none: every stitched result is deduplicated under all (frames, IoU) pairs in one
@@ -908,6 +910,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     smoothing = smooth_windows != [0]               # the innermost axes: every refined result smoothed under every (window, sigma)
     smooth_kernel = grid.get('smooth_kernel', 'gaussian')
     smooth_jobs = [{'window': w, 'sigma': v, 'kernel': smooth_kernel} for w in smooth_windows for v in smooth_sigmas] if smoothing else [None]
+    split_ious = [float(v) for v in grid.get('split_iou', [0.0])]
+    splitting = split_ious != [0.0]                 # the outermost post-pass axis: one tracked result split under every split IoU
+    split_gap, split_motion = int(grid.get('split_gap', 0)), grid.get('split_motion', 'linear')
+    split_jobs = [{'split_iou': v, 'split_gap': split_gap, 'motion': split_motion} for v in split_ious] if splitting else [None]
     low_scores, low_ious = [float(v) for v in grid.get('low_score', [])], [float(v) for v in grid.get('low_iou', [0.5])]
     second = bool(low_scores)                       # the axes just inside (score, iou): the tracker's second association (utils.track_packed_byte)
     low_jobs = [(s, v) for s in low_scores for v in low_ious] if second else [None]
@@ -923,37 +929,43 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                         base.update(low_score=low, low_iou=low_job[1])
                     else:
                         out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
-                    linked = [out]
-                    if stitching:
-                        from .stitch import stitch_tracks
-                        linked = stitch_tracks(packed, [out], link_jobs, n_classes)
-                    link_rows = [dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base for link in link_jobs]
-                    if deduping:                     # every stitched result under every (frames, IoU), in one call
-                        from .dedup import dedup_tracks
-                        every = [dict(job, result=k) for k in range(len(linked)) for job in dedup_jobs]
-                        link_rows = [dict(row, dedup_frames=job['min_frames'], dedup_iou=job['dup_iou']) for row in link_rows for job in dedup_jobs]
-                        linked = dedup_tracks(packed, linked, every, n_classes)
-                    if refining:                     # every stitched result under every (gap, length), in one call
-                        from .refine import refine_tracks
-                        every = [dict(job, result=k) for k in range(len(linked)) for job in jobs]
-                        refined = refine_tracks(packed, linked, every, n_classes)
-                    rows, passed = [], []
-                    for k, row in enumerate(link_rows):
-                        if not refining:
-                            rows.append(row)
-                            passed.append(linked[k])
-                            continue
-                        for n, job in enumerate(jobs):
-                            rows.append(dict(row, interp_gap=job['max_gap'], min_len=job['min_len']))
-                            passed.append(refined[k * len(jobs) + n])
-                    if smoothing:                    # every result so far under every (window, sigma), in one call
-                        from .smooth import smooth_tracks
-                        every = [dict(job, result=k) for k in range(len(passed)) for job in smooth_jobs]
-                        rows = [dict(row, smooth_window=job['window'], smooth_sigma=job['sigma']) for row in rows for job in smooth_jobs]
-                        passed = smooth_tracks(packed, passed, every, n_classes)
-                    for row, result in zip(rows, passed):
-                        settings.append(row)
-                        tracks.append(tracks_from_packed(packed, result))
+                    tracked, tracked_base = [out], base
+                    if splitting:                    # the tracked result under every split IoU, in one call, before anything is linked
+                        from .split import split_tracks
+                        tracked = split_tracks(packed, [out], split_jobs, n_classes)
+                    for out, split in zip(tracked, split_jobs):
+                        base = dict(tracked_base, split_iou=split['split_iou']) if splitting else tracked_base
+                        linked = [out]
+                        if stitching:
+                            from .stitch import stitch_tracks
+                            linked = stitch_tracks(packed, [out], link_jobs, n_classes)
+                        link_rows = [dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base for link in link_jobs]
+                        if deduping:                     # every stitched result under every (frames, IoU), in one call
+                            from .dedup import dedup_tracks
+                            every = [dict(job, result=k) for k in range(len(linked)) for job in dedup_jobs]
+                            link_rows = [dict(row, dedup_frames=job['min_frames'], dedup_iou=job['dup_iou']) for row in link_rows for job in dedup_jobs]
+                            linked = dedup_tracks(packed, linked, every, n_classes)
+                        if refining:                     # every stitched result under every (gap, length), in one call
+                            from .refine import refine_tracks
+                            every = [dict(job, result=k) for k in range(len(linked)) for job in jobs]
+                            refined = refine_tracks(packed, linked, every, n_classes)
+                        rows, passed = [], []
+                        for k, row in enumerate(link_rows):
+                            if not refining:
+                                rows.append(row)
+                                passed.append(linked[k])
+                                continue
+                            for n, job in enumerate(jobs):
+                                rows.append(dict(row, interp_gap=job['max_gap'], min_len=job['min_len']))
+                                passed.append(refined[k * len(jobs) + n])
+                        if smoothing:                    # every result so far under every (window, sigma), in one call
+                            from .smooth import smooth_tracks
+                            every = [dict(job, result=k) for k in range(len(passed)) for job in smooth_jobs]
+                            rows = [dict(row, smooth_window=job['window'], smooth_sigma=job['sigma']) for row in rows for job in smooth_jobs]
+                            passed = smooth_tracks(packed, passed, every, n_classes)
+                        for row, result in zip(rows, passed):
+                            settings.append(row)
+                            tracks.append(tracks_from_packed(packed, result))
     if rank_by not in ('mota', 'idf1', 'hota'):
         raise ValueError("rank_by must be 'mota', 'idf1' or 'hota'")
     identity = identity or rank_by == 'idf1'
@@ -965,7 +977,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou']) * len(low_jobs) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
+    per_mm = len(grid['score']) * len(grid['iou']) * len(low_jobs) * len(split_jobs) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
     for lv in LEVELS:
         combos = []
         for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
@@ -1009,6 +1021,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 combos[-1]['interp_gap'], combos[-1]['min_len'] = [0] * n_classes, [1] * n_classes
                 for c in classes:
                     combos[-1]['interp_gap'][c - 1], combos[-1]['min_len'][c - 1] = settings[pick[c]]['interp_gap'], settings[pick[c]]['min_len']
+            if splitting:                                             # classes that are not evaluated are not split either
+                combos[-1]['split_iou'], combos[-1]['split_gap'], combos[-1]['split_motion'] = [0.0] * n_classes, split_gap, split_motion
+                for c in classes:
+                    combos[-1]['split_iou'][c - 1] = settings[pick[c]]['split_iou']
             if stitching:                                             # classes that are not evaluated are not stitched either
                 combos[-1]['link_gap'], combos[-1]['link_iou'], combos[-1]['link_motion'] = [0] * n_classes, [link_ious[0]] * n_classes, link_motion
                 for c in classes:
@@ -1047,6 +1063,12 @@ def flag_line(setting):
         join(setting['score_threshold']), join(setting['iou_threshold']), setting['max_age'], setting['min_hits'])
     if 'low_score_threshold' in setting:
         line += ' --low-score-threshold=%s --low-iou-threshold=%s' % (join(setting['low_score_threshold']), join(setting['low_iou_threshold']))
+    if 'split_iou' in setting:
+        line += ' --split-iou=%s' % join(setting['split_iou'])
+        if setting.get('split_gap', 0):
+            line += ' --split-gap=%d' % setting['split_gap']
+        if setting.get('split_motion', 'linear') != 'linear':
+            line += ' --split-motion=%s' % setting['split_motion']
     if 'link_gap' in setting:
         line += ' --link-gap=%s --link-iou=%s' % (','.join('%d' % v for v in setting['link_gap']), join(setting['link_iou']))
         if setting.get('link_motion', 'hold') != 'hold':
@@ -1111,6 +1133,9 @@ def build_parser():
     parser.add_argument('--low-iou-grid', default='0.5', help='second association: lowest IoU of a low-score detection and its track; read when --low-score-grid is set')
     parser.add_argument('--gap-grid', default='0', help='track refinement: gaps of up to this many frames are interpolated (tracking/refine.py)')
     parser.add_argument('--min-len-grid', default='1', help='track refinement: tracks observed in fewer frames are dropped')
+    parser.add_argument('--split-iou-grid', default='0', help='track splitting: a track is cut where the extrapolated boxes overlap by less than this IoU (tracking/split.py)')
+    parser.add_argument('--split-gap', type=int, default=0, help='track splitting: a track is cut where more than this many frames lie between two boxes; read when --split-iou-grid is set')
+    parser.add_argument('--split-motion', choices=('linear', 'hold'), default='linear', help='track splitting: how a box is extrapolated')
     parser.add_argument('--link-gap-grid', default='0', help='track stitching: tracks are linked across up to this many frames (tracking/stitch.py)')
     parser.add_argument('--link-iou-grid', default='0.3', help='track stitching: lowest IoU of the extrapolated and the new box; read when --link-gap-grid is set')
     parser.add_argument('--link-motion', choices=('hold', 'linear'), default='hold', help='track stitching: how an ended track is extrapolated')
@@ -1136,7 +1161,8 @@ def main(argv=None):
                 'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')],
                 'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')],
                 'link_gap': [int(v) for v in args.link_gap_grid.split(',')], 'link_iou': _grid_values(args.link_iou_grid),
-                'link_motion': args.link_motion,
+                'link_motion': args.link_motion, 'split_iou': _grid_values(args.split_iou_grid), 'split_gap': args.split_gap,
+                'split_motion': args.split_motion,
                 'dedup_frames': [int(v) for v in args.dedup_frames_grid.split(',')], 'dedup_iou': _grid_values(args.dedup_iou_grid),
                 'dedup_frac': args.dedup_frac,
                 'smooth_window': [int(v) for v in args.smooth_window_grid.split(',')], 'smooth_sigma': _grid_values(args.smooth_sigma_grid),

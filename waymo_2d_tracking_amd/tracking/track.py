@@ -9,7 +9,7 @@ is not required to exist).
 
 Beyond the reference: `--low-score-threshold=0.3,0.3,1.0,0.3 [--low-iou-threshold 0.5]` lets detections between the two score
 thresholds continue tracks that no detection above `--score-threshold` matched (second association; one
-process only), and the post-passes of refine.py, stitch.py, dedup.py and smooth.py follow when their flags ask for them.
+process only), and the post-passes of split.py, stitch.py, dedup.py, refine.py and smooth.py follow when their flags ask for them.
 """
 import argparse
 import json
@@ -47,6 +47,13 @@ def build_parser():
                         help='drop tracks observed in fewer frames than this (one value, or one per class)')
     parser.add_argument("--track-score", choices=('keep', 'mean'), default='keep',
                         help='mean: every box of a track carries the mean score of its observed boxes')
+    parser.add_argument("--split-iou", type=_floats, default=[0.0],
+                        help='split tracks: cut a track between two consecutive boxes when the boxes extrapolated from the frames before AND after them '
+                             'overlap the other side by less than this IoU (one value, or one per class; 0 = off)')
+    parser.add_argument("--split-gap", type=_ints, default=[0],
+                        help='split tracks: cut a track where more than this many frames lie between two consecutive boxes (one value, or one per class; 0 = off)')
+    parser.add_argument("--split-motion", choices=('linear', 'hold'), default='linear',
+                        help='how a box is extrapolated for --split-iou: moved on by the step next to it, or held')
     parser.add_argument("--link-gap", type=_ints, default=[0],
                         help='stitch tracks: link a track that ends to one of its class that starts up to this many frames later (one value, or one per class)')
     parser.add_argument("--link-iou", type=_floats, default=[0.3],
@@ -84,6 +91,11 @@ def refines(args):
     return max(args.interpolate_gap) > 0 or max(args.min_track_len) > 1 or args.track_score != 'keep'
 
 
+def splits(args):
+    """Whether the flags ask for splitting (tracking/split.py)."""
+    return max(args.split_iou) > 0 or max(args.split_gap) > 0
+
+
 def stitches(args):
     """Whether the flags ask for stitching (tracking/stitch.py)."""
     return max(args.link_gap) > 0
@@ -100,9 +112,17 @@ def smooths(args):
 
 
 def refined(args, packed, out):
-    """The tracker's rows after the post-passes the flags ask for: stitching first, so that a merged track is length-filtered and
-    gap-filled as one; then the suppression of duplicates, which judges a stitched track at its full length and leaves gap filling
-    and the length filter the survivors only; smoothing last, so that filled rows are smoothed too."""
+    """The tracker's rows after the post-passes the flags ask for: splitting first, so that the pieces of an impure track can be
+    linked to the tracks they belong to - a new piece takes the next id of the tracker's counter, as a birth does; then stitching,
+    so that a merged track is length-filtered and gap-filled as one; then the suppression of duplicates, which judges a stitched
+    track at its full length and leaves gap filling and the length filter the survivors only; smoothing last, so that filled rows
+    are smoothed too."""
+    if splits(args):
+        from . import utils as T
+        from .split import split_one
+        # the tracker writes the id counter + 1 for a birth; so does a new piece
+        out = split_one(packed, out, args.split_iou, args.split_gap, args.split_motion, T._GLOBAL_IDS['next'] + 1, len(args.iou_threshold))
+        T._GLOBAL_IDS['next'] += out['n_new']
     if stitches(args):
         from .stitch import stitch_one
         out = stitch_one(packed, out, args.link_gap, args.link_iou, args.link_motion, len(args.iou_threshold))
@@ -224,7 +244,7 @@ def main(argv=None):
         from . import utils as T
         packed = T.pack_streams(predictions)
         tracked_predictions = T.format_tracks(packed, refined(args, packed, tracked_byte(args, packed)))
-    elif refines(args) or stitches(args) or dedups(args) or smooths(args):
+    elif splits(args) or refines(args) or stitches(args) or dedups(args) or smooths(args):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
