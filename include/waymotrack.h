@@ -749,6 +749,53 @@ int wt_dedup_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* str
                          int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped);
 
 /* =================================================================================================
+ * Cross-class track suppression (duplicates across classes; the definition is DESIGN.md section 26)
+ * ================================================================================================= */
+
+/* Suppresses trajectories that are the same object as a stronger one of ANOTHER class (a pedestrian track on the rider of a
+ * tracked cyclist) under J jobs.  Results, slots, streams, trajectories, local indices, c_t, n_t and s_t are those of the track
+ * deduplication above.  A job carries pair_frames[a][b] int32 >= 0 (0: the pair of classes a + 1 and b + 1 is off),
+ * pair_overlap[a][b] float64 not NaN, pair_frac[a][b] float64 in [0, 1] - three (n_classes, n_classes) tables that must be
+ * symmetric, the doubles bit for bit; the diagonal means pairs inside a class - class_prio[c] int32 and measure (0 = IoU,
+ * 1 = IoMin); n_classes <= 16.  A trajectory whose class is outside 1..n_classes takes part in no pair.
+ * Measure of two boxes [x1, y1, x2, y2], with w, h, wh, area_a, area_b as iou_dd computes them: IoU = iou_dd; IoMin = wh / lo,
+ * lo the smaller area, and only when area_a > 0, area_b > 0 and both are finite (otherwise the slot does not match).  A slot
+ * matches when v >= pair_overlap[c_t][c_u] and v > 0; m(t, u) counts the matching slots.
+ * t is stronger than u by: higher class_prio[c], then more rows, then higher score sum, then lower local index (strict, total;
+ * scores must be finite).  t and u are the same object when pair_frames[c_t][c_u] > 0, m(t, u) >= pair_frames[c_t][c_u] and
+ * (double)m(t, u) >= pair_frac[c_t][c_u] * (double)n_weak, n_weak the rows of the WEAKER of the two (one multiplication, rounded
+ * in float64).  Greedy suppression and the outputs are those of the deduplication: out_keep, out_by, out_match (J, n_traj_total),
+ * out_row_keep (J, n_rows), out_dropped (J, n_streams); entries of results the job does not name are -1.  A job whose
+ * pair_frames is all 0 keeps everything.
+ *
+ * The five entry points are the twins of wt_dedup_tracks_*: the device form takes device pointers, is stream-ordered, never
+ * allocates or waits, reports 0 or WT_ERR_CAPACITY in status_dev, answers a workspace smaller than
+ * wt_xclass_tracks_workspace() with WT_ERR_CAPACITY before any launch and does not check the layout (it reads the tables at
+ * (lower class, higher class) only); the host form checks (WT_ERR_INVALID names the result and the row or frame slot, or the
+ * job and the pair), stages and launches. */
+void wt_xclass_tracks_limits(int32_t* lds_trajectories);
+size_t wt_xclass_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_xclass_tracks_rounds(const void* workspace, int32_t n_jobs, int32_t n_streams, int32_t* out_rounds);
+int wt_xclass_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const double* score,
+                         const int32_t* category, const int32_t* local,
+                         const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                         int32_t n_jobs, const int32_t* job_result, const int32_t* job_pair_frames,
+                         const double* job_pair_overlap, const double* job_pair_frac, const int32_t* job_class_prio,
+                         const int32_t* job_measure, int32_t n_classes,
+                         int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped,
+                         int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_xclass_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                          int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                          const double* x, const double* y, const double* w, const double* h, const double* score,
+                          const int32_t* category, const int32_t* local,
+                          const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_pair_frames,
+                          const double* job_pair_overlap, const double* job_pair_frac, const int32_t* job_class_prio,
+                          const int32_t* job_measure, int32_t n_classes,
+                          int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped);
+
+/* =================================================================================================
  * Detection evaluation (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

@@ -36,6 +36,7 @@ UNITS = {
     'track_stitch.hip': ['-ffp-contract=off'],         # track stitching: the extrapolation x + ((x - xp) / (e - p)) * n unfused, the same float64 IoU
     'track_smooth.hip': ['-ffp-contract=off'],         # track smoothing: acc + k[d] * (v(f - d) + v(f + d)) and the quotient, every operation rounded on its own
     'track_dedup.hip': ['-ffp-contract=off'],          # track deduplication: the same float64 IoU, dup_frac * min(n) one multiplication
+    'track_xclass.hip': ['-ffp-contract=off'],         # cross-class suppression: the IoU terms in their order, frac * n_weak one multiplication
     'track_split.hip': ['-ffp-contract=off'],          # track splitting: the extrapolations x + ((x - xo) / slots) * n unfused, the same float64 IoU
     'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_roialign.hip': [],

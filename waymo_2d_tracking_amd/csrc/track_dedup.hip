@@ -4,347 +4,63 @@
 // highest score sum, then lowest index) to weakest and one is suppressed when a stronger KEPT one is its duplicate.  R tracking
 // results come in once; J jobs each name a result and their parameters.  Rows are only selected: no float is produced.
 //
-// Two launches, one 64-lane wavefront per independent problem:
-//   1. summary: per (result, stream), walk the slots once, the rows of a slot lane-parallel: per trajectory its row count, score
-//               sum (row after row in slot order), class and first row; per row its slot and the distance in rows to the previous
-//               and next row of its trajectory.  Shared by all jobs of the result.
-//   2. match:   per (job, stream), in rounds, without a table of pairs.  A round walks the slots; a lane takes a row of the slot
-//               and meets every later row of it (64 of them at a time, held in registers and passed from lane to lane).  A pair of rows whose boxes match belongs to its lanes only at the pair's FIRST
-//               matching slot (both chains are walked back until an earlier matching slot or their start); the owner walks both
-//               chains forward as a merge join for m and decides whether the two trajectories are duplicates.  A trajectory is
-//               undecided, kept or suppressed: a duplicate pair whose stronger side is kept proposes it as suppressor (compare-and-
-//               swap, the stronger proposal stays), one whose stronger side is undecided marks the weaker side pending.  After the
-//               sweep an undecided trajectory that is not pending is suppressed when it has a proposal and kept otherwise.  The
-//               strongest undecided trajectory is never pending, so every round decides one: the rounds are bounded by the longest
-//               chain of duplicates, and by T.  The same wavefront then writes by, match, the row mask and the count.
-// The tables of the match (12 bytes per trajectory) live in LDS up to kLdsTraj trajectories, in the workspace beyond.
+// The summary, the match in rounds and the launches are those of dup_match_device.h, shared with track_xclass.hip; this unit gives
+// them the rules of section 23 as a compile-time policy - its match kernel reads no flag on account of the sharing.
 // Compile with -ffp-contract=off: iou_dd is the IoU the metrics use, and dup_frac * min(n) is one multiplication.
 #include "eval_device.h"
 #include "tracks_device.h"
+#include "dup_match_device.h"
 #include "dedup_host.h"
 
 using namespace wtdev;
+using dup::kLdsTraj;
 
 namespace {
 
-constexpr int kLdsTraj = 1024;                // trajectories of one (result, stream) up to which the match tables stay in LDS
-constexpr int kTableBytes = 12;               // per trajectory: three int32
-constexpr int kUndecided = 0, kKept = 1, kSuppressed = 2;
-
-struct Layout : TrackLayout {                 // device pointers
-    const double* score;
+struct Layout : dup::Layout {                 // device pointers
     const int32_t* job_min_frames;
     const double *job_dup_iou, *job_dup_frac;
 };
 
-struct Summary {
-    int32_t *n, *cls, *first_row, *last_row;  // [n_traj_total]; rows relative to the stream's first row, -1 none
-    double* ssum;                             // [n_traj_total]
-    int32_t *back, *fwd, *slot;               // [n_rows]; rows from this one to the previous / next row of its trajectory, 0 = none
-};
-
-struct Workspace {
-    int32_t* rounds;                          // [J * n_streams] the sweeps the match of each problem took; first in the workspace
-    Summary sum;
-    int32_t *state, *prop, *pend;             // [J * n_traj_total] the tables of the problems above kLdsTraj
-    size_t bytes;
-};
-
-Workspace carve(void* base, size_t n_jobs, size_t n_streams, size_t n_rows, size_t n_traj_total, size_t max_traj) {
-    wt::Carver cv(base);
-    Workspace w;
-    const size_t big = max_traj > (size_t)kLdsTraj ? n_jobs * n_traj_total : 0;
-    w.rounds = cv.take<int32_t>(n_jobs * n_streams + 1);
-    w.sum.n = cv.take<int32_t>(n_traj_total + 1);
-    w.sum.cls = cv.take<int32_t>(n_traj_total + 1);
-    w.sum.first_row = cv.take<int32_t>(n_traj_total + 1);
-    w.sum.last_row = cv.take<int32_t>(n_traj_total + 1);
-    w.sum.ssum = cv.take<double>(n_traj_total + 1);
-    w.sum.back = cv.take<int32_t>(n_rows + 1);
-    w.sum.fwd = cv.take<int32_t>(n_rows + 1);
-    w.sum.slot = cv.take<int32_t>(n_rows + 1);
-    w.state = cv.take<int32_t>(big + 1);
-    w.prop = cv.take<int32_t>(big + 1);
-    w.pend = cv.take<int32_t>(big + 1);
-    w.bytes = cv.off;
-    return w;
-}
-
-__global__ __launch_bounds__(kWave) void dedup_summary_kernel(Layout L, Summary S, int* __restrict__ status) {
-    const int lane = threadIdx.x & 63;
-    const int r = (int)(blockIdx.x / (unsigned)L.n_streams), s = (int)(blockIdx.x % (unsigned)L.n_streams);
-    const Span q = span_of(L, r, s);
-    if (!q.ok) {
-        if (lane == 0) atomicMax(status, kErrCapacity);
-        return;
+// Section 23: pairs inside a class, the IoU, more rows before the higher score sum before the lower index, a share of the
+// shorter one's rows.
+struct DedupPolicy {
+    const int32_t* min_frames;
+    const double *dup_iou, *dup_frac;
+    const int32_t* n;
+    const double* ssum;
+    int C;
+    __device__ __forceinline__ static DedupPolicy make(const Layout& L, int job, const int32_t* n, const double* ssum, const int32_t*) {
+        const size_t o = (size_t)job * L.n_classes;
+        return {L.job_min_frames + o, L.job_dup_iou + o, L.job_dup_frac + o, n, ssum, L.n_classes};
     }
-    const int T = q.T;
-    for (int t = lane; t < T; t += kWave) {
-        const size_t g = (size_t)q.t0 + t;
-        S.n[g] = 0; S.cls[g] = 0; S.first_row[g] = -1; S.last_row[g] = -1; S.ssum[g] = 0.0;
-    }
-    wsync();
-    int err = 0;
-    for_stream_rows(q, L.local, &err, [&](long long d, int t, int fo) {
-        S.back[d] = 0; S.fwd[d] = 0; S.slot[d] = fo;
-        const size_t g = (size_t)q.t0 + t;
-        const int row = (int)(d - q.rs0), prev = S.last_row[g];
-        if (prev < 0) {
-            S.first_row[g] = row;
-            S.cls[g] = L.category[d];
-        } else {
-            S.back[d] = row - prev;
-            S.fwd[q.rs0 + prev] = row - prev;
-        }
-        S.last_row[g] = row;
-        S.n[g] = S.n[g] + 1;
-        S.ssum[g] = S.ssum[g] + L.score[d];                            // one by one in slot order
-    });
-    if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
-}
-
-struct Outputs {
-    int32_t *keep, *by, *match;               // [J * n_traj_total]
-    int32_t* row_keep;                        // [J * n_rows]
-    int64_t* dropped;                         // [J * n_streams]
-};
-
-// every entry: not named; the match kernel fills those of its job's result
-__global__ void dedup_init_kernel(Outputs O, long long n_traj, long long n_row) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_traj) { O.keep[i] = -1; O.by[i] = -1; O.match[i] = -1; }
-    if (i < n_row) O.row_keep[i] = -1;
-}
-
-// The chains of one stream: rows as absolute indices inside [rs0, end); -1 = the chain has ended.
-struct Chains {
-    const int32_t *back, *fwd, *slot;
-    long long rs0, end;
-    __device__ __forceinline__ long long prev(long long d) const {
-        const int b = back[d];
-        return b > 0 && d - b >= rs0 ? d - b : -1;
-    }
-    __device__ __forceinline__ long long next(long long d) const {
-        const int f = fwd[d];
-        return f > 0 && d + f < end ? d + f : -1;
-    }
-};
-
-__device__ __forceinline__ bool boxes_match(const Boxes& B, long long a, long long b, double thr) {
-    double ba[4], bb[4];
-    B.get(a, ba);
-    B.get(b, bb);
-    const double v = iou_dd(ba, bb);
-    return v >= thr && v > 0.;
-}
-
-// m of the two chains from rows a and b on: the slots that hold a row of both whose boxes match
-__device__ __forceinline__ int count_matches(const Chains& ch, const Boxes& B, long long a, long long b, double thr) {
-    int m = 0;
-    while (a >= 0 && b >= 0) {
-        const int sa = ch.slot[a], sb = ch.slot[b];
-        if (sa == sb) {
-            m += boxes_match(B, a, b, thr) ? 1 : 0;
-            a = ch.next(a);
-            b = ch.next(b);
-        } else if (sa < sb) {
-            a = ch.next(a);
-        } else {
-            b = ch.next(b);
-        }
-    }
-    return m;
-}
-
-// whether a slot before the one of rows a and b holds a row of both whose boxes match
-__device__ __forceinline__ bool matched_before(const Chains& ch, const Boxes& B, long long a, long long b, double thr) {
-    a = ch.prev(a);
-    b = ch.prev(b);
-    while (a >= 0 && b >= 0) {
-        const int sa = ch.slot[a], sb = ch.slot[b];
-        if (sa == sb) {
-            if (boxes_match(B, a, b, thr)) return true;
-            a = ch.prev(a);
-            b = ch.prev(b);
-        } else if (sa > sb) {
-            a = ch.prev(a);
-        } else {
-            b = ch.prev(b);
-        }
-    }
-    return false;
-}
-
-__global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, Workspace ws, Outputs O, int* __restrict__ status) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const size_t p = blockIdx.x;
-    int j_, s_;
-    decode_job_stream(p, L.n_streams, &j_, &s_);
-    const int job = j_, s = s_;
-    const Span q = span_of(L, L.job_result[job], s);
-    if (!q.ok) {
-        if (lane == 0) { atomicMax(status, kErrCapacity); O.dropped[p] = 0; ws.rounds[p] = 0; }
-        return;
-    }
-    const int T = q.T, C = L.n_classes;
-    const Summary S = ws.sum;
-    const size_t g0 = (size_t)q.t0;
-    const size_t tbase = (size_t)job * (size_t)L.n_traj_total + g0;
-    const size_t lbase = (size_t)job * (size_t)L.n_rows;
-    const bool in_lds = T <= L.lds_traj;
-    const size_t stride = (size_t)L.lds_traj;
-    int32_t* state = in_lds ? reinterpret_cast<int32_t*>(smem) : ws.state + tbase;
-    int32_t* prop = in_lds ? state + stride : ws.prop + tbase;          // the strongest kept duplicate proposed so far, -1 none
-    int32_t* pend = in_lds ? prop + stride : ws.pend + tbase;           // 1: a stronger duplicate is still undecided
-    const int32_t* min_frames = L.job_min_frames + (size_t)job * C;
-    const double* dup_iou = L.job_dup_iou + (size_t)job * C;
-    const double* dup_frac = L.job_dup_frac + (size_t)job * C;
-    int err = 0;
-    const long long end = stream_end(q, &err);
-    const Chains ch = {S.back, S.fwd, S.slot, q.rs0, end};
-    for (int t = lane; t < T; t += kWave) { state[t] = kUndecided; prop[t] = -1; pend[t] = 0; }
-    wsync();
-
+    // the class when the job deduplicates it, 0 otherwise
+    __device__ __forceinline__ int live_class(int c) const { return c >= 1 && c <= C && min_frames[c - 1] > 0 ? c : 0; }
+    __device__ __forceinline__ bool pair_live(int ca, int cb) const { return ca == cb; }
+    __device__ __forceinline__ double threshold(int ca, int) const { return dup_iou[ca - 1]; }
+    __device__ __forceinline__ int frames(int ca, int) const { return min_frames[ca - 1]; }
+    __device__ __forceinline__ double measure(const double a[4], const double b[4]) const { return iou_dd(a, b); }
     // t is stronger than u: more rows, then the higher score sum, then the lower index
-    auto stronger = [&](int t, int u) {
-        const int nt = S.n[g0 + t], nu = S.n[g0 + u];
+    __device__ __forceinline__ bool stronger(int t, int u) const {
+        const int nt = n[t], nu = n[u];
         if (nt != nu) return nt > nu;
-        const double st = S.ssum[g0 + t], su = S.ssum[g0 + u];
+        const double st = ssum[t], su = ssum[u];
         if (st > su) return true;
         if (st < su) return false;
         return t < u;
-    };
-    // the class of trajectory t when the job deduplicates it, 0 otherwise
-    auto live_class = [&](int t) {
-        const int c = S.cls[g0 + t];
-        return c >= 1 && c <= C && min_frames[c - 1] > 0 ? c : 0;
-    };
+    }
+    __device__ __forceinline__ double need(int ca, int, int t, int u) const {
+        const int nt = n[t], nu = n[u];
+        return dup_frac[ca - 1] * (double)(nt < nu ? nt : nu);
+    }
+};
 
-    int rounds = 0;
-    bool undecided = T > 0 && !err;
-    for (int round = 0; round <= T && undecided; ++round) {    // every round decides a trajectory: at most T rounds
-        ++rounds;
-        for (long long f = q.f0; f < q.f1; ++f) {
-            long long r0, r1;
-            if (!slot_rows(q, f, &r0, &r1) || r1 > end) { err = kErrCapacity; break; }
-            for (long long b = r0; b + 1 < r1; b += kWave) {
-                const long long di = b + lane;
-                int ti = -1, ci = 0, si = kSuppressed;
-                double bi[4] = {0., 0., 0., 0.};
-                if (di < r1) {
-                    ti = L.local[di];
-                    if (ti < 0 || ti >= T) { err = kErrCapacity; ti = -1; }
-                    else { ci = live_class(ti); si = state[ti]; B.get(di, bi); }
-                }
-                const bool active = ti >= 0 && ci > 0 && si != kSuppressed;  // a suppressed trajectory neither suppresses nor is asked again
-                if (__ballot(active) == 0ull) continue;
-                for (long long jb = b; jb < r1; jb += kWave) {              // the later rows of the slot, 64 at a time in registers
-                    const long long dl = jb + lane;
-                    int tl = -1, cl = 0, sl = kSuppressed;
-                    double bl[4] = {0., 0., 0., 0.};
-                    if (dl < r1) {
-                        tl = L.local[dl];
-                        if (tl < 0 || tl >= T) { err = kErrCapacity; tl = -1; }
-                        else { cl = live_class(tl); sl = state[tl]; B.get(dl, bl); }
-                    }
-                    unsigned long long live = __ballot(tl >= 0 && cl > 0 && sl != kSuppressed);
-                    while (live) {                                          // the same row for every lane
-                        const int jj = __builtin_ctzll(live);
-                        live &= live - 1ull;
-                        const long long dj = jb + jj;
-                        const int tj = __builtin_amdgcn_readlane(tl, jj), cj = __builtin_amdgcn_readlane(cl, jj), sj = __builtin_amdgcn_readlane(sl, jj);
-                        const double bj[4] = {bcast_d(bl[0], jj), bcast_d(bl[1], jj), bcast_d(bl[2], jj), bcast_d(bl[3], jj)};
-                        if (!active || dj <= di || cj != ci || tj == ti || (si != kUndecided && sj != kUndecided)) continue;
-                        const double thr = dup_iou[ci - 1];
-                        const double a = iou_dd(bi, bj);                      // in registers: before anything that reads memory
-                        if (!(a >= thr && a > 0.)) continue;
-                        const bool i_strong = stronger(ti, tj);
-                        const int strong = i_strong ? ti : tj, weak = i_strong ? tj : ti;
-                        if ((i_strong ? sj : si) != kUndecided) continue;     // the weaker side is decided: nothing to do
-                        if (matched_before(ch, B, di, dj, thr)) continue;     // the pair belongs to its first matching slot
-                        const int m = count_matches(ch, B, di, dj, thr);
-                        const int ni = S.n[g0 + ti], nj = S.n[g0 + tj];
-                        const double need = dup_frac[ci - 1] * (double)(ni < nj ? ni : nj);
-                        if (m < min_frames[ci - 1] || !((double)m >= need)) continue;
-                        if ((i_strong ? si : sj) == kKept) {
-                            int cur = prop[weak];
-                            while (cur < 0 || (cur != strong && stronger(strong, cur))) {
-                                const int old = atomicCAS(&prop[weak], cur, strong);
-                                if (old == cur) break;
-                                cur = old;
-                            }
-                        } else {
-                            pend[weak] = 1;
-                        }
-                    }
-                }
-            }
-        }
-        wsync();
-        undecided = false;
-        for (int tb = 0; tb < T; tb += kWave) {
-            const int t = tb + lane;
-            bool left = false;
-            if (t < T && state[t] == kUndecided) {
-                if (pend[t]) { pend[t] = 0; left = true; }
-                else state[t] = prop[t] >= 0 ? kSuppressed : kKept;
-            }
-            undecided = undecided || __ballot(left) != 0ull;
-        }
-        wsync();
-        if (undecided && round == T) err = kErrCapacity;               // cannot happen: the strongest undecided one is never pending
-        if (__ballot(err != 0) != 0ull) break;
-    }
-
-    // ---- by, match, count, row mask ----
-    long long n_dropped = 0;
-    for (int t = lane; t < T; t += kWave) {
-        const bool gone = state[t] == kSuppressed;
-        int by = -1, m = 0;
-        if (gone) {
-            by = prop[t];
-            const int c = S.cls[g0 + t];
-            const int fa = S.first_row[g0 + t], fb = by >= 0 && by < T ? S.first_row[g0 + by] : -1;
-            if (c >= 1 && c <= C && fa >= 0 && fb >= 0 && q.rs0 + fa < end && q.rs0 + fb < end)
-                m = count_matches(ch, B, q.rs0 + fa, q.rs0 + fb, dup_iou[c - 1]);
-            else
-                err = kErrCapacity;
-        }
-        O.keep[tbase + t] = gone ? 0 : 1;
-        O.by[tbase + t] = by;
-        O.match[tbase + t] = m;
-        n_dropped += gone;
-    }
-    for (int o = 32; o > 0; o >>= 1) n_dropped += __shfl_xor(n_dropped, o, kWave);
-    for (long long d = q.rs0 + lane; d < end; d += kWave) {
-        const int t = L.local[d];
-        if (t < 0 || t >= T) { err = kErrCapacity; continue; }
-        O.row_keep[lbase + d] = state[t] == kSuppressed ? 0 : 1;
-    }
-    if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
-    if (lane == 0) { O.dropped[p] = n_dropped; ws.rounds[p] = rounds; }
+__global__ __launch_bounds__(kWave) void dedup_match_kernel(Layout L, Boxes B, dup::Workspace ws, dup::Outputs O, int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    dup::match_problem<DedupPolicy>(L, B, ws, O, status, smem);
 }
 
 constexpr const char* kGridText = "%s: %d jobs, %d results x %d streams in one call";
-
-int launch(const char* entry, const Layout& L, const Boxes& B, const Outputs& O, int32_t* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    WT_TRY(wt::ensure_device());
-    const Workspace ws = carve(wt::align_ptr(workspace), (size_t)L.n_jobs, (size_t)L.n_streams, (size_t)L.n_rows, (size_t)L.n_traj_total, (size_t)L.max_traj);
-    WT_TRY(wt::check_workspace_fits(entry, workspace, workspace_bytes, ws.bytes, WT_ERR_CAPACITY));
-    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
-    const size_t P = (size_t)L.n_jobs * (size_t)L.n_streams, RS = (size_t)L.r_sets * (size_t)L.n_streams;
-    const long long n_traj = (long long)L.n_jobs * L.n_traj_total, n_row = (long long)L.n_jobs * L.n_rows;
-    const long long n_init = n_traj > n_row ? n_traj : n_row;
-    if (n_init > 0x7fffffffll * 256) { wt::set_error("%s: %d jobs over %lld rows in one call", entry, (int)L.n_jobs, (long long)L.n_rows); return WT_ERR_CAPACITY; }
-    if (n_init) hipLaunchKernelGGL(dedup_init_kernel, dim3((unsigned)((n_init + 255) / 256)), dim3(256), 0, stream, O, n_traj, n_row);
-    if (P) {
-        hipLaunchKernelGGL(dedup_summary_kernel, dim3((unsigned)RS), dim3(kWave), 0, stream, L, ws.sum, (int*)status_dev);
-        hipLaunchKernelGGL(dedup_match_kernel, dim3((unsigned)P), dim3(kWave), (size_t)L.lds_traj * kTableBytes, stream, L, B, ws, O, (int*)status_dev);
-    }
-    WT_HIP(hipGetLastError());
-    return WT_OK;
-}
 
 }  // namespace
 
@@ -355,18 +71,11 @@ void wt_dedup_tracks_limits(int32_t* lds_trajectories) {
 }
 
 size_t wt_dedup_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj) {
-    if (n_jobs < 0 || n_streams < 0 || n_rows < 0 || n_traj_total < 0 || max_traj < 0) return 0;
-    return carve(nullptr, (size_t)n_jobs, (size_t)n_streams, (size_t)n_rows, (size_t)n_traj_total, (size_t)(max_traj > 0 ? max_traj : 1)).bytes + 256;
+    return dup::workspace_bytes(n_jobs, n_streams, n_rows, n_traj_total, max_traj);
 }
 
 int wt_dedup_tracks_rounds(const void* workspace, int32_t n_jobs, int32_t n_streams, int32_t* out_rounds) {
-    const size_t P = (size_t)(n_jobs > 0 ? n_jobs : 0) * (size_t)(n_streams > 0 ? n_streams : 0);
-    if (!workspace || n_jobs < 0 || n_streams < 0 || (P && !out_rounds)) {
-        wt::set_error("wt_dedup_tracks_rounds: bad argument");
-        return WT_ERR_INVALID;
-    }
-    if (P) WT_HIP(hipMemcpy(out_rounds, wt::align_ptr(const_cast<void*>(workspace)), 4 * P, hipMemcpyDeviceToHost));
-    return WT_OK;
+    return dup::read_rounds("wt_dedup_tracks_rounds", workspace, n_jobs, n_streams, out_rounds);
 }
 
 int wt_dedup_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
@@ -389,8 +98,8 @@ int wt_dedup_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stre
     wt::fill_track_layout(&L, dev, n_rows, traj_offsets, n_traj_total, max_traj, n_jobs, job_result, kLdsTraj);
     L.score = score; L.job_min_frames = job_min_frames; L.job_dup_iou = job_dup_iou; L.job_dup_frac = job_dup_frac;
     const Boxes B = {x, y, w, h};
-    const Outputs O = {out_keep, out_by, out_match, out_row_keep, out_dropped};
-    return launch("wt_dedup_tracks_dev", L, B, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    const dup::Outputs O = {out_keep, out_by, out_match, out_row_keep, out_dropped};
+    return dup::launch("wt_dedup_tracks_dev", dedup_match_kernel, L, B, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int wt_dedup_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
@@ -409,31 +118,14 @@ int wt_dedup_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* str
         wt::set_error("wt_dedup_tracks_host: bad argument");
         return WT_ERR_INVALID;
     }
+    wt::DevBuf jm, ji, jf;
     WT_TRY(wt::check_track_args("wt_dedup_tracks_host", n_frames, n_streams, r_sets, (int64_t)nr, n_traj_total, max_traj, n_jobs, n_classes, true,
                                 wt::grid_fits(n_jobs, n_streams) && wt::grid_fits(r_sets, n_streams), kGridText, (int)n_jobs, (int)r_sets, (int)n_streams));
-    WT_TRY(wt::ensure_device());
-    wt::StagedTrackSet st;
-    wt::DevBuf jm, ji, jf, ok, ob, om, orr, od, dws;
-    WT_TRY(st.upload(in, n_jobs, job_result));
-    WT_TRY(jm.upload(job_min_frames, 4 * jc)); WT_TRY(ji.upload(job_dup_iou, 8 * jc)); WT_TRY(jf.upload(job_dup_frac, 8 * jc));
-    WT_TRY(ok.alloc(4 * J * nt)); WT_TRY(ob.alloc(4 * J * nt)); WT_TRY(om.alloc(4 * J * nt)); WT_TRY(orr.alloc(4 * J * nr));
-    WT_TRY(od.alloc(8 * J * (size_t)n_streams));
-    const size_t wsb = wt_dedup_tracks_workspace(n_jobs, n_streams, (int64_t)nr, n_traj_total, max_traj);
-    WT_TRY(dws.alloc(wsb));
-    Layout L;
-    st.fill(&L, n_traj_total, max_traj, n_jobs, kLdsTraj);
-    L.score = st.dev.score; L.job_min_frames = jm.as<int32_t>(); L.job_dup_iou = ji.as<double>(); L.job_dup_frac = jf.as<double>();
-    const Boxes B = {st.dev.x, st.dev.y, st.dev.w, st.dev.h};
-    const Outputs O = {ok.as<int32_t>(), ob.as<int32_t>(), om.as<int32_t>(), orr.as<int32_t>(), od.as<int64_t>()};
-    WT_TRY(launch("wt_dedup_tracks_host", L, B, O, st.status.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_TRY(st.finish("dedup", "counts or offsets"));
-    if (J * nt) {
-        WT_HIP(hipMemcpy(out_keep, ok.p, 4 * J * nt, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(out_by, ob.p, 4 * J * nt, hipMemcpyDeviceToHost));
-        WT_HIP(hipMemcpy(out_match, om.p, 4 * J * nt, hipMemcpyDeviceToHost));
-    }
-    if (J * nr) WT_HIP(hipMemcpy(out_row_keep, orr.p, 4 * J * nr, hipMemcpyDeviceToHost));
-    if (J * (size_t)n_streams) WT_HIP(hipMemcpy(out_dropped, od.p, 8 * J * (size_t)n_streams, hipMemcpyDeviceToHost));
-    return WT_OK;
+    return dup::run_host<Layout>("wt_dedup_tracks_host", "dedup", dedup_match_kernel, in, n_jobs, job_result, n_traj_total, max_traj, [&](Layout* L) {
+        WT_TRY(jm.upload(job_min_frames, 4 * jc)); WT_TRY(ji.upload(job_dup_iou, 8 * jc)); WT_TRY(jf.upload(job_dup_frac, 8 * jc));
+        L->job_min_frames = jm.as<int32_t>(); L->job_dup_iou = ji.as<double>(); L->job_dup_frac = jf.as<double>();
+        return (int)WT_OK;
+    }, out_keep, out_by, out_match, out_row_keep, out_dropped);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Device side shared by the track post-passes (track_refine.hip, track_stitch.hip, track_smooth.hip, track_dedup.hip,
-// track_split.hip; DESIGN.md section 20, "The shared layer"): the layout all five take - R results over the frame slots of S streams, CSR offsets, a dense
+// track_split.hip, track_xclass.hip; DESIGN.md section 20, "The shared layer"): the layout all six take - R results over the frame slots of S streams, CSR offsets, a dense
 // per-stream trajectory index per row, J jobs that each name a result - the rows and trajectories of one (result, stream) with
 // every bound checked once, and the walk of a wavefront over them.
 // Include it after eval_device.h, only from units compiled with -ffp-contract=off.

@@ -1,5 +1,5 @@
 // Host side shared by the track post-passes (track_refine.hip, track_stitch.hip, track_smooth.hip, track_dedup.hip,
-// track_split.hip; DESIGN.md section 20, "The shared layer"): the tracking results all five take, the checks every entry point makes on them before it
+// track_split.hip, track_xclass.hip; DESIGN.md section 20, "The shared layer"): the tracking results all six take, the checks every entry point makes on them before it
 // touches a device, and the staging of a host-side input in device memory.  Host code only, so that the checks can also be
 // compiled into programs of their own (tools/*_layout_check.cpp).
 #pragma once

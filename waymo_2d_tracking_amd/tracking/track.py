@@ -9,7 +9,8 @@ is not required to exist).
 
 Beyond the reference: `--low-score-threshold=0.3,0.3,1.0,0.3 [--low-iou-threshold 0.5]` lets detections between the two score
 thresholds continue tracks that no detection above `--score-threshold` matched (second association; one
-process only), and the post-passes of split.py, stitch.py, dedup.py, refine.py and smooth.py follow when their flags ask for them.
+process only), and the post-passes of split.py, stitch.py, dedup.py, xclass.py, refine.py and smooth.py follow when their flags ask
+for them.
 """
 import argparse
 import json
@@ -26,6 +27,10 @@ def _floats(s):
 
 def _ints(s):
     return [int(item) for item in s.split(',')]
+
+
+def _pairs(s):
+    return [tuple(int(c) for c in item.split(':')) for item in s.split(',')]
 
 
 def build_parser():
@@ -67,6 +72,19 @@ def build_parser():
                         help='lowest IoU of the two tracks\' boxes in a frame that counts (one value, or one per class); read when --dedup-frames is set')
     parser.add_argument("--dedup-frac", type=_floats, default=[0.5],
                         help='lowest share of the shorter track\'s frames that must count (one value, or one per class); read when --dedup-frames is set')
+    parser.add_argument("--xclass-pairs", type=_pairs, default=None,
+                        help='suppress duplicate tracks across classes: the class pairs that are compared, as 2:4,1:4 (absent = off); a track is '
+                             'dropped when a stronger one of the other class overlaps it in enough frames')
+    parser.add_argument("--xclass-frames", type=_ints, default=[3],
+                        help='lowest number of frames in which the two tracks\' boxes overlap (one value, or one per listed pair; 0 = the pair is off)')
+    parser.add_argument("--xclass-overlap", type=_floats, default=[0.7],
+                        help='lowest overlap of the two tracks\' boxes in a frame that counts (one value, or one per listed pair)')
+    parser.add_argument("--xclass-frac", type=_floats, default=[0.5],
+                        help='lowest share of the weaker track\'s frames that must count (one value, or one per listed pair)')
+    parser.add_argument("--xclass-measure", choices=('iou', 'iomin'), default='iomin',
+                        help='the overlap of two boxes: intersection over union, or over the smaller area (a rider box inside a cyclist box)')
+    parser.add_argument("--xclass-prio", type=_ints, default=[0],
+                        help='class priority, one int per class: of two overlapping tracks the one of the higher priority stays, whatever their lengths')
     parser.add_argument("--smooth-window", type=_ints, default=[0],
                         help='smooth tracks: every box becomes the weighted mean of its track\'s boxes up to this many frames to either side, '
                              'both sides or neither (one value, or one per class)')
@@ -106,6 +124,27 @@ def dedups(args):
     return max(args.dedup_frames) > 0
 
 
+def xclass_pairs(args):
+    """The pairs of tracking/xclass.py that the flags switch on: {(a, b): {'frames', 'overlap', 'frac'}}; empty = the pass is off."""
+    if not args.xclass_pairs:
+        return {}
+    n = len(args.xclass_pairs)
+    if any(len(pair) != 2 for pair in args.xclass_pairs):
+        raise SystemExit('--xclass-pairs takes pairs of classes, as 2:4,1:4')
+
+    def per_pair(values, flag):
+        if len(values) not in (1, n):
+            raise SystemExit('%s needs one value, or one per listed pair (%d)' % (flag, n))
+        return list(values) * n if len(values) == 1 else list(values)
+    frames, overlap, frac = per_pair(args.xclass_frames, '--xclass-frames'), per_pair(args.xclass_overlap, '--xclass-overlap'), per_pair(args.xclass_frac, '--xclass-frac')
+    return dict((pair, {'frames': f, 'overlap': o, 'frac': q}) for pair, f, o, q in zip(args.xclass_pairs, frames, overlap, frac) if f > 0)
+
+
+def xclasses(args):
+    """Whether the flags ask for the suppression of duplicate tracks across classes (tracking/xclass.py)."""
+    return bool(xclass_pairs(args))
+
+
 def smooths(args):
     """Whether the flags ask for smoothing (tracking/smooth.py)."""
     return max(args.smooth_window) > 0
@@ -115,8 +154,8 @@ def refined(args, packed, out):
     """The tracker's rows after the post-passes the flags ask for: splitting first, so that the pieces of an impure track can be
     linked to the tracks they belong to - a new piece takes the next id of the tracker's counter, as a birth does; then stitching,
     so that a merged track is length-filtered and gap-filled as one; then the suppression of duplicates, which judges a stitched
-    track at its full length and leaves gap filling and the length filter the survivors only; smoothing last, so that filled rows
-    are smoothed too."""
+    track at its full length and leaves gap filling and the length filter the survivors only - inside a class first, then across
+    the class pairs that are switched on; smoothing last, so that filled rows are smoothed too."""
     if splits(args):
         from . import utils as T
         from .split import split_one
@@ -129,6 +168,9 @@ def refined(args, packed, out):
     if dedups(args):
         from .dedup import dedup_one
         out = dedup_one(packed, out, args.dedup_frames, args.dedup_iou, args.dedup_frac, len(args.iou_threshold))
+    if xclasses(args):
+        from .xclass import xclass_one
+        out = xclass_one(packed, out, xclass_pairs(args), args.xclass_prio, args.xclass_measure, len(args.iou_threshold))
     if refines(args):
         from .refine import refine_one
         out = refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, len(args.iou_threshold))
@@ -244,7 +286,7 @@ def main(argv=None):
         from . import utils as T
         packed = T.pack_streams(predictions)
         tracked_predictions = T.format_tracks(packed, refined(args, packed, tracked_byte(args, packed)))
-    elif splits(args) or refines(args) or stitches(args) or dedups(args) or smooths(args):
+    elif splits(args) or refines(args) or stitches(args) or dedups(args) or xclasses(args) or smooths(args):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
