@@ -493,6 +493,50 @@ int wt_mot_hota_host(int64_t n_gt, const double* gx, const double* gy, const dou
                      int64_t* hota_counts, double* hota_sums, int64_t* hyp_match);
 
 /* =================================================================================================
+ * MOT trajectory coverage (MT / PT / ML and fragmentations per class and Waymo difficulty level; the definition is DESIGN.md
+ * section 27)
+ * ================================================================================================= */
+
+/* Says what happened to every ground-truth trajectory under the matching of wt_mot_eval_*: a consumer of the hyp_match and
+ * hyp_switch that call leaves behind, integers only.  Three passes on one stream: a mark pass (one lane per result row writes one
+ * byte at (set, matched ground-truth row)), a link pass (one wavefront per (stream, class), once per call, chains every
+ * ground-truth row to the next row of its trajectory) and a walk pass (one lane per (result set, trajectory) follows its chain).
+ * At LEVEL_1 the rows with level 2 do not exist; a trajectory without a row at a level is none at that level.  Per trajectory
+ * and level: len rows, tracked of them matched, frag = runs of unmatched rows with a matched row before and after, idsw =
+ * matched rows whose match is an identity switch.  Mostly tracked: 5 * tracked >= 4 * len; mostly lost: 5 * tracked < len;
+ * partially tracked otherwise.
+ *
+ * Ground truth: g_category, g_level, frame_gt_offsets, stream_frame_offsets as wt_mot_eval_* takes them; g_traj and g_ntraj
+ * (n_streams, n_classes) as wt_mot_identity_* takes them (each count <= 4096, a stream has at most 65535 frames; more is
+ * WT_ERR_CAPACITY); traj_offsets (n_streams * n_classes + 1) int64 = the exclusive scan of g_ntraj, total_traj its last entry: the
+ * trajectories of all (stream, class) are numbered in that order.
+ * Results: k_sets, n_hyp, set_row_offsets as wt_mot_eval_dev takes them, and its outputs hyp_match and hyp_switch (n_hyp each).
+ * Outputs: cov_counts (K, n_streams, n_classes, 2, 5) int64 = traj, mt, pt, ml, frag for LEVEL_1, LEVEL_2;
+ *          traj_stats (K, total_traj, 2, 4) int32 = len, tracked, frag, idsw for LEVEL_1, LEVEL_2, may be NULL (16-byte aligned).
+ * The device form takes device pointers, is stream-ordered, never allocates or synchronises, clears what it reads inside the
+ * call, and reports in status_dev (device int32) 0 or WT_ERR_CAPACITY (counts, offsets, trajectory indices or matches that do not
+ * fit the rows), after which that (stream, class)'s outputs stay zero.  A workspace smaller than wt_mot_coverage_workspace() says
+ * is WT_ERR_INVALID and nothing is launched.  pass_events: NULL, or four hipEvent_t the call records before the clears and after
+ * each pass (for measurements).  It does not check the layout; the host form does (WT_ERR_INVALID names the frame).
+ * The host form takes the arguments of wt_mot_eval_host (g_id / h_id are object ids) and the trajectory columns beside them,
+ * stages everything itself and runs wt_mot_eval_dev and the three passes on one stream. */
+size_t wt_mot_coverage_workspace(int32_t k_sets, int32_t n_streams, int32_t n_classes, int64_t n_gt, int64_t total_traj);
+int wt_mot_coverage_dev(int64_t n_gt, const int32_t* g_category, const int32_t* g_level, const int32_t* g_traj,
+                        int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                        int32_t n_classes, const int32_t* g_ntraj, const int64_t* traj_offsets, int64_t total_traj,
+                        int32_t k_sets, int64_t n_hyp, const int64_t* set_row_offsets, const int64_t* hyp_match, const uint8_t* hyp_switch,
+                        int64_t* cov_counts, int32_t* traj_stats, int32_t* status_dev,
+                        void* workspace, size_t workspace_bytes, void* stream, void* const* pass_events);
+int wt_mot_coverage_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh,
+                         const int32_t* g_category, const int32_t* g_level, const int32_t* g_id, const int32_t* g_traj,
+                         int64_t n_frames, const int64_t* frame_gt_offsets, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t k_sets, const int64_t* set_row_offsets, const int64_t* frame_hyp_offsets,
+                         const double* hx, const double* hy, const double* hw, const double* hh,
+                         const int32_t* h_category, const int32_t* h_id,
+                         const int32_t* g_ntraj, int32_t n_classes, const double* thr,
+                         int64_t* cov_counts, int32_t* traj_stats);
+
+/* =================================================================================================
  * Track refinement (length filter, linear gap filling, mean track score; the definition is DESIGN.md section 20)
  * ================================================================================================= */
 

@@ -1,0 +1,121 @@
+"""Hand-worked cases that pin the definition of the trajectory coverage table on the plain-Python reference
+tests/coverage_ref.py, which the GPU tests then hold the kernels to."""
+import math
+
+import coverage_ref
+from coverage_cases import ann, by_pattern, copies, stats_of
+
+
+def _eval(anns, patterns, extra_rows=(), **kw):
+    return coverage_ref.evaluate(anns, copies(anns, by_pattern(patterns), **kw) + list(extra_rows))
+
+
+def test_mostly_tracked_partially_tracked_mostly_lost():
+    anns = [ann(f, o) for o, n in (('o1', 5), ('o2', 5), ('o3', 5), ('o4', 6)) for f in range(n)]
+    ref = _eval(anns, {'o1': '11110', 'o2': '00100', 'o3': '00000', 'o4': '010000'})
+    assert [coverage_ref.classify(stats_of(ref, o)[2]) for o in ('o1', 'o2', 'o3', 'o4')] == ['mt', 'pt', 'ml', 'ml']
+    row = ref['table'][1][2]
+    assert (row['traj'], row['mt'], row['pt'], row['ml']) == (4, 1, 1, 2) and row['MT'] == 0.25 and row['ML'] == 0.5
+    assert ref['table']['ALL'][2] == row and ref['table'][2][2]['traj'] == 0
+
+
+def test_fragmentations_count_inner_runs_only():
+    assert coverage_ref.fragmentations([1, 0, 0, 1, 0, 1, 0]) == 2
+    assert coverage_ref.fragmentations([0, 0, 1, 1, 0]) == 0
+    assert coverage_ref.fragmentations([0, 0, 0]) == 0 and coverage_ref.fragmentations([]) == 0
+    anns = [ann(f, 'o1') for f in range(7)] + [ann(f, 'o2') for f in range(5)]
+    ref = _eval(anns, {'o1': '1001010', 'o2': '01010'})
+    assert stats_of(ref, 'o1')[2] == {'len': 7, 'tracked': 3, 'frag': 2, 'idsw': 0}
+    assert stats_of(ref, 'o2')[2] == {'len': 5, 'tracked': 2, 'frag': 1, 'idsw': 0}
+    assert ref['table'][1][2]['frag'] == 3 and ref['table'][1][2]['FM'] == 3
+
+
+def test_a_frame_without_the_object_does_not_interrupt_it():
+    anns = [ann(f, 'o1') for f in (0, 1, 3, 4)] + [ann(f, 'o2') for f in range(5)]
+    ref = _eval(anns, {})
+    assert stats_of(ref, 'o1')[2] == {'len': 4, 'tracked': 4, 'frag': 0, 'idsw': 0}
+    # the same when the object is missed around the hole: one run, not two
+    ref = _eval(anns, {'o1': '1001'})
+    assert stats_of(ref, 'o1')[2]['frag'] == 1
+
+
+def test_a_level_2_row_exists_at_level_2_only():
+    anns = [ann(0, 'o1'), ann(1, 'o1', level=2), ann(2, 'o1')] + [ann(f, 'o2', level=2) for f in range(3)]
+    ref = _eval(anns, {'o1': '101', 'o2': '111'})
+    assert stats_of(ref, 'o1')[2] == {'len': 3, 'tracked': 2, 'frag': 1, 'idsw': 0}
+    assert stats_of(ref, 'o1')[1] == {'len': 2, 'tracked': 2, 'frag': 0, 'idsw': 0}
+    # a trajectory made of level-2 rows only is no LEVEL_1 trajectory
+    assert stats_of(ref, 'o2')[1]['len'] == 0 and stats_of(ref, 'o2')[2]['len'] == 3
+    assert ref['table'][1][1]['traj'] == 1 and ref['table'][1][2]['traj'] == 2
+    assert ref['table'][1][1]['mt'] == 1 and ref['table'][1][2] == dict(traj=2, mt=1, pt=1, ml=0, frag=1, MT=0.5, ML=0.0, FM=1)
+    # the sums are those of CLEAR-MOT
+    for lv in (1, 2):
+        assert sum(st[lv]['len'] for _, st in ref['trajectories']) == ref['mot']['table'][1][lv]['gt']
+        assert sum(st[lv]['tracked'] for _, st in ref['trajectories']) == ref['mot']['table'][1][lv]['tp']
+
+
+def test_identity_switches_are_counted_per_trajectory():
+    anns = [ann(f, 'o1') for f in range(4)] + [ann(f, 'o2') for f in range(4)]
+    ref = _eval(anns, {'o1': '1101'}, hyp_id=lambda a: 'h%s_%d' % (a['object_id'], 0 if a['object_id'] == 'o2' else int(a['image_id'].split('/')[1]) // 2))
+    assert stats_of(ref, 'o1')[2] == {'len': 4, 'tracked': 3, 'frag': 1, 'idsw': 1}
+    assert stats_of(ref, 'o2')[2]['idsw'] == 0
+    assert ref['mot']['table'][1][2]['idsw'] == 1
+
+
+def test_one_object_id_in_two_classes_or_cameras_is_two_trajectories():
+    anns = [ann(f, 'o1', cat=c, cam=cam) for f in range(3) for c in (1, 2) for cam in ('FRONT', 'SIDE')]
+    ref = _eval(anns, {})
+    assert len(ref['trajectories']) == 4
+    assert ref['table'][1][2]['traj'] == 2 and ref['table'][2][2]['traj'] == 2 and ref['table']['ALL'][2]['traj'] == 4
+    assert ref['per_stream'][('seg', 'SIDE')][2][2] == dict(traj=1, mt=1, pt=0, ml=0, frag=0)
+    assert [k for k, _ in ref['trajectories']] == [(('seg', 'FRONT'), 1, 'o1'), (('seg', 'FRONT'), 2, 'o1'),
+                                                   (('seg', 'SIDE'), 1, 'o1'), (('seg', 'SIDE'), 2, 'o1')]
+
+
+def test_result_rows_outside_the_ground_truth_change_nothing():
+    anns = [ann(f, 'o1') for f in range(5)]
+    plain = _eval(anns, {'o1': '10110'})
+    stray = [{'image_id': 'seg/9/FRONT', 'bbox': anns[0]['bbox'], 'score': 1.0, 'category_id': 1, 'object_id': 'ho1'},
+             {'image_id': 'nowhere/0/FRONT', 'bbox': anns[0]['bbox'], 'score': 1.0, 'category_id': 1, 'object_id': 'ho1'}]
+    more = _eval(anns, {'o1': '10110'}, extra_rows=stray)
+    assert more['ignored_rows'] == 2 and plain['ignored_rows'] == 0
+    assert more['table'] == plain['table'] and more['trajectories'] == plain['trajectories']
+    assert plain['table'][1][2] == dict(traj=1, mt=0, pt=1, ml=0, frag=1, MT=0.0, ML=0.0, FM=1)
+
+
+def test_empty_sides():
+    anns = [ann(f, 'o1') for f in range(3)]
+    none = coverage_ref.evaluate(anns, [])
+    assert none['table'][1][2] == dict(traj=1, mt=0, pt=0, ml=1, frag=0, MT=0.0, ML=1.0, FM=0)
+    for ref in (coverage_ref.evaluate([], copies(anns, lambda a: True)), coverage_ref.evaluate([], [])):
+        for c in (1, 2, 3, 4, 'ALL'):
+            for lv in (1, 2):
+                row = ref['table'][c][lv]
+                assert row['traj'] == row['mt'] == row['pt'] == row['ml'] == row['frag'] == 0
+                assert math.isnan(row['MT']) and math.isnan(row['ML']) and row['FM'] == 0
+        assert ref['trajectories'] == []
+
+
+def test_tracked_sequence_with_every_class_of_the_table():
+    """The sequence the GPU tests track (seed 11), tracked here by the C SORT oracle under the second of their settings: the
+    reference finds mostly tracked, partially tracked and mostly lost trajectories and fragmentations in it."""
+    import json
+    from oracle import oracle as O
+    from waymo_2d_tracking_amd import synthetic as syn
+    from waymo_2d_tracking_amd.tracking import utils as T
+    dets, gt_json = syn.make_tracking_json(11, n_segments=1, n_frames=24, n_objects=40, integer_boxes=True)
+    predictions = {}
+    for e in dets:
+        seg, fr, cam = e['image_id'].split('/')
+        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
+            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
+    packed = T.pack_streams(predictions)
+    out = O.track_streams(packed, 1, 1, [0.6, 0.6, 1.0, 0.6], [0.3, 0.3, 1.0, 0.3])
+    ref = coverage_ref.evaluate(gt_json, json.loads(json.dumps(T.format_tracks(packed, out))))
+    assert ref['table'][1][2] == dict(traj=116, mt=10, pt=101, ml=5, frag=179, MT=10 / 116, ML=5 / 116, FM=179)
+    assert ref['table']['ALL'][2]['traj'] == 200 and ref['table']['ALL'][1]['traj'] == 161
+    for lv in (1, 2):
+        for c in (1, 2, 4):
+            mine = [st[lv] for (_, cc, _), st in ref['trajectories'] if cc == c]
+            mot = ref['mot']['table'][c][lv]
+            assert (sum(s['len'] for s in mine), sum(s['tracked'] for s in mine), sum(s['idsw'] for s in mine)) == (mot['gt'], mot['tp'], mot['idsw'])

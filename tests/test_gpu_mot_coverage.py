@@ -1,0 +1,210 @@
+"""HIP trajectory coverage (csrc/mot_coverage.hip through tracking/evaluate.py) against the plain-Python restatement
+tests/coverage_ref.py: every count, every per-trajectory row and the table must be EQUAL - there is no floating point in it."""
+import json
+
+import numpy as np
+import pytest
+
+import coverage_cases
+import coverage_ref
+from test_gpu_mot import SETTINGS, _track, same_number
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module', params=[True, False], ids=['integer_boxes', 'fractional_boxes'])
+def sequence(request):
+    from waymo_2d_tracking_amd import synthetic as syn
+    dets, gt_json = syn.make_tracking_json(11 if request.param else 12, n_segments=1, n_frames=24, n_objects=40,
+                                           integer_boxes=request.param)
+    results = [_track(dets, *s) for s in SETTINGS]
+    return gt_json, results, [coverage_ref.evaluate(gt_json, r) for r in results], request.param
+
+
+def assert_equals_reference(got, ref, n_classes=4, per_trajectory=False):
+    """CoverageResult == coverage_ref.evaluate() output: everything, exactly."""
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    assert got.stream_keys == ref['stream_keys']
+    for s, key in enumerate(got.stream_keys):
+        for c in range(1, n_classes + 1):
+            for li, lv in enumerate((1, 2)):
+                exp = ref['per_stream'][key][c][lv]
+                assert got.cov_counts[s, c - 1, li].tolist() == [exp[f] for f in coverage_ref.COV_FIELDS], (key, c, lv)
+    assert got.ignored_rows == ref['ignored_rows']
+    for c, rows in ref['table'].items():
+        for lv, row in rows.items():
+            assert sorted(got.table[c][lv]) == sorted(row)
+            for name, v in row.items():
+                assert same_number(got.table[c][lv][name], v), (c, lv, name, got.table[c][lv][name], v)
+    if per_trajectory:
+        assert [tuple(k) for k in got.traj_keys] == [k for k, _ in ref['trajectories']]
+        exp = [[[st[lv][f] for f in coverage_ref.TRAJ_FIELDS] for lv in (1, 2)] for _, st in ref['trajectories']]
+        assert got.traj_stats.dtype == np.int32 and got.traj_stats.shape == (len(exp), 2, 4)
+        assert got.traj_stats.tolist() == exp
+    assert E.TRAJ_FIELDS == coverage_ref.TRAJ_FIELDS
+
+
+def test_device_equals_reference_on_tracked_sequences(sequence):
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results, refs, integer_boxes = sequence
+    # the reference's own numbers first: every class of the table occurs, LEVEL_1 has fewer trajectories, the results differ
+    all2 = [r['table']['ALL'][2] for r in refs]
+    for f in ('mt', 'pt', 'ml', 'frag'):
+        assert sum(row[f] for row in all2) > 0, f
+    assert all(r['table']['ALL'][1]['traj'] < r['table']['ALL'][2]['traj'] for r in refs)
+    assert len(set(json.dumps(row, sort_keys=True) for row in all2)) == 3
+    if integer_boxes:                                # seed 11, setting (1, 1), class 1: worked out with the C SORT oracle and mot_ref on a CPU
+        assert [refs[1]['table'][1][2][f] for f in coverage_ref.COV_FIELDS] == [116, 10, 101, 5, 179]
+    gt = E.load_ground_truth(gt_json)
+    got = E.evaluate_coverage(gt, [E.load_tracks(r) for r in results], per_trajectory=True)
+    assert len(got) == 3
+    for g, r in zip(got, refs):
+        assert_equals_reference(g, r, per_trajectory=True)
+    # without the per-trajectory table the counts are the same
+    plain = E.evaluate_coverage(gt, [E.load_tracks(r) for r in results])
+    assert all(p.traj_stats is None and np.array_equal(p.cov_counts, g.cov_counts) for p, g in zip(plain, got))
+
+
+@pytest.mark.parametrize('name', sorted(coverage_cases.CASES))
+def test_adversarial_layouts_row_for_row_and_the_sums_of_clear_mot(name):
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results, check, refs = coverage_cases.case(name)
+    gt = E.load_ground_truth(gt_json)
+    tracks = [E.load_tracks(r) for r in results]
+    got = E.evaluate_coverage(gt, tracks, per_trajectory=True)
+    mot = E.evaluate_tracks(gt, tracks)
+    for g, m, r in zip(got, mot, refs):
+        assert_equals_reference(g, r, per_trajectory=True)
+        n_classes = g.cov_counts.shape[1]
+        for c in range(1, n_classes + 1):
+            mine = np.asarray([i for i, k in enumerate(g.traj_keys) if k[1] == c], dtype=np.int64)
+            for li, lv in enumerate((1, 2)):
+                st = g.traj_stats[mine, li] if mine.size else np.zeros((0, 4), np.int32)
+                assert int(st[:, 0].sum()) == m.table[c][lv]['gt'] and int(st[:, 1].sum()) == m.table[c][lv]['tp']
+                assert int(st[:, 3].sum()) == m.table[c][lv]['idsw'] and int(st[:, 2].sum()) == g.table[c][lv]['frag']
+                row = g.table[c][lv]
+                assert row['mt'] + row['pt'] + row['ml'] == row['traj'] == int((st[:, 0] > 0).sum())
+
+
+def test_device_form_equals_host_form_and_clears_between_launches(sequence):
+    import torch
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results, _, _ = sequence
+    gt = E.load_ground_truth(gt_json)
+    tracks = [E.load_tracks(r) for r in results]
+    host = E.evaluate_coverage(gt, tracks, per_trajectory=True)
+    dev = E.DeviceCoverage(gt, tracks, per_trajectory=True)
+    dev.launch()
+    dev.launch()                                     # no read in between: the second call clears what the first one left
+    from_dev = dev.results()
+    # an evaluation the caller already launched: only the coverage kernels run here
+    ev = E.DeviceEvaluation(gt, tracks[::-1])
+    ev.launch()
+    shared = E.DeviceCoverage(gt, tracks[::-1], per_trajectory=True, evaluation=ev)
+    shared.launch()
+    from_shared = shared.results()[::-1]
+    for h, a, b in zip(host, from_dev, from_shared):
+        for other in (a, b):
+            assert np.array_equal(h.cov_counts, other.cov_counts) and np.array_equal(h.traj_stats, other.traj_stats)
+            assert h.traj_keys == other.traj_keys and h.ignored_rows == other.ignored_rows and h.table[1] == other.table[1]
+    torch.cuda.synchronize()
+
+
+def test_64_copies_of_one_result_give_64_equal_rows(sequence):
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results, refs, _ = sequence
+    gt = E.load_ground_truth(gt_json)
+    tr = E.load_tracks(results[0])
+    dev = E.DeviceCoverage(gt, [tr] * 64, per_trajectory=True)
+    dev.launch()
+    got = dev.results()
+    assert len(got) == 64
+    assert_equals_reference(got[0], refs[0], per_trajectory=True)
+    for g in got[1:]:
+        assert np.array_equal(g.cov_counts, got[0].cov_counts) and np.array_equal(g.traj_stats, got[0].traj_stats)
+
+
+def test_a_workspace_one_byte_short_is_refused_and_nothing_is_written(sequence):
+    import torch
+    from waymo_2d_tracking_amd import _lib
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results, _, _ = sequence
+    gt = E.load_ground_truth(gt_json)
+    tracks = [E.load_tracks(results[0])]
+    ev = E.DeviceEvaluation(gt, tracks)
+    ev.launch()
+    need = E.DeviceCoverage(gt, tracks, evaluation=ev).ws_bytes
+    dev = E.DeviceCoverage(gt, tracks, per_trajectory=True, evaluation=ev, workspace_bytes=need - 1)
+    dev.cov_counts.fill_(-7)
+    dev.traj_stats.fill_(-7)
+    dev.status.fill_(-7)
+    dev.ws.fill_(0x5a)
+    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_INVALID'):
+        dev.launch()
+    torch.cuda.synchronize()
+    assert bool((dev.cov_counts == -7).all()) and bool((dev.traj_stats == -7).all()) and int(dev.status.item()) == -7
+    assert bool((dev.ws == 0x5a).all())
+    # the size it asks for is enough
+    ok = E.DeviceCoverage(gt, tracks, evaluation=ev, workspace_bytes=need)
+    ok.launch()
+    assert ok.results()[0].table['ALL'][2]['traj'] > 0
+
+
+def test_matches_outside_the_ground_truth_are_reported_not_followed(sequence):
+    from waymo_2d_tracking_amd import _lib
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    gt_json, results, _, _ = sequence
+    gt = E.load_ground_truth(gt_json)
+    tracks = [E.load_tracks(results[0])]
+    ev = E.DeviceEvaluation(gt, tracks)
+    ev.launch()
+    ev.wait()
+    ev.hyp_match[0] = int(gt['x'].size)              # one past the last ground-truth row
+    dev = E.DeviceCoverage(gt, tracks, evaluation=ev)
+    dev.launch()
+    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
+        dev.results()
+
+
+def test_cli_prints_the_table_and_the_sweep_ranks_by_mt(tmp_path, capsys):
+    from waymo_2d_tracking_amd import synthetic as syn
+    from waymo_2d_tracking_amd.tracking import evaluate as E
+    dets, gt_json = syn.make_tracking_json(31, n_segments=1, n_frames=16, n_objects=30, cameras=('FRONT', 'FRONT_LEFT'), clutter=0.3)
+    (tmp_path / 'det.json').write_text(json.dumps(dets))
+    (tmp_path / 'gt.json').write_text(json.dumps(gt_json))
+    rows = _track(dets, *SETTINGS[0])
+    (tmp_path / 'tracks.json').write_text(json.dumps(rows))
+    capsys.readouterr()
+    assert E.main(['--annotations', str(tmp_path / 'gt.json'), '--coverage', '--json', str(tmp_path / 'out.json'), str(tmp_path / 'tracks.json')]) == 0
+    printed = capsys.readouterr().out
+    gt = E.load_ground_truth(gt_json)
+    api = E.evaluate_coverage(gt, [E.load_tracks(rows)])[0]
+    path = str(tmp_path / 'tracks.json')
+    assert printed == E.format_table(E.evaluate_tracks(gt, [E.load_tracks(rows)])[0], path) + '\n' + E.format_coverage_table(api, path) + '\n'
+    ref = coverage_ref.evaluate(gt_json, rows)
+    saved = json.loads((tmp_path / 'out.json').read_text())[path]['coverage']
+    for c in (1, 2, 4, 'ALL'):
+        for lv in (1, 2):
+            for name, v in ref['table'][c][lv].items():
+                assert same_number(api.table[c][lv][name], v) and same_number(saved[str(c)]['LEVEL_%d' % lv][name], v)
+    # the sweep on a 2 x 2 grid: the fields are there, and the pick is the reference's
+    assert E.main(['--annotations', str(tmp_path / 'gt.json'), '--sweep', str(tmp_path / 'det.json'), '--score-grid', '0.2,0.7',
+                   '--iou-grid', '0.01,0.3', '--max-age', '2', '--min-hits', '0', '--rank-by', 'mt', '--json', str(tmp_path / 'sweep.json')]) == 0
+    capsys.readouterr()
+    doc = json.loads((tmp_path / 'sweep.json').read_text())
+    assert doc['rank_by'] == 'mt' and len(doc['coverage_tables']) == 4
+    grid = {'score': [0.2, 0.7], 'iou': [0.01, 0.3], 'max_age': [2], 'min_hits': [0]}
+    res = E.sweep(str(tmp_path / 'det.json'), gt, grid, rank_by='mt')
+    refs = [coverage_ref.evaluate(gt_json, _track(dets, 2, 0, [s] * 4, [v] * 4))['table'] for s in grid['score'] for v in grid['iou']]
+    for lv in (1, 2):
+        best = res['best'][lv]
+        assert doc['ranked']['LEVEL_%d' % lv][0]['coverage_counts'] == best['coverage_counts']
+        total = dict((f, 0) for f in coverage_ref.COV_FIELDS)
+        for c in (1, 2, 4):
+            k = max(range(4), key=lambda i: (refs[i][c][lv]['mt'], -i))       # most mt, the first in grid order
+            assert (best['score_threshold'][c - 1], best['iou_threshold'][c - 1]) == (grid['score'][k // 2], grid['iou'][k % 2])
+            for f in total:
+                total[f] += refs[k][c][lv][f]
+        assert best['coverage_counts'] == total
+        assert best['MT'] == total['mt'] / total['traj'] and best['ML'] == total['ml'] / total['traj'] and best['FM'] == total['frag']
+        assert best['PT'] == total['pt'] / total['traj'] and 'MOTA' in best

@@ -32,6 +32,7 @@ UNITS = {
     'mot_eval.hip': ['-ffp-contract=off'],             # CLEAR-MOT evaluation: float64 IoU in the reference's operation order
     'mot_identity.hip': ['-ffp-contract=off'],         # IDF1 / IDP / IDR: the same float64 IoU, trajectory overlap counts and one global assignment
     'mot_hota.hip': ['-ffp-contract=off'],             # HOTA: the same float64 IoU, float64 alignment scores, one assignment per frame for 19 thresholds
+    'mot_coverage.hip': ['-ffp-contract=off'],         # MT / PT / ML / fragmentations: integers only; the flag matches the units whose headers it includes
     'track_refine.hip': ['-ffp-contract=off'],         # track refinement: a fill is va + (vb - va) * (j / n), every operation rounded on its own
     'track_stitch.hip': ['-ffp-contract=off'],         # track stitching: the extrapolation x + ((x - xp) / (e - p)) * n unfused, the same float64 IoU
     'track_smooth.hip': ['-ffp-contract=off'],         # track smoothing: acc + k[d] * (v(f - d) + v(f + d)) and the quotient, every operation rounded on its own

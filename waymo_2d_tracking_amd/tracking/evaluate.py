@@ -1,9 +1,9 @@
 """MOTA / MOTP of tracking results against ground truth, and the threshold sweep that tunes the tracker's flags.
 
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
-        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota]
+        [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota] [--coverage]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--low-score-grid 0.2,0.4 --low-iou-grid 0.3,0.5] [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--rank-by idf1|hota]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--low-score-grid 0.2,0.4 --low-iou-grid 0.3,0.5] [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--coverage] [--rank-by idf1|hota|mt]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
@@ -11,7 +11,9 @@ kernel behind ``wt_mot_eval_host`` (include/waymotrack.h): K results are scored 
 sweep over tracker settings cost seconds.  --identity adds identity preservation (IDF1 / IDP / IDR, Ristani et al. 2016; DESIGN.md
 section 18) through ``wt_mot_identity_host``: per problem one trajectory-by-trajectory overlap matrix and one global assignment.
 --hota adds HOTA / DetA / AssA / LocA (Luiten et al. 2021) through ``wt_mot_hota_host``: one wavefront per
-problem and difficulty level, one assignment per frame scored at 19 localisation thresholds.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
+problem and difficulty level, one assignment per frame scored at 19 localisation thresholds.  --coverage adds what became of every
+ground-truth trajectory (mostly tracked / partially tracked / mostly lost, fragmentations) through
+``wt_mot_coverage_host``, which reads the matches of the CLEAR-MOT kernel where they lie in device memory.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
 """
 import argparse
 import ctypes as C
@@ -124,6 +126,7 @@ def load_ground_truth(path_or_json):
         x=np.ascontiguousarray(box[order, 0]), y=np.ascontiguousarray(box[order, 1]),
         w=np.ascontiguousarray(box[order, 2]), h=np.ascontiguousarray(box[order, 3]),
         category=np.ascontiguousarray(cat[order]), level=np.ascontiguousarray(level[order]), gt_id=gt_id, max_gt_ids=max_ids,
+        object_id=oid[order],
         source_row=order.astype(np.int64), frame_gt_offsets=frame_gt_offsets, stream_frame_offsets=stream_frame_offsets,
         frame_ids=frame_ids.astype(np.int64), frame_values=frame_values, frame_keys=fkeys, stream_keys=keys,
         stream_index=dict((k, i) for i, k in enumerate(keys)))
@@ -836,6 +839,151 @@ class DeviceHota(_DeviceForm):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# trajectory coverage (MT / PT / ML, fragmentations)
+COV_FIELDS = ('traj', 'mt', 'pt', 'ml', 'frag')
+TRAJ_FIELDS = ('len', 'tracked', 'frag', 'idsw')
+
+
+def coverage_row(traj, mt, pt, ml, frag):
+    """Added counts -> the reported row: the counts, MT = mt / traj, ML = ml / traj (NaN without a trajectory) and FM = frag."""
+    traj, mt, pt, ml, frag = int(traj), int(mt), int(pt), int(ml), int(frag)
+    return {'traj': traj, 'mt': mt, 'pt': pt, 'ml': ml, 'frag': frag,
+            'MT': mt / traj if traj else math.nan, 'ML': ml / traj if traj else math.nan, 'FM': frag}
+
+
+class CoverageResult(object):
+    """What became of the ground-truth trajectories under one tracking result (the matching is that of MotResult).
+
+    cov_counts  (n_streams, n_classes, 2, 5) int64: traj, mt, pt, ml, frag for LEVEL_1, LEVEL_2, per stream
+    table       {class id or 'ALL': {1: row, 2: row}}, row = coverage_row() of the added counts ('ALL' = classes 1, 2, 4)
+    ignored_rows   result rows that took no part
+    traj_stats  (with per_trajectory=True) (trajectories, 2, 4) int32: len, tracked, frag, idsw for LEVEL_1, LEVEL_2
+    traj_keys   (with per_trajectory=True) one (stream key, class, object id) per row of traj_stats."""
+
+    def __init__(self, cov_counts, ignored_rows, stream_keys, traj_stats=None, traj_keys=None):
+        self.cov_counts, self.ignored_rows, self.stream_keys = cov_counts, ignored_rows, stream_keys
+        self.traj_stats, self.traj_keys = traj_stats, traj_keys
+        self.table = {}
+        n_classes = cov_counts.shape[1]
+        for c in list(range(1, n_classes + 1)) + ['ALL']:
+            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
+            self.table[c] = {}
+            for li, lv in enumerate(LEVELS):
+                tot = cov_counts[:, [cc - 1 for cc in classes], li, :].reshape(-1, len(COV_FIELDS)).sum(axis=0)
+                self.table[c][lv] = coverage_row(*tot)
+
+    def mt(self, level=2, category='ALL'):
+        return self.table[category][level]['MT']
+
+    def as_json(self):
+        return {'ignored_rows': int(self.ignored_rows),
+                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
+
+
+def _traj_keys(gt, g_traj, g_ntraj):
+    """(stream key, class, object id) of every ground-truth trajectory, in the order of traj_stats."""
+    n_classes = g_ntraj.shape[1]
+    offsets = np.concatenate([[0], np.cumsum(g_ntraj.reshape(-1))]).astype(np.int64)
+    keys = [None] * int(offsets[-1])
+    n = int(gt['frame_gt_offsets'][-1]) if gt['frame_ids'].size else 0
+    frame = np.searchsorted(gt['frame_gt_offsets'], np.arange(n), side='right') - 1
+    stream = np.searchsorted(gt['stream_frame_offsets'], frame, side='right') - 1
+    for r in range(n):
+        c = int(gt['category'][r])
+        if 1 <= c <= n_classes:
+            s = int(stream[r])
+            keys[int(offsets[s * n_classes + c - 1]) + int(g_traj[r])] = (gt['stream_keys'][s], c, gt['object_id'][r])
+    return keys
+
+
+def _coverage_results(gt, packed, cov_counts, traj_stats, keys):
+    results = []
+    set_rows = packed['set_row_offsets']
+    for k in range(len(set_rows) - 1):
+        ignored = int(set_rows[k + 1] - set_rows[k]) - int(packed['frame_hyp_offsets'][k][-1])
+        results.append(CoverageResult(cov_counts[k], ignored, gt['stream_keys'], None if traj_stats is None else traj_stats[k], keys))
+    return results
+
+
+def evaluate_coverage(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_trajectory=False, packed=None):
+    """MT / PT / ML and fragmentations of K tracking results against one ground truth in ONE wt_mot_coverage_host call (the
+    CLEAR-MOT matching of evaluate_tracks, then the coverage kernels on the same stream).  packed: pack_results() of the same
+    arguments, when the caller has it.  Returns a list of K CoverageResult."""
+    lib = _lib.lib()
+    thr = _lib.as_f64(iou_threshold)
+    n_classes = int(thr.size)
+    p = packed if packed is not None else pack_results(gt, tracks_list, n_classes)
+    g_traj, g_ntraj, _, _ = trajectory_indices(gt, p, n_classes)
+    K = len(tracks_list)
+    n_streams = len(gt['stream_keys'])
+    total = int(g_ntraj.sum())
+    cov_counts = np.zeros((K, n_streams, n_classes, 2, len(COV_FIELDS)), np.int64)
+    traj_stats = np.zeros((K, total, 2, len(TRAJ_FIELDS)), np.int32) if per_trajectory else None
+    g_args = _gt_args(gt, gt, gt['gt_id'], _lib.ptr)
+    rc = lib.wt_mot_coverage_host(
+        *(g_args[:8] + [_lib.ptr(g_traj)] + g_args[8:]),               # the trajectory column follows the id column
+        *_hyp_args(K, None, p, p['h_id'], _lib.ptr), _lib.ptr(np.ascontiguousarray(g_ntraj)),
+        C.c_int32(n_classes), _lib.ptr(thr), _lib.ptr(cov_counts), _lib.ptr(traj_stats) if per_trajectory else None)
+    _lib.check(rc, 'wt_mot_coverage_host')
+    return _coverage_results(gt, p, cov_counts, traj_stats, _traj_keys(gt, g_traj, g_ntraj) if per_trajectory else None)
+
+
+class DeviceCoverage(_DeviceForm):
+    """evaluate_coverage with everything resident in HBM: ``launch()`` enqueues the evaluation and one wt_mot_coverage_dev on the
+    current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.  evaluation: a
+    DeviceEvaluation of the same arguments whose launch the caller has already enqueued on this stream (its hyp_match and
+    hyp_switch are read where they lie, and only the coverage kernels are paid for); without one the object owns and launches its
+    own.  workspace_bytes overrides the size of the workspace tensor (a smaller one is refused by the library)."""
+    name = 'wt_mot_coverage_dev'
+
+    def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_trajectory=False, evaluation=None, workspace_bytes=None):
+        self.own = evaluation is None
+        self.ev = DeviceEvaluation(gt, tracks_list, iou_threshold) if self.own else evaluation
+        for name in ('torch', 'lib', 'gt', 'thr', 'n_classes', 'p', 'K', 'n_streams', 'n_hyp', 'device', 'g', 'h'):
+            setattr(self, name, getattr(self.ev, name))             # the packed results and the columns already in HBM
+        torch = self.torch
+        self.status = self.zeros(1, torch.int32)                    # a word of its own: the evaluation's is read as well
+        g_traj, g_ntraj, _, _ = trajectory_indices(gt, self.p, self.n_classes)
+        self.g_traj, self.g_ntraj = g_traj, g_ntraj
+        traj_offsets = np.concatenate([[0], np.cumsum(g_ntraj.reshape(-1))]).astype(np.int64)
+        self.total_traj = int(traj_offsets[-1])
+        self.per_trajectory = per_trajectory
+        self.d_traj, self.d_ntraj, self.d_offsets = self.up(g_traj), self.up(g_ntraj), self.up(traj_offsets)
+        self.cov_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, len(COV_FIELDS)), torch.int64)
+        self.traj_stats = self.zeros((self.K, max(1, self.total_traj), 2, len(TRAJ_FIELDS)), torch.int32) if per_trajectory else None
+        self.lib.wt_mot_coverage_workspace.restype = C.c_size_t
+        self.ws_bytes = int(self.lib.wt_mot_coverage_workspace(C.c_int32(self.K), C.c_int32(self.n_streams), C.c_int32(self.n_classes),
+                                                               C.c_int64(int(gt['x'].size)), C.c_int64(self.total_traj)))
+        if not self.ws_bytes:
+            _lib.check(4, 'wt_mot_coverage_workspace')
+        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
+
+    def launch(self, pass_events=None):
+        """pass_events: four recorded torch.cuda.Event(enable_timing=True), re-recorded around the passes (tools/mot_coverage_bench.py)."""
+        if self.own:
+            self.ev.launch()
+        d, g = self.d, self.g
+        events = None
+        if pass_events is not None:
+            events = (C.c_void_p * 4)(*[e.cuda_event for e in pass_events])
+        rc = self.lib.wt_mot_coverage_dev(
+            C.c_int64(self.gt['x'].size), d(g['category']), d(g['level']), d(self.d_traj),
+            C.c_int64(self.gt['frame_ids'].size), d(g['frame_gt_offsets']), C.c_int32(self.n_streams), d(g['stream_frame_offsets']),
+            C.c_int32(self.n_classes), d(self.d_ntraj), d(self.d_offsets), C.c_int64(self.total_traj),
+            C.c_int32(self.K), C.c_int64(self.n_hyp), d(self.h['set_row_offsets']), d(self.ev.hyp_match), d(self.ev.hyp_switch),
+            d(self.cov_counts), d(self.traj_stats) if self.per_trajectory else None, d(self.status),
+            d(self.ws), C.c_size_t(int(self.ws.numel())), C.c_void_p(self.torch.cuda.current_stream().cuda_stream), events)
+        _lib.check(rc, self.name)
+
+    def results(self):
+        self.ev.wait()
+        self.wait()
+        stats = self.traj_stats.cpu().numpy()[:, :self.total_traj] if self.per_trajectory else None
+        return _coverage_results(self.gt, self.p, self.cov_counts.cpu().numpy(), stats,
+                                 _traj_keys(self.gt, self.g_traj, self.g_ntraj) if self.per_trajectory else None)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # threshold sweep
 def _grid_values(text):
     """'0.5:1.0:0.05' (inclusive range) or '0.0,0.01,0.1' -> list of floats."""
@@ -846,7 +994,7 @@ def _grid_values(text):
     return [float(v) for v in text.split(',')]
 
 
-def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False):
+def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False, coverage=False):
     """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
 
     grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
@@ -878,6 +1026,10 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     ranked setting.  rank_by='hota' (implies hota): per (max_age, min_hits) each class takes the grid point with its own highest class
     HOTA, ties going to grid order; the combined row reports ALL from the added counts and sums and the rows are ranked by its HOTA
     (DESIGN.md section 19).
+    coverage=True scores every setting with evaluate_coverage as well and adds 'MT', 'PT', 'ML' (shares of the trajectories), 'FM'
+    (fragmentations) and 'coverage_counts' to every ranked setting, the per-class picks' counts added class by class.  rank_by='mt'
+    (implies coverage): per (max_age, min_hits) each class takes the grid point with its most mostly-tracked trajectories (traj is
+    the same for every setting), ties going to grid order, and the rows are ranked by ALL MT.
     Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}}."""
     if isinstance(gt, str):
         gt = load_ground_truth(gt)
@@ -966,15 +1118,17 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                         for row, result in zip(rows, passed):
                             settings.append(row)
                             tracks.append(tracks_from_packed(packed, result))
-    if rank_by not in ('mota', 'idf1', 'hota'):
-        raise ValueError("rank_by must be 'mota', 'idf1' or 'hota'")
+    if rank_by not in ('mota', 'idf1', 'hota', 'mt'):
+        raise ValueError("rank_by must be 'mota', 'idf1', 'hota' or 'mt'")
     identity = identity or rank_by == 'idf1'
     hota = hota or rank_by == 'hota'
+    coverage = coverage or rank_by == 'mt'
     packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for both metrics
     results = evaluate_tracks(gt, tracks, iou_threshold, packed=packed_results)
     id_results = evaluate_identity(gt, tracks, iou_threshold, packed=packed_results) if identity else None
     hota_results = evaluate_hota(gt, tracks, iou_threshold, packed=packed_results) if hota else None
-    key = {'idf1': 'IDF1', 'hota': 'HOTA'}.get(rank_by, 'MOTA')
+    cov_results = evaluate_coverage(gt, tracks, iou_threshold, packed=packed_results) if coverage else None
+    key = {'idf1': 'IDF1', 'hota': 'HOTA', 'mt': 'MT'}.get(rank_by, 'MOTA')
     classes = [c for c in ALL_CLASSES if c <= n_classes]
     ranked, best = {}, {}
     per_mm = len(grid['score']) * len(grid['iou']) * len(low_jobs) * len(split_jobs) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
@@ -984,6 +1138,7 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
             pick, total = {}, dict((f, 0) for f in FIELDS)
             id_total = dict((f, 0) for f in ID_FIELDS)
             hota_cnt, hota_sum = np.zeros(2 + N_ALPHAS, np.int64), np.zeros((N_ALPHAS, 4), np.float64)
+            cov_total = dict((f, 0) for f in COV_FIELDS)
             for c in classes:
                 top = None
                 for k in range(g, g + per_mm):
@@ -995,6 +1150,8 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                     if rank_by == 'hota':                             # highest class HOTA, NaN last
                         v = hota_results[k].table[c][lv]['HOTA']
                         errors = -v if v == v else math.inf
+                    if rank_by == 'mt':                               # most mostly-tracked trajectories of the class
+                        errors = -cov_results[k].table[c][lv]['mt']
                     if top is None or errors < top[0]:
                         top = (errors, k)
                 pick[c] = top[1]
@@ -1003,6 +1160,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 if identity:
                     for f in ID_FIELDS:
                         id_total[f] += id_results[top[1]].table[c][lv][f]
+                if coverage:
+                    for f in COV_FIELDS:
+                        cov_total[f] += cov_results[top[1]].table[c][lv][f]
                 if hota:                                              # the pick's class row, added class by class
                     r = hota_results[top[1]].table[c][lv]
                     hota_cnt += np.asarray([r['gt'], r['hyp']] + r['tp'], np.int64)
@@ -1045,6 +1205,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
                 combos[-1].update((n, r[n]) for n in ('HOTA', 'DetA', 'AssA', 'LocA'))
                 combos[-1]['hota_counts'] = {'gt': r['gt'], 'hyp': r['hyp'], 'tp': r['tp'],
                                              'sums': dict((n, hota_sum[:, i].tolist()) for i, n in enumerate(HOTA_SUMS))}
+            if coverage:
+                r = coverage_row(*[cov_total[f] for f in COV_FIELDS])
+                combos[-1].update(MT=r['MT'], PT=r['pt'] / r['traj'] if r['traj'] else math.nan, ML=r['ML'], FM=r['FM'], coverage_counts=cov_total)
         order = sorted(range(len(combos)), key=lambda i: (-(combos[i][key] if combos[i][key] == combos[i][key] else -math.inf), i))
         ranked[lv] = [combos[i] for i in order]
         best[lv] = ranked[lv][0] if ranked[lv] else None
@@ -1053,6 +1216,8 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
         out['id_results'] = id_results
     if hota:
         out['hota_results'] = hota_results
+    if coverage:
+        out['coverage_results'] = cov_results
     return out
 
 
@@ -1117,6 +1282,16 @@ def format_hota_table(result, name=''):
     return '\n'.join(lines)
 
 
+def format_coverage_table(result, name=''):
+    lines = ['%s  coverage' % name,
+             '%-6s %-8s %9s %9s %9s %9s %9s %9s %9s' % ('class', 'level', 'traj', 'mt', 'pt', 'ml', 'MT', 'ML', 'FM')]
+    for c, rows in result.table.items():
+        for lv in LEVELS:
+            r = rows[lv]
+            lines.append('%-6s LEVEL_%d  %9d %9d %9d %9d %9.5f %9.5f %9d' % (c, lv, r['traj'], r['mt'], r['pt'], r['ml'], r['MT'], r['ML'], r['FM']))
+    return '\n'.join(lines)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('tracks', nargs='*', help='tracking JSON files written by tracking/track.py')
@@ -1148,8 +1323,9 @@ def build_parser():
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
     parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
-    parser.add_argument('--rank-by', choices=('mota', 'idf1', 'hota'), default='mota',
-                        help='what the sweep ranks by (idf1 implies --identity, hota implies --hota)')
+    parser.add_argument('--coverage', action='store_true', help='also score trajectory coverage: mostly tracked / partially tracked / mostly lost, fragmentations')
+    parser.add_argument('--rank-by', choices=('mota', 'idf1', 'hota', 'mt'), default='mota',
+                        help='what the sweep ranks by (idf1 implies --identity, hota implies --hota, mt implies --coverage)')
     return parser
 
 
@@ -1170,11 +1346,14 @@ def main(argv=None):
                 'low_score': _grid_values(args.low_score_grid) if args.low_score_grid else [], 'low_iou': _grid_values(args.low_iou_grid)}
         identity = args.identity or args.rank_by == 'idf1'
         hota = args.hota or args.rank_by == 'hota'
-        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota)
+        coverage = args.coverage or args.rank_by == 'mt'
+        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota,
+                    coverage=coverage)
         for lv in LEVELS:
             print('LEVEL_%d: %d settings tracked, best per class combined for each (max_age, min_hits)' % (lv, len(res['settings'])))
             for r in res['ranked'][lv][:args.top]:
                 extra = ('  IDF1 %9.5f' % r['IDF1'] if identity else '') + ('  HOTA %9.5f' % r['HOTA'] if hota else '')
+                extra += '  MT %9.5f  ML %9.5f  FM %d' % (r['MT'], r['ML'], r['FM']) if coverage else ''
                 print('  MOTA %9.5f%s  %s' % (r['MOTA'], extra, flag_line(r)))
         if args.json:
             with open(args.json, 'wt') as fp:
@@ -1186,6 +1365,9 @@ def main(argv=None):
                 if hota:
                     doc['hota_tables'] = [r.as_json() for r in res['hota_results']]
                     doc['rank_by'] = args.rank_by
+                if coverage:
+                    doc['coverage_tables'] = [r.as_json() for r in res['coverage_results']]
+                    doc['rank_by'] = args.rank_by
                 json.dump(doc, fp)
         if res['best'][2] is not None:
             print(flag_line(res['best'][2]))
@@ -1196,8 +1378,11 @@ def main(argv=None):
     results = evaluate_tracks(gt, tracks, args.iou_threshold)
     id_results = evaluate_identity(gt, tracks, args.iou_threshold) if args.identity else [None] * len(results)
     hota_results = evaluate_hota(gt, tracks, args.iou_threshold) if args.hota else [None] * len(results)
-    for path, r, ir, hr in zip(args.tracks, results, id_results, hota_results):
+    cov_results = evaluate_coverage(gt, tracks, args.iou_threshold) if args.coverage else [None] * len(results)
+    for path, r, ir, hr, cr in zip(args.tracks, results, id_results, hota_results, cov_results):
         print(format_table(r, path))
+        if cr is not None:
+            print(format_coverage_table(cr, path))
         if ir is not None:
             print(format_identity_table(ir, path))
         if hr is not None:
@@ -1210,6 +1395,9 @@ def main(argv=None):
         for p, hr in zip(args.tracks, hota_results):
             if hr is not None:
                 doc[p]['hota'] = hr.as_json()['table']
+        for p, cr in zip(args.tracks, cov_results):
+            if cr is not None:
+                doc[p]['coverage'] = cr.as_json()['table']
         with open(args.json, 'wt') as fp:
             json.dump(doc, fp)
     return 0
