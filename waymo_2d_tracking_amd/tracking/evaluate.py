@@ -16,7 +16,10 @@ ground-truth trajectory (mostly tracked / partially tracked / mostly lost, fragm
 ``wt_mot_coverage_host``, which reads the matches of the CLEAR-MOT kernel where they lie in device memory.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
 """
 import argparse
+import collections
 import ctypes as C
+import importlib
+import itertools
 import json
 import math
 
@@ -210,12 +213,32 @@ def _check_unique(gt, tr, order, offsets, h_id, set_index):
                                    % (set_index, tr['object_id'][order[i]], segment_id, int(gt['frame_ids'][f]), camera_id))
 
 
-class MotResult(object):
+class _Scores(object):
+    """What the four result classes share: `table` {class id or 'ALL': {1: row, 2: row}} ('ALL' = classes 1, 2, 4), every row made
+    by the subclass's row(classes, level index) from its per-stream counts, and the JSON form."""
+
+    def fill_table(self, n_classes):
+        self.table = {}
+        for c in list(range(1, n_classes + 1)) + ['ALL']:
+            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
+            self.table[c] = dict((lv, self.row(classes, li)) for li, lv in enumerate(LEVELS))
+
+    def as_json(self):
+        return {'ignored_rows': int(self.ignored_rows),
+                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
+
+
+def _added(counts, classes, li):
+    """Counts (n_streams, n_classes, 2, fields) of `classes` at level index li, added over the streams."""
+    return counts[:, [c - 1 for c in classes], li, :].reshape(-1, counts.shape[-1]).sum(axis=0)
+
+
+class MotResult(_Scores):
     """Scores of one tracking result.
 
     counts    (n_streams, n_classes, 2, 5) int64: gt, tp, fn, fp, idsw for LEVEL_1, LEVEL_2, per stream
     iou_sum   (n_streams, n_classes, 2) float64
-    table     {class id or 'ALL': {1: row, 2: row}}, row = gt, tp, fn, fp, idsw, iou_sum, MOTA, MOTP ('ALL' = classes 1, 2, 4)
+    table     row = gt, tp, fn, fp, idsw, iou_sum, MOTA, MOTP
     ignored_rows   result rows that took no part (frames or streams the ground truth does not have)
     hyp_match / hyp_switch (with per_row=True), one entry per result row in file order: index of the matched annotation in the
         ground-truth file's list (-1 false positive, -2 ignored) and 1 where that match is an identity switch."""
@@ -223,28 +246,20 @@ class MotResult(object):
     def __init__(self, counts, iou_sum, ignored_rows, stream_keys, hyp_match=None, hyp_switch=None):
         self.counts, self.iou_sum, self.ignored_rows, self.stream_keys = counts, iou_sum, ignored_rows, stream_keys
         self.hyp_match, self.hyp_switch = hyp_match, hyp_switch
-        self.table = {}
-        n_classes = counts.shape[1]
-        for c in list(range(1, n_classes + 1)) + ['ALL']:
-            self.table[c] = {}
-            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
-            for li, lv in enumerate(LEVELS):
-                sel = counts[:, [cc - 1 for cc in classes], li, :]
-                row = dict((f, int(sel[..., fi].sum())) for fi, f in enumerate(FIELDS))
-                # the order of this sum is part of the definition: class by class, stream by stream (cumsum adds one by one)
-                parts = np.concatenate([iou_sum[:, cc - 1, li] for cc in classes]) if classes else np.zeros(0)
-                total = float(np.cumsum(parts)[-1]) if parts.size else 0.0
-                row['iou_sum'] = total
-                row['MOTA'] = 1.0 - (row['fn'] + row['fp'] + row['idsw']) / row['gt'] if row['gt'] else math.nan
-                row['MOTP'] = total / row['tp'] if row['tp'] else math.nan
-                self.table[c][lv] = row
+        self.fill_table(counts.shape[1])
+
+    def row(self, classes, li):
+        row = dict(zip(FIELDS, (int(v) for v in _added(self.counts, classes, li))))
+        # the order of this sum is part of the definition: class by class, stream by stream (cumsum adds one by one)
+        parts = np.concatenate([self.iou_sum[:, c - 1, li] for c in classes]) if classes else np.zeros(0)
+        total = float(np.cumsum(parts)[-1]) if parts.size else 0.0
+        row['iou_sum'] = total
+        row['MOTA'] = 1.0 - (row['fn'] + row['fp'] + row['idsw']) / row['gt'] if row['gt'] else math.nan
+        row['MOTP'] = total / row['tp'] if row['tp'] else math.nan
+        return row
 
     def mota(self, level=2, category='ALL'):
         return self.table[category][level]['MOTA']
-
-    def as_json(self):
-        return {'ignored_rows': int(self.ignored_rows),
-                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
 
 
 def pack_results(gt, tracks_list, n_classes):
@@ -291,19 +306,30 @@ def max_frame_boxes(gt, packed, n_classes):
     return best
 
 
-def _results(gt, packed, counts, iou_sum, hyp_match, hyp_switch, per_row):
-    results = []
+def _result_sets(packed):
+    """(k, first row, end row, rows that took no part) of every result in pack_results() output."""
     set_rows = packed['set_row_offsets']
     for k in range(len(set_rows) - 1):
         lo, hi = int(set_rows[k]), int(set_rows[k + 1])
+        yield k, lo, hi, (hi - lo) - int(packed['frame_hyp_offsets'][k][-1])
+
+
+def _file_order(gt, packed, k, m):
+    """Matches of result k's rows in the kernel's order -> the file's row order, ground-truth rows as annotation indices."""
+    match = np.empty(m.shape, np.int64)
+    match[packed['orders'][k]] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
+    return match
+
+
+def _results(gt, packed, counts, iou_sum, hyp_match, hyp_switch, per_row):
+    results = []
+    for k, lo, hi, _ in _result_sets(packed):
         m = hyp_match[lo:hi]
         match = switch = None
-        if per_row:                                  # back to the file's row order, ground-truth rows as annotation indices
-            order = packed['orders'][k]
-            match = np.empty(hi - lo, np.int64)
-            match[order] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
+        if per_row:
+            match = _file_order(gt, packed, k, m)
             switch = np.empty(hi - lo, np.uint8)
-            switch[order] = hyp_switch[lo:hi]
+            switch[packed['orders'][k]] = hyp_switch[lo:hi]
         results.append(MotResult(counts[k], iou_sum[k], int((m == -2).sum()), gt['stream_keys'], match, switch))
     return results
 
@@ -429,6 +455,24 @@ class DeviceEvaluation(_DeviceForm):
                         self.hyp_match.cpu().numpy()[:self.n_hyp], self.hyp_switch.cpu().numpy()[:self.n_hyp], per_row)
 
 
+class _DeviceTrajectoryForm(_DeviceForm):
+    """What DeviceIdentity and DeviceHota share beyond _DeviceForm: the trajectory columns and counts in HBM, their maxima, the
+    offsets of every problem's matrices, and the workspace tensor."""
+
+    def set_up_matrices(self, sizes, workspace, workspace_bytes):
+        """sizes(g_ntraj, h_ntraj): the matrix elements per problem; workspace(total elements) -> bytes, 0 is refused.  Returns the total."""
+        g_traj, self.g_ntraj, h_traj, self.h_ntraj = trajectory_indices(self.gt, self.p, self.n_classes)
+        self.max_g, self.max_h = _max(self.g_ntraj), _max(self.h_ntraj)
+        mat_offsets = np.concatenate([[0], np.cumsum(sizes(self.g_ntraj, self.h_ntraj).reshape(-1))]).astype(np.int64)
+        self.ws_bytes = workspace(int(mat_offsets[-1]))
+        if not self.ws_bytes:
+            _lib.check(4, self.name.replace('_dev', '_workspace'))
+        self.g['traj'], self.h['traj'] = self.up(g_traj), self.up(h_traj)
+        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = self.up(self.g_ntraj), self.up(self.h_ntraj), self.up(mat_offsets)
+        self.ws = self.torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=self.torch.uint8, device=self.device)
+        return int(mat_offsets[-1])
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # identity preservation (IDF1 / IDP / IDR; DESIGN.md section 18)
 ID_FIELDS = ('idtp', 'gt', 'hyp')
@@ -489,48 +533,29 @@ def identity_row(idtp, gt, hyp):
             'idf1': 2 * idtp / (gt + hyp) if gt + hyp else math.nan}
 
 
-class IdentityResult(object):
+class IdentityResult(_Scores):
     """Identity scores of one tracking result.
 
     id_counts   (n_streams, n_classes, 2, 3) int64: idtp, gt, hyp for LEVEL_1, LEVEL_2, per stream
-    table       {class id or 'ALL': {1: row, 2: row}}, row = idtp, idfn, idfp, gt, hyp, idp, idr, idf1 ('ALL' = classes 1, 2, 4,
-                counts summed stream by stream)
+    table       row = idtp, idfn, idfp, gt, hyp, idp, idr, idf1 (counts summed stream by stream)
     ignored_rows   result rows that took no part
     hyp_idmatch (with per_row=True) (rows, 2) int64 in file order, LEVEL_1 then LEVEL_2: index of the identity-matched annotation
                 in the ground-truth file's list, -1 not matched, -2 took no part or left out at that level."""
 
     def __init__(self, id_counts, ignored_rows, stream_keys, hyp_idmatch=None):
         self.id_counts, self.ignored_rows, self.stream_keys, self.hyp_idmatch = id_counts, ignored_rows, stream_keys, hyp_idmatch
-        self.table = {}
-        n_classes = id_counts.shape[1]
-        for c in list(range(1, n_classes + 1)) + ['ALL']:
-            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
-            self.table[c] = {}
-            for li, lv in enumerate(LEVELS):
-                tot = id_counts[:, [cc - 1 for cc in classes], li, :].reshape(-1, 3).sum(axis=0)
-                self.table[c][lv] = identity_row(int(tot[0]), int(tot[1]), int(tot[2]))
+        self.fill_table(id_counts.shape[1])
+
+    def row(self, classes, li):
+        return identity_row(*(int(v) for v in _added(self.id_counts, classes, li)))
 
     def idf1(self, level=2, category='ALL'):
         return self.table[category][level]['idf1']
 
-    def as_json(self):
-        return {'ignored_rows': int(self.ignored_rows),
-                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
-
 
 def _identity_results(gt, packed, id_counts, hyp_idmatch, per_row):
-    results = []
-    set_rows = packed['set_row_offsets']
-    for k in range(len(set_rows) - 1):
-        lo, hi = int(set_rows[k]), int(set_rows[k + 1])
-        match = None
-        if per_row:
-            m = hyp_idmatch[lo:hi]
-            match = np.empty((hi - lo, 2), np.int64)
-            match[packed['orders'][k]] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
-        ignored = (hi - lo) - int(packed['frame_hyp_offsets'][k][-1])
-        results.append(IdentityResult(id_counts[k], ignored, gt['stream_keys'], match))
-    return results
+    return [IdentityResult(id_counts[k], ignored, gt['stream_keys'], _file_order(gt, packed, k, hyp_idmatch[lo:hi]) if per_row else None)
+            for k, lo, hi, ignored in _result_sets(packed)]
 
 
 def _identity_workspace(lib, k, n_streams, n_classes, max_g, max_h, floats):
@@ -539,23 +564,42 @@ def _identity_workspace(lib, k, n_streams, n_classes, max_g, max_h, floats):
                                              C.c_int64(floats)))
 
 
-def _identity_calls(lib, g_ntraj, h_ntraj, limit):
-    """Consecutive result sets per call: as many as fit the workspace limit, at least one."""
-    K, n_streams, n_classes = h_ntraj.shape
-    floats = _matrix_floats(g_ntraj, h_ntraj).reshape(K, -1).sum(axis=1)
-    max_g = int(g_ntraj.max()) if g_ntraj.size else 0
+def _max(a):
+    return int(a.max()) if a.size else 0
+
+
+def _calls(K, need, limit):
+    """Consecutive result sets per call: as many as fit the workspace limit, at least one.  need(k0, k1): the bytes sets k0:k1 ask for
+    (0 = more than the library sizes)."""
     calls, k0 = [], 0
     while k0 < K:
         k1 = k0 + 1
         while k1 < K:
-            max_h = int(h_ntraj[k0:k1 + 1].max()) if h_ntraj[k0:k1 + 1].size else 0
-            need = _identity_workspace(lib, k1 + 1 - k0, n_streams, n_classes, max_g, max_h, int(floats[k0:k1 + 1].sum()))
-            if need == 0 or (limit and need > limit):
+            n = need(k0, k1 + 1)
+            if n == 0 or (limit and n > limit):
                 break
             k1 += 1
         calls.append((k0, k1))
         k0 = k1
     return calls
+
+
+def _identity_calls(lib, g_ntraj, h_ntraj, limit):
+    K, n_streams, n_classes = h_ntraj.shape
+    floats = _matrix_floats(g_ntraj, h_ntraj).reshape(K, -1).sum(axis=1)
+    max_g = _max(g_ntraj)
+    return _calls(K, lambda k0, k1: _identity_workspace(lib, k1 - k0, n_streams, n_classes, max_g, _max(h_ntraj[k0:k1]), int(floats[k0:k1].sum())), limit)
+
+
+def _call_slice(p, h_traj, h_ntraj, k0, k1):
+    """Result sets k0:k1 of pack_results() output as the input of a call of their own: (first row, end row, the columns with
+    offsets from 0, their trajectory column, their trajectory counts)."""
+    set_rows = p['set_row_offsets']
+    lo, hi = int(set_rows[k0]), int(set_rows[k1])
+    h = dict((n, p[n][lo:hi]) for n in _BOX + ('category',))
+    h['set_row_offsets'] = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
+    h['frame_hyp_offsets'] = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
+    return lo, hi, h, h_traj[lo:hi], np.ascontiguousarray(h_ntraj[k0:k1])
 
 
 def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, workspace_limit_bytes=DEFAULT_WORKSPACE_LIMIT,
@@ -571,19 +615,14 @@ def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_
     K = len(tracks_list)
     n_streams = len(gt['stream_keys'])
     id_counts = np.zeros((K, n_streams, n_classes, 2, 3), np.int64)
-    set_rows = p['set_row_offsets']
-    hyp_idmatch = np.full((int(set_rows[-1]), 2), -2, np.int64)
+    hyp_idmatch = np.full((int(p['set_row_offsets'][-1]), 2), -2, np.int64)
     g_ntraj_c = np.ascontiguousarray(g_ntraj)
     for k0, k1 in _identity_calls(lib, g_ntraj, h_ntraj, workspace_limit_bytes):
-        lo, hi = int(set_rows[k0]), int(set_rows[k1])
-        h = dict((n, p[n][lo:hi]) for n in _BOX + ('category',))
-        h['set_row_offsets'] = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
-        h['frame_hyp_offsets'] = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
-        hn = np.ascontiguousarray(h_ntraj[k0:k1])
+        lo, hi, h, ht, hn = _call_slice(p, h_traj, h_ntraj, k0, k1)
         cnt = np.zeros((k1 - k0, n_streams, n_classes, 2, 3), np.int64)
         match = np.full((hi - lo, 2), -2, np.int64)
         rc = lib.wt_mot_identity_host(
-            *_gt_args(gt, gt, g_traj, _lib.ptr), *_hyp_args(k1 - k0, None, h, h_traj[lo:hi], _lib.ptr),
+            *_gt_args(gt, gt, g_traj, _lib.ptr), *_hyp_args(k1 - k0, None, h, ht, _lib.ptr),
             _lib.ptr(g_ntraj_c), _lib.ptr(hn),
             C.c_int32(n_classes), _lib.ptr(thr), C.c_size_t(int(workspace_limit_bytes or 0)), _lib.ptr(cnt),
             _lib.ptr(match) if per_row else None)
@@ -593,7 +632,7 @@ def evaluate_identity(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_
     return _identity_results(gt, p, id_counts, hyp_idmatch, per_row)
 
 
-class DeviceIdentity(_DeviceForm):
+class DeviceIdentity(_DeviceTrajectoryForm):
     """evaluate_identity with everything resident in HBM, beside DeviceEvaluation: ``launch()`` enqueues one wt_mot_identity_dev
     on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.  All K results go into
     one call; workspace_bytes overrides the size of the workspace tensor (a smaller one is refused by the library)."""
@@ -601,22 +640,10 @@ class DeviceIdentity(_DeviceForm):
 
     def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, workspace_bytes=None):
         _DeviceForm.__init__(self, gt, tracks_list, iou_threshold)
-        torch = self.torch
-        g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, self.p, self.n_classes)
-        self.g_ntraj, self.h_ntraj = g_ntraj, h_ntraj
-        self.max_g = int(g_ntraj.max()) if g_ntraj.size else 0
-        self.max_h = int(h_ntraj.max()) if h_ntraj.size else 0
-        floats = _matrix_floats(g_ntraj, h_ntraj).reshape(-1)
-        mat_offsets = np.concatenate([[0], np.cumsum(floats)]).astype(np.int64)
-        self.matrix_floats = int(mat_offsets[-1])
-        self.ws_bytes = _identity_workspace(self.lib, self.K, self.n_streams, self.n_classes, self.max_g, self.max_h, self.matrix_floats)
-        if not self.ws_bytes:
-            _lib.check(4, 'wt_mot_identity_workspace')
-        self.g['traj'], self.h['traj'] = self.up(g_traj), self.up(h_traj)
-        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = self.up(g_ntraj), self.up(h_ntraj), self.up(mat_offsets)
-        self.id_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 3), torch.int64)
-        self.hyp_idmatch = self.zeros((max(1, self.n_hyp), 2), torch.int64)
-        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
+        self.matrix_floats = self.set_up_matrices(_matrix_floats, lambda n: _identity_workspace(
+            self.lib, self.K, self.n_streams, self.n_classes, self.max_g, self.max_h, n), workspace_bytes)
+        self.id_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 3), self.torch.int64)
+        self.hyp_idmatch = self.zeros((max(1, self.n_hyp), 2), self.torch.int64)
 
     def launch(self):
         d = self.d
@@ -686,12 +713,12 @@ def _hota_added(counts, sums, classes, li):
     return cnt, tot
 
 
-class HotaResult(object):
+class HotaResult(_Scores):
     """HOTA scores of one tracking result.
 
     hota_counts (n_streams, n_classes, 2, 21) int64: gt, hyp, tp[19] for LEVEL_1, LEVEL_2, per stream
     hota_sums   (n_streams, n_classes, 2, 19, 4) float64: ass, assre, asspr, loc per threshold alpha_a = (a + 1) / 20
-    table       {class id or 'ALL': {1: row, 2: row}}, row = hota_row() of the added counts ('ALL' = classes 1, 2, 4)
+    table       row = hota_row() of the added counts, plus 'sums'
     ignored_rows   result rows that took no part
     hyp_match   (with per_row=True) (rows, 2) int64 in file order, LEVEL_1 then LEVEL_2: index of the annotation in the ground-truth
                 file's list that the frame's assignment gave the box, -1 unmatched, -2 took no part or removed at that level."""
@@ -699,37 +726,21 @@ class HotaResult(object):
     def __init__(self, hota_counts, hota_sums, ignored_rows, stream_keys, hyp_match=None):
         self.hota_counts, self.hota_sums, self.ignored_rows, self.stream_keys = hota_counts, hota_sums, ignored_rows, stream_keys
         self.hyp_match = hyp_match
-        self.table = {}
-        n_classes = hota_counts.shape[1]
-        for c in list(range(1, n_classes + 1)) + ['ALL']:
-            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
-            self.table[c] = {}
-            for li, lv in enumerate(LEVELS):
-                cnt, tot = _hota_added(hota_counts, hota_sums, classes, li)
-                self.table[c][lv] = hota_row(cnt[0], cnt[1], cnt[2:], tot)
-                self.table[c][lv]['sums'] = dict((n, tot[:, i].tolist()) for i, n in enumerate(HOTA_SUMS))
+        self.fill_table(hota_counts.shape[1])
+
+    def row(self, classes, li):
+        cnt, tot = _hota_added(self.hota_counts, self.hota_sums, classes, li)
+        row = hota_row(cnt[0], cnt[1], cnt[2:], tot)
+        row['sums'] = dict((n, tot[:, i].tolist()) for i, n in enumerate(HOTA_SUMS))
+        return row
 
     def hota(self, level=2, category='ALL'):
         return self.table[category][level]['HOTA']
 
-    def as_json(self):
-        return {'ignored_rows': int(self.ignored_rows),
-                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
-
 
 def _hota_results(gt, packed, hota_counts, hota_sums, hyp_match, per_row):
-    results = []
-    set_rows = packed['set_row_offsets']
-    for k in range(len(set_rows) - 1):
-        lo, hi = int(set_rows[k]), int(set_rows[k + 1])
-        match = None
-        if per_row:
-            m = hyp_match[lo:hi]
-            match = np.empty((hi - lo, 2), np.int64)
-            match[packed['orders'][k]] = np.where(m >= 0, gt['source_row'][np.maximum(m, 0)], m) if gt['source_row'].size else m
-        ignored = (hi - lo) - int(packed['frame_hyp_offsets'][k][-1])
-        results.append(HotaResult(hota_counts[k], hota_sums[k], ignored, gt['stream_keys'], match))
-    return results
+    return [HotaResult(hota_counts[k], hota_sums[k], ignored, gt['stream_keys'], _file_order(gt, packed, k, hyp_match[lo:hi]) if per_row else None)
+            for k, lo, hi, ignored in _result_sets(packed)]
 
 
 def _hota_workspace(lib, k, n_streams, n_classes, max_boxes, max_g, max_h, cells):
@@ -739,23 +750,11 @@ def _hota_workspace(lib, k, n_streams, n_classes, max_boxes, max_g, max_h, cells
 
 
 def _hota_calls(lib, g_ntraj, h_ntraj, max_boxes, limit):
-    """Consecutive result sets per call: as many as fit the workspace limit, at least one.  max_boxes: the bound of the whole
-    input (a smaller per-call bound would only shrink the workspace)."""
+    """max_boxes: the bound of the whole input (a smaller per-call bound would only shrink the workspace)."""
     K, n_streams, n_classes = h_ntraj.shape
     cells = _matrix_cells(g_ntraj, h_ntraj).reshape(K, -1).sum(axis=1)
-    max_g = int(g_ntraj.max()) if g_ntraj.size else 0
-    calls, k0 = [], 0
-    while k0 < K:
-        k1 = k0 + 1
-        while k1 < K:
-            max_h = int(h_ntraj[k0:k1 + 1].max()) if h_ntraj[k0:k1 + 1].size else 0
-            need = _hota_workspace(lib, k1 + 1 - k0, n_streams, n_classes, max_boxes, max_g, max_h, int(cells[k0:k1 + 1].sum()))
-            if need == 0 or (limit and need > limit):
-                break
-            k1 += 1
-        calls.append((k0, k1))
-        k0 = k1
-    return calls
+    max_g = _max(g_ntraj)
+    return _calls(K, lambda k0, k1: _hota_workspace(lib, k1 - k0, n_streams, n_classes, max_boxes, max_g, _max(h_ntraj[k0:k1]), int(cells[k0:k1].sum())), limit)
 
 
 def evaluate_hota(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=False, workspace_limit_bytes=DEFAULT_WORKSPACE_LIMIT,
@@ -772,20 +771,15 @@ def evaluate_hota(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=
     n_streams = len(gt['stream_keys'])
     hota_counts = np.zeros((K, n_streams, n_classes, 2, 2 + N_ALPHAS), np.int64)
     hota_sums = np.zeros((K, n_streams, n_classes, 2, N_ALPHAS, 4), np.float64)
-    set_rows = p['set_row_offsets']
-    hyp_match = np.full((int(set_rows[-1]), 2), -2, np.int64)
+    hyp_match = np.full((int(p['set_row_offsets'][-1]), 2), -2, np.int64)
     g_ntraj_c = np.ascontiguousarray(g_ntraj)
     for k0, k1 in _hota_calls(lib, g_ntraj, h_ntraj, max_frame_boxes(gt, p, n_classes), workspace_limit_bytes):
-        lo, hi = int(set_rows[k0]), int(set_rows[k1])
-        h = dict((n, p[n][lo:hi]) for n in _BOX + ('category',))
-        h['set_row_offsets'] = np.ascontiguousarray(set_rows[k0:k1 + 1] - lo)
-        h['frame_hyp_offsets'] = np.ascontiguousarray(p['frame_hyp_offsets'][k0:k1])
-        hn = np.ascontiguousarray(h_ntraj[k0:k1])
+        lo, hi, h, ht, hn = _call_slice(p, h_traj, h_ntraj, k0, k1)
         cnt = np.zeros((k1 - k0,) + hota_counts.shape[1:], np.int64)
         sums = np.zeros((k1 - k0,) + hota_sums.shape[1:], np.float64)
         match = np.full((hi - lo, 2), -2, np.int64)
         rc = lib.wt_mot_hota_host(
-            *_gt_args(gt, gt, g_traj, _lib.ptr), *_hyp_args(k1 - k0, None, h, h_traj[lo:hi], _lib.ptr),
+            *_gt_args(gt, gt, g_traj, _lib.ptr), *_hyp_args(k1 - k0, None, h, ht, _lib.ptr),
             _lib.ptr(g_ntraj_c), _lib.ptr(hn),
             C.c_int32(n_classes), _lib.ptr(thr), C.c_size_t(int(workspace_limit_bytes or 0)), _lib.ptr(cnt), _lib.ptr(sums),
             _lib.ptr(match) if per_row else None)
@@ -796,7 +790,7 @@ def evaluate_hota(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_row=
     return _hota_results(gt, p, hota_counts, hota_sums, hyp_match, per_row)
 
 
-class DeviceHota(_DeviceForm):
+class DeviceHota(_DeviceTrajectoryForm):
     """evaluate_hota with everything resident in HBM, beside DeviceEvaluation and DeviceIdentity: ``launch()`` enqueues one
     wt_mot_hota_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.  All K
     results go into one call; workspace_bytes overrides the size of the workspace tensor (a smaller one is refused by the library)."""
@@ -804,23 +798,12 @@ class DeviceHota(_DeviceForm):
 
     def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, workspace_bytes=None):
         _DeviceForm.__init__(self, gt, tracks_list, iou_threshold)
-        torch = self.torch
-        g_traj, g_ntraj, h_traj, h_ntraj = trajectory_indices(gt, self.p, self.n_classes)
-        self.g_ntraj, self.h_ntraj = g_ntraj, h_ntraj
         self.max_boxes = max_frame_boxes(gt, self.p, self.n_classes)
-        self.max_g = int(g_ntraj.max()) if g_ntraj.size else 0
-        self.max_h = int(h_ntraj.max()) if h_ntraj.size else 0
-        mat_offsets = np.concatenate([[0], np.cumsum(_matrix_cells(g_ntraj, h_ntraj).reshape(-1))]).astype(np.int64)
-        self.matrix_cells = int(mat_offsets[-1])
-        self.ws_bytes = _hota_workspace(self.lib, self.K, self.n_streams, self.n_classes, self.max_boxes, self.max_g, self.max_h, self.matrix_cells)
-        if not self.ws_bytes:
-            _lib.check(4, 'wt_mot_hota_workspace')
-        self.g['traj'], self.h['traj'] = self.up(g_traj), self.up(h_traj)
-        self.g['ntraj'], self.h['ntraj'], self.mat_offsets = self.up(g_ntraj), self.up(h_ntraj), self.up(mat_offsets)
-        self.hota_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 2 + N_ALPHAS), torch.int64)
-        self.hota_sums = self.zeros((self.K, self.n_streams, self.n_classes, 2, N_ALPHAS, 4), torch.float64)
-        self.hyp_match = self.zeros((max(1, self.n_hyp), 2), torch.int64)
-        self.ws = torch.empty(self.ws_bytes if workspace_bytes is None else int(workspace_bytes), dtype=torch.uint8, device=self.device)
+        self.matrix_cells = self.set_up_matrices(_matrix_cells, lambda n: _hota_workspace(
+            self.lib, self.K, self.n_streams, self.n_classes, self.max_boxes, self.max_g, self.max_h, n), workspace_bytes)
+        self.hota_counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 2 + N_ALPHAS), self.torch.int64)
+        self.hota_sums = self.zeros((self.K, self.n_streams, self.n_classes, 2, N_ALPHAS, 4), self.torch.float64)
+        self.hyp_match = self.zeros((max(1, self.n_hyp), 2), self.torch.int64)
 
     def launch(self):
         d = self.d
@@ -851,11 +834,11 @@ def coverage_row(traj, mt, pt, ml, frag):
             'MT': mt / traj if traj else math.nan, 'ML': ml / traj if traj else math.nan, 'FM': frag}
 
 
-class CoverageResult(object):
+class CoverageResult(_Scores):
     """What became of the ground-truth trajectories under one tracking result (the matching is that of MotResult).
 
     cov_counts  (n_streams, n_classes, 2, 5) int64: traj, mt, pt, ml, frag for LEVEL_1, LEVEL_2, per stream
-    table       {class id or 'ALL': {1: row, 2: row}}, row = coverage_row() of the added counts ('ALL' = classes 1, 2, 4)
+    table       row = coverage_row() of the added counts
     ignored_rows   result rows that took no part
     traj_stats  (with per_trajectory=True) (trajectories, 2, 4) int32: len, tracked, frag, idsw for LEVEL_1, LEVEL_2
     traj_keys   (with per_trajectory=True) one (stream key, class, object id) per row of traj_stats."""
@@ -863,21 +846,13 @@ class CoverageResult(object):
     def __init__(self, cov_counts, ignored_rows, stream_keys, traj_stats=None, traj_keys=None):
         self.cov_counts, self.ignored_rows, self.stream_keys = cov_counts, ignored_rows, stream_keys
         self.traj_stats, self.traj_keys = traj_stats, traj_keys
-        self.table = {}
-        n_classes = cov_counts.shape[1]
-        for c in list(range(1, n_classes + 1)) + ['ALL']:
-            classes = [c] if c != 'ALL' else [x for x in ALL_CLASSES if x <= n_classes]
-            self.table[c] = {}
-            for li, lv in enumerate(LEVELS):
-                tot = cov_counts[:, [cc - 1 for cc in classes], li, :].reshape(-1, len(COV_FIELDS)).sum(axis=0)
-                self.table[c][lv] = coverage_row(*tot)
+        self.fill_table(cov_counts.shape[1])
+
+    def row(self, classes, li):
+        return coverage_row(*_added(self.cov_counts, classes, li))
 
     def mt(self, level=2, category='ALL'):
         return self.table[category][level]['MT']
-
-    def as_json(self):
-        return {'ignored_rows': int(self.ignored_rows),
-                'table': dict((str(c), dict(('LEVEL_%d' % lv, r) for lv, r in rows.items())) for c, rows in self.table.items())}
 
 
 def _traj_keys(gt, g_traj, g_ntraj):
@@ -897,12 +872,8 @@ def _traj_keys(gt, g_traj, g_ntraj):
 
 
 def _coverage_results(gt, packed, cov_counts, traj_stats, keys):
-    results = []
-    set_rows = packed['set_row_offsets']
-    for k in range(len(set_rows) - 1):
-        ignored = int(set_rows[k + 1] - set_rows[k]) - int(packed['frame_hyp_offsets'][k][-1])
-        results.append(CoverageResult(cov_counts[k], ignored, gt['stream_keys'], None if traj_stats is None else traj_stats[k], keys))
-    return results
+    return [CoverageResult(cov_counts[k], ignored, gt['stream_keys'], None if traj_stats is None else traj_stats[k], keys)
+            for k, _, _, ignored in _result_sets(packed)]
 
 
 def evaluate_coverage(gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD, per_trajectory=False, packed=None):
@@ -984,7 +955,94 @@ class DeviceCoverage(_DeviceForm):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# threshold sweep
+# the printed tables: one formatter, one column spec (row key = heading, format) per metric
+_D, _F = '%9d', '%9.5f'
+_MOT_COLUMNS = tuple((k, _D) for k in FIELDS[:4]) + (('idsw', '%7d'), ('MOTA', _F), ('MOTP', _F))
+_ID_COLUMNS = tuple((k, _D) for k in ('idtp', 'idfn', 'idfp')) + tuple((k, _F) for k in ('idf1', 'idp', 'idr'))
+_HOTA_COLUMNS = tuple((k, _F) for k in HOTA_NAMES + ('HOTA(0)', 'LocA(0)'))
+_COV_COLUMNS = tuple((k, _D) for k in ('traj', 'mt', 'pt', 'ml')) + (('MT', _F), ('ML', _F), ('FM', _D))
+
+
+def _format_rows(result, title, columns, heading=str):
+    lines = [title, '%-6s %-8s' % ('class', 'level') + ''.join(' %*s' % (int(f[1]), heading(k)) for k, f in columns)]
+    for c, rows in result.table.items():
+        for lv in LEVELS:
+            lines.append('%-6s LEVEL_%d ' % (c, lv) + ''.join(' ' + f % rows[lv][k] for k, f in columns))
+    return '\n'.join(lines)
+
+
+def format_table(result, name=''):
+    return _format_rows(result, '%s  (ignored rows: %d)' % (name, result.ignored_rows), _MOT_COLUMNS)
+
+
+def format_identity_table(result, name=''):
+    return _format_rows(result, '%s  identity' % name, _ID_COLUMNS, str.upper)
+
+
+def format_hota_table(result, name=''):
+    return _format_rows(result, '%s  HOTA' % name, _HOTA_COLUMNS)
+
+
+def format_coverage_table(result, name=''):
+    return _format_rows(result, '%s  coverage' % name, _COV_COLUMNS)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the metrics, as the sweep's ranking and main() use them
+def _counter(fields):
+    """(start, add) of a total that adds `fields` of class rows."""
+    def add(total, row):
+        for f in fields:
+            total[f] += row[f]
+        return total
+    return (lambda: dict((f, 0) for f in fields)), add
+
+
+def _highest(key):
+    """Class pick: the highest row[key], NaN (nothing on either side) last."""
+    return lambda row: -row[key] if row[key] == row[key] else math.inf
+
+
+def _hota_add(total, r):
+    return [total[0] + np.asarray([r['gt'], r['hyp']] + r['tp'], np.int64), total[1] + np.asarray([r['sums'][n] for n in HOTA_SUMS], np.float64).T]
+
+
+def _hota_finish(total):
+    r = hota_row(total[0][0], total[0][1], total[0][2:], total[1])
+    out = dict((n, r[n]) for n in ('HOTA', 'DetA', 'AssA', 'LocA'))
+    out['hota_counts'] = {'gt': r['gt'], 'hyp': r['hyp'], 'tp': r['tp'], 'sums': dict((n, total[1][:, i].tolist()) for i, n in enumerate(HOTA_SUMS))}
+    return out
+
+
+def _coverage_finish(total):
+    r = coverage_row(*[total[f] for f in COV_FIELDS])
+    return {'MT': r['MT'], 'PT': r['pt'] / r['traj'] if r['traj'] else math.nan, 'ML': r['ML'], 'FM': r['FM'], 'coverage_counts': total}
+
+
+# name: the --rank-by value; option: what switches the metric on (None: always); evaluate: the function, looked up when it is called;
+# results / tables / section: its keys in sweep()'s return value, the sweep's JSON document and a result's JSON document; pick: class
+# row -> what the per-class pick minimises (ties: grid order); start, add, finish: the total of the picks' class rows, added class
+# by class, and the keys it gives the combined row, `key` being the one the rows are ranked by; table, line: the printed forms
+_Metric = collections.namedtuple('_Metric', 'name option evaluate results tables section key pick start add finish table line')
+METRICS = (
+    # gt is the same for every setting: fewest errors = highest MOTA
+    _Metric('mota', None, 'evaluate_tracks', 'results', 'tables', None, 'MOTA', lambda row: row['fn'] + row['fp'] + row['idsw'], *_counter(FIELDS),
+            finish=lambda t: {'MOTA': 1.0 - (t['fn'] + t['fp'] + t['idsw']) / t['gt'] if t['gt'] else math.nan, 'counts': t},
+            table=format_table, line=lambda r: '  MOTA %9.5f' % r['MOTA']),
+    _Metric('idf1', 'identity', 'evaluate_identity', 'id_results', 'identity_tables', 'identity', 'IDF1', _highest('idf1'), *_counter(ID_FIELDS),
+            finish=lambda t: {'IDF1': identity_row(t['idtp'], t['gt'], t['hyp'])['idf1'], 'id_counts': t},
+            table=format_identity_table, line=lambda r: '  IDF1 %9.5f' % r['IDF1']),
+    _Metric('hota', 'hota', 'evaluate_hota', 'hota_results', 'hota_tables', 'hota', 'HOTA', _highest('HOTA'),
+            lambda: [np.zeros(2 + N_ALPHAS, np.int64), np.zeros((N_ALPHAS, 4), np.float64)], _hota_add, _hota_finish,
+            table=format_hota_table, line=lambda r: '  HOTA %9.5f' % r['HOTA']),
+    # traj is the same for every setting: most mostly-tracked trajectories = highest MT
+    _Metric('mt', 'coverage', 'evaluate_coverage', 'coverage_results', 'coverage_tables', 'coverage', 'MT', _highest('mt'), *_counter(COV_FIELDS),
+            finish=_coverage_finish, table=format_coverage_table, line=lambda r: '  MT %9.5f  ML %9.5f  FM %d' % (r['MT'], r['ML'], r['FM'])))
+_PRINT_ORDER = (METRICS[0], METRICS[3], METRICS[1], METRICS[2])       # a result's coverage table follows the matching it reads
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# threshold sweep (DESIGN.md section 15, "Structure of the sweep")
 def _grid_values(text):
     """'0.5:1.0:0.05' (inclusive range) or '0.0,0.01,0.1' -> list of floats."""
     if ':' in text:
@@ -994,50 +1052,204 @@ def _grid_values(text):
     return [float(v) for v in text.split(',')]
 
 
-def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False, coverage=False):
-    """Track `detections_path` under every setting of `grid` and score all results in ONE wt_mot_eval call.
+def _int_values(text):
+    return [int(v) for v in text.split(',')]
 
-    grid: dict with lists 'score' and 'iou' (per-class thresholds of the tracker, the same grid for every class), 'max_age'
-    and 'min_hits', optionally 'split_iou' and the single values 'split_gap' and 'split_motion' (track splitting, tracking/split.py; defaults
-    [0.0], 0, 'linear' = none: every tracked result is split under all split IoUs in one call, before it is stitched; the values are the outermost
-    post-pass axis, and the pass is per trajectory with per-class parameters, so the per-class pick ranges over them too), optionally 'link_gap', 'link_iou' and 'link_motion' (track stitching, tracking/stitch.py; defaults [0], [0.3], 'hold' = none:
-    every tracked result is stitched under all (link_gap, link_iou) pairs in one call, before it is refined; stitching is per class, so the
-    per-class pick ranges over these too), optionally 'dedup_frames', 'dedup_iou' and the single value 'dedup_frac' (suppression of duplicate
-    tracks, tracking/dedup.py; defaults [0], [0.7], 0.5 = none: every stitched result is deduplicated under all (frames, IoU) pairs in one
-    call, before it is refined; the pass is per class, so the per-class pick ranges over these too), and optionally 'gap' and 'min_len' (track refinement, tracking/refine.py; defaults [0] and [1] = none): every
-    tracked result is refined under all (gap, min_len) pairs in one call, the pairs are the innermost axes of `settings`, and the
-    per-class pick ranges over them too - refinement is per trajectory with per-class parameters, so it stays valid.  Optionally
-    'smooth_window', 'smooth_sigma' and 'smooth_kernel' (track smoothing, tracking/smooth.py; defaults [0], [1.0], 'gaussian' = none):
-    all refined results of a tracked result are smoothed under all (window, sigma) pairs in one call, the pairs become the
-    innermost axes, and the per-class pick ranges over them too - the pass is per trajectory with per-class parameters.  Classes are tracked independently (one Sort per class), so a class's counts depend only on its own two
-    thresholds and on (max_age, min_hits): every tracked setting uses ONE (score, iou) grid point for all classes -
-    K = |score| x |iou| x |max_age| x |min_hits| settings - and the best point is read off per class for each
-    (max_age, min_hits); no product over classes is tracked.  Best = highest ALL MOTA at the level; ties go to the setting that
-    comes first in grid order (max_age, min_hits, then per class score, iou).
-    Optionally 'low_score' and 'low_iou' (the tracker's second association, utils.track_packed_byte; defaults [] = off and [0.5]): every
-    (score, iou) point is tracked under all (low_score, low_iou) pairs, a low score above the point's score clamped to it (that point is
-    plain tracking); the pairs are the axes just inside (score, iou), every setting row carries 'low_score' and 'low_iou', and the
-    per-class pick ranges over them too - the second association is per class like the first.
-    identity=True scores every setting with evaluate_identity as well and adds 'IDF1' (with 'id_counts') to every ranked setting.
-    rank_by='idf1' (implies identity): per (max_age, min_hits) each class takes the grid point with its own highest class IDF1, the
-    combined row reports ALL from the summed identity counts and the rows are ranked by it (this is not the
-    argmax of ALL IDF1 over one shared grid point - hyp varies with the setting, and per-class flags can only be tuned per class).
-    hota=True scores every setting with evaluate_hota as well and adds 'HOTA', 'DetA', 'AssA', 'LocA' (with 'hota_counts') to every
-    ranked setting.  rank_by='hota' (implies hota): per (max_age, min_hits) each class takes the grid point with its own highest class
-    HOTA, ties going to grid order; the combined row reports ALL from the added counts and sums and the rows are ranked by its HOTA
-    (DESIGN.md section 19).
-    coverage=True scores every setting with evaluate_coverage as well and adds 'MT', 'PT', 'ML' (shares of the trajectories), 'FM'
-    (fragmentations) and 'coverage_counts' to every ranked setting, the per-class picks' counts added class by class.  rank_by='mt'
-    (implies coverage): per (max_age, min_hits) each class takes the grid point with its most mostly-tracked trajectories (traj is
-    the same for every setting), ties going to grid order, and the rows are ranked by ALL MT.
-    Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}}."""
-    if isinstance(gt, str):
-        gt = load_ground_truth(gt)
-    with open(detections_path) as fp:
+
+class _Axis(object):
+    """One swept parameter of a pass.  grid[key] lists its values (`text`: the default as --KEY-grid takes it); a value becomes
+    job[job] of the stage call and row[row] of the setting, and the combined row lists one value per class under `combined`,
+    which tracking/track.py takes as `flag`.  switch: the pass is live when the values differ from the default.  A class that is
+    not evaluated gets, in the combined row, the default (off) value of a switch and the first grid value of another axis - or a
+    copy of the combined row's `rest` list."""
+
+    def __init__(self, key, text, cast, job, flag, help, row=None, combined=None, switch=True, rest=None):
+        self.key, self.text, self.cast, self.job, self.flag, self.help, self.switch, self.rest = key, text, cast, job, flag, help, switch, rest
+        self.row = row or key
+        self.combined = combined or self.row
+        self.default = self.parse(text)
+
+    def parse(self, text):
+        if not text and not self.text:                # an axis that is empty by default
+            return []
+        return _int_values(text) if self.cast is int else _grid_values(text)
+
+    def join(self, values):
+        return ','.join('%d' % v if self.cast is int else repr(float(v)) for v in values)
+
+
+class _Single(object):
+    """One parameter of a pass that is not swept: grid[key] (one value) goes into every job as job[job] and into the combined
+    row under its key; tracking/track.py takes it as --KEY, written when it differs from the default (always: in any case)."""
+
+    def __init__(self, key, default, cast, job, fmt, help, choices=None, always=False):
+        self.key, self.default, self.cast, self.job, self.fmt, self.help, self.choices, self.always = key, default, cast, job, fmt, help, choices, always
+        self.flag = '--' + key.replace('_', '-')
+
+
+class _Pass(object):
+    """One entry of the table of passes.  stage: the function of tracking/<name>.py that runs it - module and function are looked
+    up when a live pass runs, not before; indexed: its jobs carry 'result', the index of their input among the results so far."""
+
+    def __init__(self, name, axes, singles=(), stage=None, indexed=True):
+        self.name, self.axes, self.singles, self.stage, self.indexed = name, axes, singles, stage, indexed
+
+    def run(self, packed, outs, jobs, n_classes):
+        """Every result of `outs` under every job in ONE call of the stage; the outputs are result-major, job-minor."""
+        if self.indexed:
+            jobs = [dict(job, result=k) for k in range(len(outs)) for job in jobs]
+        return getattr(importlib.import_module('.' + self.name, __package__), self.stage)(packed, outs, jobs, n_classes)
+
+
+# the tracker's second association (utils.track_packed_byte): its points are tracked, the axes just inside (score, iou)
+SECOND = _Pass('second', (
+    _Axis('low_score', '', float, 'low_score', '--low-score-threshold', 'second association of the tracker: detections from this score on may continue an unmatched track '
+          '(tracking/track.py --low-score-threshold; a value above the point\'s score is clamped to it; empty = off)',
+          combined='low_score_threshold', rest='score_threshold'),   # classes that are not evaluated have nothing between low and high
+    _Axis('low_iou', '0.5', float, 'low_iou', '--low-iou-threshold', 'second association: lowest IoU of a low-score detection and its track; read when --low-score-grid is set',
+          combined='low_iou_threshold', switch=False)))
+# the post-passes in the order tracking/track.py chains them: outermost axes first
+PASSES = (
+    _Pass('split', (
+        _Axis('split_iou', '0', float, 'split_iou', '--split-iou', 'track splitting: a track is cut where the extrapolated boxes overlap by less than this IoU (tracking/split.py)'),), (
+        _Single('split_gap', 0, int, 'split_gap', '%d', 'track splitting: a track is cut where more than this many frames lie between two boxes; read when --split-iou-grid is set'),
+        _Single('split_motion', 'linear', str, 'motion', '%s', 'track splitting: how a box is extrapolated', choices=('linear', 'hold'))),
+        stage='split_tracks', indexed=False),
+    _Pass('stitch', (
+        _Axis('link_gap', '0', int, 'max_link', '--link-gap', 'track stitching: tracks are linked across up to this many frames (tracking/stitch.py)'),
+        _Axis('link_iou', '0.3', float, 'link_iou', '--link-iou', 'track stitching: lowest IoU of the extrapolated and the new box; read when --link-gap-grid is set', switch=False)), (
+        _Single('link_motion', 'hold', str, 'motion', '%s', 'track stitching: how an ended track is extrapolated', choices=('hold', 'linear')),),
+        stage='stitch_tracks', indexed=False),
+    _Pass('dedup', (
+        _Axis('dedup_frames', '0', int, 'min_frames', '--dedup-frames', 'track deduplication: a track is dropped when a stronger one overlaps it in this many frames (tracking/dedup.py)'),
+        _Axis('dedup_iou', '0.7', float, 'dup_iou', '--dedup-iou', 'track deduplication: lowest IoU of the two boxes that counts; read when --dedup-frames-grid is set', switch=False)), (
+        _Single('dedup_frac', 0.5, float, 'dup_frac', '%r', 'track deduplication: lowest share of the shorter track\'s frames that must count', always=True),),
+        stage='dedup_tracks'),
+    _Pass('refine', (
+        _Axis('gap', '0', int, 'max_gap', '--interpolate-gap', 'track refinement: gaps of up to this many frames are interpolated (tracking/refine.py)', row='interp_gap'),
+        _Axis('min_len', '1', int, 'min_len', '--min-track-len', 'track refinement: tracks observed in fewer frames are dropped')),
+        stage='refine_tracks'),
+    _Pass('smooth', (
+        _Axis('smooth_window', '0', int, 'window', '--smooth-window', 'track smoothing: boxes are averaged over up to this many frames to either side (tracking/smooth.py)'),
+        _Axis('smooth_sigma', '1.0', float, 'sigma', '--smooth-sigma', 'track smoothing: width of the gaussian weights; read when --smooth-window-grid is set', switch=False)), (
+        _Single('smooth_kernel', 'gaussian', str, 'kernel', '%s', 'track smoothing: the weights over the window', choices=('gaussian', 'box')),),
+        stage='smooth_tracks'))
+# refinement was the sweep's first pass: the keys of a ranked row and the command line's help list it before the others
+_KEY_ORDER = (SECOND, PASSES[3]) + PASSES[:3] + PASSES[4:]
+
+
+class _Plan(object):
+    """A pass under one grid: values (one list per axis), singles {key: value}, on, and points - one (job, keys of the setting row)
+    per combination of the values, first axis outermost.  The one empty point of a pass that is off leaves results and rows alone."""
+
+    def __init__(self, p, grid):
+        self.values = [[a.cast(v) for v in grid.get(a.key, a.default)] for a in p.axes]
+        self.singles = dict((s.key, s.cast(grid.get(s.key, s.default))) for s in p.singles)
+        self.on = any(v != a.default for a, v in zip(p.axes, self.values) if a.switch)
+        fixed = [(s.job, self.singles[s.key]) for s in p.singles]
+        self.points = [({}, {})]
+        if self.on:
+            self.points = [(dict([(a.job, v) for a, v in zip(p.axes, point)] + fixed), dict((a.row, v) for a, v in zip(p.axes, point)))
+                           for point in itertools.product(*self.values)]
+        self.jobs = [job for job, _ in self.points]
+
+
+def _tracked_points(grid, second):
+    """The tracker's runs in grid order - max_age, min_hits, score, iou, then the second association's points: (the row the run's
+    settings begin with, the tracker's arguments).  A low score above the point's score is clamped to it: that point is plain tracking."""
+    for max_age, min_hits, score, iou, low in itertools.product(grid['max_age'], grid['min_hits'], grid['score'], grid['iou'], second.jobs):
+        row = {'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)}
+        if second.on:
+            low = (min(low['low_score'], float(score)), low['low_iou'])
+            row.update(low_score=low[0], low_iou=low[1])
+        yield row, (max_age, min_hits, score, iou) + (low if second.on else ())
+
+
+def sweep_settings(grid):
+    """Enumerate: (settings, plans).  One row per setting - the tracker's axes outermost, then the live passes in chain order, a
+    pass's first axis outside its second - and {pass name: _Plan}."""
+    plans = dict((p.name, _Plan(p, grid)) for p in (SECOND,) + PASSES)
+    settings = []
+    for row, _ in _tracked_points(grid, plans['second']):
+        rows = [row]
+        for p in PASSES:
+            rows = [dict(row, **keys) for row in rows for _, keys in plans[p.name].points]
+        settings += rows
+    return settings, plans
+
+
+def run_settings(packed, grid, plans, n_classes):
+    """Run: the tracks of every setting, in the order of sweep_settings().  One tracker call per tracked point; the first pass of
+    the chain fans its result out in one call; then every output goes through the other live passes ON ITS OWN, a pass taking all
+    results so far times all of its jobs in one call - a stage's workspace grows with jobs x rows in the call."""
+    first, others = PASSES[0], [p for p in PASSES[1:] if plans[p.name].on]
+    tracks = []
+    for _, (max_age, min_hits, score, iou, *low) in _tracked_points(grid, plans['second']):
+        if low:
+            out, _ = T.track_packed_byte(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes, [low[0]] * n_classes, [low[1]] * n_classes)
+        else:
+            out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
+        for out in first.run(packed, [out], plans[first.name].jobs, n_classes) if plans[first.name].on else [out]:
+            results = [out]
+            for p in others:
+                results = p.run(packed, results, plans[p.name].jobs, n_classes)
+            tracks += [tracks_from_packed(packed, result) for result in results]
+    return tracks
+
+
+def _class_columns(p, plan, row, settings, pick, n_classes):
+    """The keys a live pass adds to a combined row: per axis one value per class, the pick's where the class is evaluated."""
+    columns = {}
+    for a, values in zip(p.axes, plan.values):
+        column = list(row[a.rest]) if a.rest else [a.default[0] if a.switch else values[0]] * n_classes
+        for c, k in pick.items():
+            column[c - 1] = settings[k][a.row]
+        columns[a.combined] = column
+    columns.update(plan.singles)
+    return columns
+
+
+def rank_settings(settings, plans, scored, rank_by, group, n_classes):
+    """Rank: pure host code.  scored: {metric name: one result per setting} of the live metrics; group: the settings of one
+    (max_age, min_hits), which are consecutive.  Per group and level every evaluated class takes the setting that is best for it
+    under the metric `rank_by` (METRICS: pick), ties going to grid order; the combined row lists the picks' parameters per class
+    and every live metric over the picks' class rows, and the rows are ranked by rank_by's key, NaN last, ties in grid order.
+    Returns (ranked {level: rows}, best {level: row or None})."""
+    by = next(m for m in METRICS if m.name == rank_by)
+    live = [m for m in METRICS if m.name in scored]
+    classes = [c for c in ALL_CLASSES if c <= n_classes]
+    ranked, best = {}, {}
+    for lv in LEVELS:
+        combos = []
+        for g in range(0, len(settings), group):
+            pick = dict((c, min(range(g, g + group), key=lambda k: by.pick(scored[by.name][k].table[c][lv]))) for c in classes)
+            totals = dict((m.name, m.start()) for m in live)
+            score_thr, iou_thr = [1.0] * n_classes, [1.0] * n_classes      # classes that are not evaluated are not tracked
+            for c, k in pick.items():
+                score_thr[c - 1], iou_thr[c - 1] = settings[k]['score'], settings[k]['iou']
+                for m in live:
+                    totals[m.name] = m.add(totals[m.name], scored[m.name][k].table[c][lv])
+            row = {'max_age': settings[g]['max_age'], 'min_hits': settings[g]['min_hits'], 'score_threshold': score_thr, 'iou_threshold': iou_thr}
+            row.update(live[0].finish(totals[live[0].name]))
+            for p in _KEY_ORDER:
+                if plans[p.name].on:
+                    row.update(_class_columns(p, plans[p.name], row, settings, pick, n_classes))
+            for m in live[1:]:
+                row.update(m.finish(totals[m.name]))
+            combos.append(row)
+        order = sorted(range(len(combos)), key=lambda i: (-(combos[i][by.key] if combos[i][by.key] == combos[i][by.key] else -math.inf), i))
+        ranked[lv] = [combos[i] for i in order]
+        best[lv] = ranked[lv][0] if ranked[lv] else None
+    return ranked, best
+
+
+def _detections(path):
+    """utils.read_data_file without the score filter: the tracker applies it per setting."""
+    with open(path) as fp:
         raw = json.load(fp)
     if 'annotations' in raw:
         raw = raw['annotations']
-    entries = {}                                     # read_data_file without the score filter: the kernel applies it per setting
+    entries = {}
     for entry in raw:
         segment_id, frame_id, camera_id = _split(entry['image_id'])
         bucket = entries.setdefault(segment_id, {}).setdefault(camera_id, {}).setdefault(frame_id, [])
@@ -1045,179 +1257,39 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
         if bbox[2] < 1 or bbox[3] < 1:
             continue
         bucket.append({'bbox': bbox, 'score': entry['score'] if 'score' in entry else 1.0, 'category_id': entry['category_id']})
-    packed = T.pack_streams(entries)
-    settings, tracks = [], []
-    gaps, lens = [int(v) for v in grid.get('gap', [0])], [int(v) for v in grid.get('min_len', [1])]
-    refining = gaps != [0] or lens != [1]           # the two innermost axes: one tracked result refined under every (gap, length)
-    jobs = [{'max_gap': g, 'min_len': n} for g in gaps for n in lens]
-    link_gaps, link_ious = [int(v) for v in grid.get('link_gap', [0])], [float(v) for v in grid.get('link_iou', [0.3])]
-    stitching = link_gaps != [0]                    # the two axes outside them: one tracked result stitched under every (link gap, link IoU)
-    link_motion = grid.get('link_motion', 'hold')
-    link_jobs = [{'max_link': g, 'link_iou': v, 'motion': link_motion} for g in link_gaps for v in link_ious] if stitching else [None]
-    dedup_frames, dedup_ious = [int(v) for v in grid.get('dedup_frames', [0])], [float(v) for v in grid.get('dedup_iou', [0.7])]
-    deduping = dedup_frames != [0]                  # between them: every stitched result deduplicated under every (frames, IoU)
-    dedup_frac = float(grid.get('dedup_frac', 0.5))
-    dedup_jobs = [{'min_frames': f, 'dup_iou': v, 'dup_frac': dedup_frac} for f in dedup_frames for v in dedup_ious] if deduping else [None]
-    smooth_windows, smooth_sigmas = [int(v) for v in grid.get('smooth_window', [0])], [float(v) for v in grid.get('smooth_sigma', [1.0])]
-    smoothing = smooth_windows != [0]               # the innermost axes: every refined result smoothed under every (window, sigma)
-    smooth_kernel = grid.get('smooth_kernel', 'gaussian')
-    smooth_jobs = [{'window': w, 'sigma': v, 'kernel': smooth_kernel} for w in smooth_windows for v in smooth_sigmas] if smoothing else [None]
-    split_ious = [float(v) for v in grid.get('split_iou', [0.0])]
-    splitting = split_ious != [0.0]                 # the outermost post-pass axis: one tracked result split under every split IoU
-    split_gap, split_motion = int(grid.get('split_gap', 0)), grid.get('split_motion', 'linear')
-    split_jobs = [{'split_iou': v, 'split_gap': split_gap, 'motion': split_motion} for v in split_ious] if splitting else [None]
-    low_scores, low_ious = [float(v) for v in grid.get('low_score', [])], [float(v) for v in grid.get('low_iou', [0.5])]
-    second = bool(low_scores)                       # the axes just inside (score, iou): the tracker's second association (utils.track_packed_byte)
-    low_jobs = [(s, v) for s in low_scores for v in low_ious] if second else [None]
-    for max_age in grid['max_age']:
-        for min_hits in grid['min_hits']:
-            for score in grid['score']:
-                for iou, low_job in ((v, j) for v in grid['iou'] for j in low_jobs):
-                    base = {'max_age': int(max_age), 'min_hits': int(min_hits), 'score': float(score), 'iou': float(iou)}
-                    if second:                       # a low score above the point's high score is clamped to it: that point is plain tracking
-                        low = min(low_job[0], float(score))
-                        out, _ = T.track_packed_byte(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes,
-                                                     [low] * n_classes, [low_job[1]] * n_classes)
-                        base.update(low_score=low, low_iou=low_job[1])
-                    else:
-                        out, _ = T.track_packed(packed, [iou] * n_classes, max_age, min_hits, [score] * n_classes)
-                    tracked, tracked_base = [out], base
-                    if splitting:                    # the tracked result under every split IoU, in one call, before anything is linked
-                        from .split import split_tracks
-                        tracked = split_tracks(packed, [out], split_jobs, n_classes)
-                    for out, split in zip(tracked, split_jobs):
-                        base = dict(tracked_base, split_iou=split['split_iou']) if splitting else tracked_base
-                        linked = [out]
-                        if stitching:
-                            from .stitch import stitch_tracks
-                            linked = stitch_tracks(packed, [out], link_jobs, n_classes)
-                        link_rows = [dict(base, link_gap=link['max_link'], link_iou=link['link_iou']) if stitching else base for link in link_jobs]
-                        if deduping:                     # every stitched result under every (frames, IoU), in one call
-                            from .dedup import dedup_tracks
-                            every = [dict(job, result=k) for k in range(len(linked)) for job in dedup_jobs]
-                            link_rows = [dict(row, dedup_frames=job['min_frames'], dedup_iou=job['dup_iou']) for row in link_rows for job in dedup_jobs]
-                            linked = dedup_tracks(packed, linked, every, n_classes)
-                        if refining:                     # every stitched result under every (gap, length), in one call
-                            from .refine import refine_tracks
-                            every = [dict(job, result=k) for k in range(len(linked)) for job in jobs]
-                            refined = refine_tracks(packed, linked, every, n_classes)
-                        rows, passed = [], []
-                        for k, row in enumerate(link_rows):
-                            if not refining:
-                                rows.append(row)
-                                passed.append(linked[k])
-                                continue
-                            for n, job in enumerate(jobs):
-                                rows.append(dict(row, interp_gap=job['max_gap'], min_len=job['min_len']))
-                                passed.append(refined[k * len(jobs) + n])
-                        if smoothing:                    # every result so far under every (window, sigma), in one call
-                            from .smooth import smooth_tracks
-                            every = [dict(job, result=k) for k in range(len(passed)) for job in smooth_jobs]
-                            rows = [dict(row, smooth_window=job['window'], smooth_sigma=job['sigma']) for row in rows for job in smooth_jobs]
-                            passed = smooth_tracks(packed, passed, every, n_classes)
-                        for row, result in zip(rows, passed):
-                            settings.append(row)
-                            tracks.append(tracks_from_packed(packed, result))
-    if rank_by not in ('mota', 'idf1', 'hota', 'mt'):
+    return entries
+
+
+def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False, coverage=False):
+    """Track `detections_path` under every setting of `grid`, score all results in ONE call per metric and rank the settings.
+
+    grid: lists 'score' and 'iou' (the tracker's thresholds, one grid point for all classes), 'max_age' and 'min_hits', and
+    optionally the keys of SECOND and PASSES: per axis a list, per single parameter one value; the defaults switch a pass off, and
+    its module is then not imported and the setting rows carry none of its keys.  The work is sweep_settings() (enumerate),
+    run_settings() (run) and rank_settings() (rank); their docstrings and DESIGN.md section 15 have the order of the settings, the
+    call structure and the ranking.  Classes are tracked and post-processed independently, so a class's counts depend only on its
+    own parameters and on (max_age, min_hits), which the tracker shares: the grid is tracked with ONE point for all classes, and
+    the best point is read off per class for each (max_age, min_hits); no product over classes is tracked.
+    MOTA is always scored; identity / hota / coverage (and the rank_by that needs them: 'idf1', 'hota', 'mt') add their metric's
+    keys to every ranked row (METRICS).  Ranking by anything but 'mota' is not the argmax of the ALL score over one shared grid
+    point: per-class flags can only be tuned per class (DESIGN.md sections 18, 19 and 27).
+    Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}} and, per further
+    metric, its results under 'id_results', 'hota_results', 'coverage_results'."""
+    if rank_by not in [m.name for m in METRICS]:
         raise ValueError("rank_by must be 'mota', 'idf1', 'hota' or 'mt'")
-    identity = identity or rank_by == 'idf1'
-    hota = hota or rank_by == 'hota'
-    coverage = coverage or rank_by == 'mt'
-    packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for both metrics
-    results = evaluate_tracks(gt, tracks, iou_threshold, packed=packed_results)
-    id_results = evaluate_identity(gt, tracks, iou_threshold, packed=packed_results) if identity else None
-    hota_results = evaluate_hota(gt, tracks, iou_threshold, packed=packed_results) if hota else None
-    cov_results = evaluate_coverage(gt, tracks, iou_threshold, packed=packed_results) if coverage else None
-    key = {'idf1': 'IDF1', 'hota': 'HOTA', 'mt': 'MT'}.get(rank_by, 'MOTA')
-    classes = [c for c in ALL_CLASSES if c <= n_classes]
-    ranked, best = {}, {}
-    per_mm = len(grid['score']) * len(grid['iou']) * len(low_jobs) * len(split_jobs) * len(link_jobs) * len(dedup_jobs) * len(jobs) * len(smooth_jobs)
-    for lv in LEVELS:
-        combos = []
-        for g in range(0, len(settings), per_mm):    # one (max_age, min_hits)
-            pick, total = {}, dict((f, 0) for f in FIELDS)
-            id_total = dict((f, 0) for f in ID_FIELDS)
-            hota_cnt, hota_sum = np.zeros(2 + N_ALPHAS, np.int64), np.zeros((N_ALPHAS, 4), np.float64)
-            cov_total = dict((f, 0) for f in COV_FIELDS)
-            for c in classes:
-                top = None
-                for k in range(g, g + per_mm):
-                    row = results[k].table[c][lv]
-                    errors = row['fn'] + row['fp'] + row['idsw']       # gt is the same for every setting: fewest errors = highest MOTA
-                    if rank_by == 'idf1':                             # highest class IDF1 (NaN = nothing on either side: last)
-                        v = id_results[k].table[c][lv]['idf1']
-                        errors = -v if v == v else math.inf
-                    if rank_by == 'hota':                             # highest class HOTA, NaN last
-                        v = hota_results[k].table[c][lv]['HOTA']
-                        errors = -v if v == v else math.inf
-                    if rank_by == 'mt':                               # most mostly-tracked trajectories of the class
-                        errors = -cov_results[k].table[c][lv]['mt']
-                    if top is None or errors < top[0]:
-                        top = (errors, k)
-                pick[c] = top[1]
-                for f in FIELDS:
-                    total[f] += results[top[1]].table[c][lv][f]
-                if identity:
-                    for f in ID_FIELDS:
-                        id_total[f] += id_results[top[1]].table[c][lv][f]
-                if coverage:
-                    for f in COV_FIELDS:
-                        cov_total[f] += cov_results[top[1]].table[c][lv][f]
-                if hota:                                              # the pick's class row, added class by class
-                    r = hota_results[top[1]].table[c][lv]
-                    hota_cnt += np.asarray([r['gt'], r['hyp']] + r['tp'], np.int64)
-                    hota_sum = hota_sum + np.asarray([r['sums'][n] for n in HOTA_SUMS], np.float64).T
-            mota = 1.0 - (total['fn'] + total['fp'] + total['idsw']) / total['gt'] if total['gt'] else math.nan
-            score_thr, iou_thr = [1.0] * n_classes, [1.0] * n_classes      # classes that are not evaluated are not tracked
-            for c in classes:
-                score_thr[c - 1], iou_thr[c - 1] = settings[pick[c]]['score'], settings[pick[c]]['iou']
-            combos.append({'max_age': settings[g]['max_age'], 'min_hits': settings[g]['min_hits'], 'score_threshold': score_thr,
-                           'iou_threshold': iou_thr, 'MOTA': mota, 'counts': total})
-            if second:                                                # classes that are not evaluated have nothing between low and high
-                combos[-1]['low_score_threshold'], combos[-1]['low_iou_threshold'] = list(score_thr), [low_ious[0]] * n_classes
-                for c in classes:
-                    combos[-1]['low_score_threshold'][c - 1], combos[-1]['low_iou_threshold'][c - 1] = settings[pick[c]]['low_score'], settings[pick[c]]['low_iou']
-            if refining:                                              # classes that are not evaluated are not refined either
-                combos[-1]['interp_gap'], combos[-1]['min_len'] = [0] * n_classes, [1] * n_classes
-                for c in classes:
-                    combos[-1]['interp_gap'][c - 1], combos[-1]['min_len'][c - 1] = settings[pick[c]]['interp_gap'], settings[pick[c]]['min_len']
-            if splitting:                                             # classes that are not evaluated are not split either
-                combos[-1]['split_iou'], combos[-1]['split_gap'], combos[-1]['split_motion'] = [0.0] * n_classes, split_gap, split_motion
-                for c in classes:
-                    combos[-1]['split_iou'][c - 1] = settings[pick[c]]['split_iou']
-            if stitching:                                             # classes that are not evaluated are not stitched either
-                combos[-1]['link_gap'], combos[-1]['link_iou'], combos[-1]['link_motion'] = [0] * n_classes, [link_ious[0]] * n_classes, link_motion
-                for c in classes:
-                    combos[-1]['link_gap'][c - 1], combos[-1]['link_iou'][c - 1] = settings[pick[c]]['link_gap'], settings[pick[c]]['link_iou']
-            if deduping:                                              # classes that are not evaluated are not deduplicated either
-                combos[-1]['dedup_frames'], combos[-1]['dedup_iou'], combos[-1]['dedup_frac'] = [0] * n_classes, [dedup_ious[0]] * n_classes, dedup_frac
-                for c in classes:
-                    combos[-1]['dedup_frames'][c - 1], combos[-1]['dedup_iou'][c - 1] = settings[pick[c]]['dedup_frames'], settings[pick[c]]['dedup_iou']
-            if smoothing:                                             # classes that are not evaluated are not smoothed either
-                combos[-1]['smooth_window'], combos[-1]['smooth_sigma'], combos[-1]['smooth_kernel'] = [0] * n_classes, [smooth_sigmas[0]] * n_classes, smooth_kernel
-                for c in classes:
-                    combos[-1]['smooth_window'][c - 1], combos[-1]['smooth_sigma'][c - 1] = settings[pick[c]]['smooth_window'], settings[pick[c]]['smooth_sigma']
-            if identity:
-                combos[-1]['IDF1'] = identity_row(id_total['idtp'], id_total['gt'], id_total['hyp'])['idf1']
-                combos[-1]['id_counts'] = id_total
-            if hota:
-                r = hota_row(hota_cnt[0], hota_cnt[1], hota_cnt[2:], hota_sum)
-                combos[-1].update((n, r[n]) for n in ('HOTA', 'DetA', 'AssA', 'LocA'))
-                combos[-1]['hota_counts'] = {'gt': r['gt'], 'hyp': r['hyp'], 'tp': r['tp'],
-                                             'sums': dict((n, hota_sum[:, i].tolist()) for i, n in enumerate(HOTA_SUMS))}
-            if coverage:
-                r = coverage_row(*[cov_total[f] for f in COV_FIELDS])
-                combos[-1].update(MT=r['MT'], PT=r['pt'] / r['traj'] if r['traj'] else math.nan, ML=r['ML'], FM=r['FM'], coverage_counts=cov_total)
-        order = sorted(range(len(combos)), key=lambda i: (-(combos[i][key] if combos[i][key] == combos[i][key] else -math.inf), i))
-        ranked[lv] = [combos[i] for i in order]
-        best[lv] = ranked[lv][0] if ranked[lv] else None
-    out = {'settings': settings, 'results': results, 'ranked': ranked, 'best': best}
-    if identity:
-        out['id_results'] = id_results
-    if hota:
-        out['hota_results'] = hota_results
-    if coverage:
-        out['coverage_results'] = cov_results
+    if isinstance(gt, str):
+        gt = load_ground_truth(gt)
+    packed = T.pack_streams(_detections(detections_path))
+    settings, plans = sweep_settings(grid)
+    tracks = run_settings(packed, grid, plans, n_classes)
+    asked = {'identity': identity, 'hota': hota, 'coverage': coverage}
+    live = [m for m in METRICS if m.option is None or asked[m.option] or rank_by == m.name]
+    packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for all metrics
+    scored = dict((m.name, globals()[m.evaluate](gt, tracks, iou_threshold, packed=packed_results)) for m in live)
+    group = len(grid['score']) * len(grid['iou']) * math.prod(len(plan.points) for plan in plans.values())
+    ranked, best = rank_settings(settings, plans, scored, rank_by, group, n_classes)
+    out = {'settings': settings, 'results': scored['mota'], 'ranked': ranked, 'best': best}
+    out.update((m.results, scored[m.name]) for m in live[1:])
     return out
 
 
@@ -1226,70 +1298,15 @@ def flag_line(setting):
     join = lambda v: ','.join(repr(float(x)) for x in v)
     line = '--score-threshold=%s --iou-threshold=%s --max-age=%d --min-hits=%d' % (
         join(setting['score_threshold']), join(setting['iou_threshold']), setting['max_age'], setting['min_hits'])
-    if 'low_score_threshold' in setting:
-        line += ' --low-score-threshold=%s --low-iou-threshold=%s' % (join(setting['low_score_threshold']), join(setting['low_iou_threshold']))
-    if 'split_iou' in setting:
-        line += ' --split-iou=%s' % join(setting['split_iou'])
-        if setting.get('split_gap', 0):
-            line += ' --split-gap=%d' % setting['split_gap']
-        if setting.get('split_motion', 'linear') != 'linear':
-            line += ' --split-motion=%s' % setting['split_motion']
-    if 'link_gap' in setting:
-        line += ' --link-gap=%s --link-iou=%s' % (','.join('%d' % v for v in setting['link_gap']), join(setting['link_iou']))
-        if setting.get('link_motion', 'hold') != 'hold':
-            line += ' --link-motion=%s' % setting['link_motion']
-    if 'dedup_frames' in setting:
-        line += ' --dedup-frames=%s --dedup-iou=%s --dedup-frac=%r' % (','.join('%d' % v for v in setting['dedup_frames']), join(setting['dedup_iou']),
-                                                                        float(setting.get('dedup_frac', 0.5)))
-    if 'interp_gap' in setting:
-        line += ' --interpolate-gap=%s --min-track-len=%s' % (','.join('%d' % v for v in setting['interp_gap']),
-                                                              ','.join('%d' % v for v in setting['min_len']))
-    if 'smooth_window' in setting:
-        line += ' --smooth-window=%s --smooth-sigma=%s' % (','.join('%d' % v for v in setting['smooth_window']), join(setting['smooth_sigma']))
-        if setting.get('smooth_kernel', 'gaussian') != 'gaussian':
-            line += ' --smooth-kernel=%s' % setting['smooth_kernel']
+    for p in (SECOND,) + PASSES:
+        if p.axes[0].combined not in setting:
+            continue
+        line += ''.join(' %s=%s' % (a.flag, a.join(setting[a.combined])) for a in p.axes)
+        for s in p.singles:
+            value = s.cast(setting.get(s.key, s.default))
+            if s.always or value != s.default:
+                line += ' %s=%s' % (s.flag, s.fmt % value)
     return line
-
-
-def format_table(result, name=''):
-    lines = ['%s  (ignored rows: %d)' % (name, result.ignored_rows),
-             '%-6s %-8s %9s %9s %9s %9s %7s %9s %9s' % ('class', 'level', 'gt', 'tp', 'fn', 'fp', 'idsw', 'MOTA', 'MOTP')]
-    for c, rows in result.table.items():
-        for lv in LEVELS:
-            r = rows[lv]
-            lines.append('%-6s LEVEL_%d  %9d %9d %9d %9d %7d %9.5f %9.5f' % (c, lv, r['gt'], r['tp'], r['fn'], r['fp'], r['idsw'],
-                                                                         r['MOTA'], r['MOTP']))
-    return '\n'.join(lines)
-
-
-def format_identity_table(result, name=''):
-    lines = ['%s  identity' % name,
-             '%-6s %-8s %9s %9s %9s %9s %9s %9s' % ('class', 'level', 'IDTP', 'IDFN', 'IDFP', 'IDF1', 'IDP', 'IDR')]
-    for c, rows in result.table.items():
-        for lv in LEVELS:
-            r = rows[lv]
-            lines.append('%-6s LEVEL_%d  %9d %9d %9d %9.5f %9.5f %9.5f' % (c, lv, r['idtp'], r['idfn'], r['idfp'], r['idf1'], r['idp'], r['idr']))
-    return '\n'.join(lines)
-
-
-def format_hota_table(result, name=''):
-    lines = ['%s  HOTA' % name,
-             '%-6s %-8s %9s %9s %9s %9s %9s %9s %9s %9s %9s %9s' % (('class', 'level') + HOTA_NAMES + ('HOTA(0)', 'LocA(0)'))]
-    for c, rows in result.table.items():
-        for lv in LEVELS:
-            r = rows[lv]
-            lines.append('%-6s LEVEL_%d  ' % (c, lv) + ' '.join('%9.5f' % r[n] for n in HOTA_NAMES + ('HOTA(0)', 'LocA(0)')))
-    return '\n'.join(lines)
-
-
-def format_coverage_table(result, name=''):
-    lines = ['%s  coverage' % name,
-             '%-6s %-8s %9s %9s %9s %9s %9s %9s %9s' % ('class', 'level', 'traj', 'mt', 'pt', 'ml', 'MT', 'ML', 'FM')]
-    for c, rows in result.table.items():
-        for lv in LEVELS:
-            r = rows[lv]
-            lines.append('%-6s LEVEL_%d  %9d %9d %9d %9d %9.5f %9.5f %9d' % (c, lv, r['traj'], r['mt'], r['pt'], r['ml'], r['MT'], r['ML'], r['FM']))
-    return '\n'.join(lines)
 
 
 def build_parser():
@@ -1303,28 +1320,16 @@ def build_parser():
     parser.add_argument('--iou-grid', default='0.0,0.01,0.1,0.3')
     parser.add_argument('--max-age', default='1,2,3')
     parser.add_argument('--min-hits', default='0,1')
-    parser.add_argument('--low-score-grid', default='', help='second association of the tracker: detections from this score on may continue an unmatched track '
-                                                             '(tracking/track.py --low-score-threshold; a value above the point\'s score is clamped to it; empty = off)')
-    parser.add_argument('--low-iou-grid', default='0.5', help='second association: lowest IoU of a low-score detection and its track; read when --low-score-grid is set')
-    parser.add_argument('--gap-grid', default='0', help='track refinement: gaps of up to this many frames are interpolated (tracking/refine.py)')
-    parser.add_argument('--min-len-grid', default='1', help='track refinement: tracks observed in fewer frames are dropped')
-    parser.add_argument('--split-iou-grid', default='0', help='track splitting: a track is cut where the extrapolated boxes overlap by less than this IoU (tracking/split.py)')
-    parser.add_argument('--split-gap', type=int, default=0, help='track splitting: a track is cut where more than this many frames lie between two boxes; read when --split-iou-grid is set')
-    parser.add_argument('--split-motion', choices=('linear', 'hold'), default='linear', help='track splitting: how a box is extrapolated')
-    parser.add_argument('--link-gap-grid', default='0', help='track stitching: tracks are linked across up to this many frames (tracking/stitch.py)')
-    parser.add_argument('--link-iou-grid', default='0.3', help='track stitching: lowest IoU of the extrapolated and the new box; read when --link-gap-grid is set')
-    parser.add_argument('--link-motion', choices=('hold', 'linear'), default='hold', help='track stitching: how an ended track is extrapolated')
-    parser.add_argument('--dedup-frames-grid', default='0', help='track deduplication: a track is dropped when a stronger one overlaps it in this many frames (tracking/dedup.py)')
-    parser.add_argument('--dedup-iou-grid', default='0.7', help='track deduplication: lowest IoU of the two boxes that counts; read when --dedup-frames-grid is set')
-    parser.add_argument('--dedup-frac', type=float, default=0.5, help='track deduplication: lowest share of the shorter track\'s frames that must count')
-    parser.add_argument('--smooth-window-grid', default='0', help='track smoothing: boxes are averaged over up to this many frames to either side (tracking/smooth.py)')
-    parser.add_argument('--smooth-sigma-grid', default='1.0', help='track smoothing: width of the gaussian weights; read when --smooth-window-grid is set')
-    parser.add_argument('--smooth-kernel', choices=('gaussian', 'box'), default='gaussian', help='track smoothing: the weights over the window')
+    for p in _KEY_ORDER:
+        for a in p.axes:
+            parser.add_argument('--%s-grid' % a.key.replace('_', '-'), default=a.text, help=a.help)
+        for s in p.singles:
+            parser.add_argument(s.flag, default=s.default, help=s.help, **({'choices': s.choices} if s.choices else {'type': s.cast}))
     parser.add_argument('--top', type=int, default=10, help='ranked settings to print per level')
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
     parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
     parser.add_argument('--coverage', action='store_true', help='also score trajectory coverage: mostly tracked / partially tracked / mostly lost, fragmentations')
-    parser.add_argument('--rank-by', choices=('mota', 'idf1', 'hota', 'mt'), default='mota',
+    parser.add_argument('--rank-by', choices=tuple(m.name for m in METRICS), default='mota',
                         help='what the sweep ranks by (idf1 implies --identity, hota implies --hota, mt implies --coverage)')
     return parser
 
@@ -1332,42 +1337,25 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     gt = load_ground_truth(args.annotations)
+    live = [m for m in METRICS if m.option is None or getattr(args, m.option) or (args.sweep and args.rank_by == m.name)]
     if args.sweep:
         grid = {'score': _grid_values(args.score_grid), 'iou': _grid_values(args.iou_grid),
-                'max_age': [int(v) for v in args.max_age.split(',')], 'min_hits': [int(v) for v in args.min_hits.split(',')],
-                'gap': [int(v) for v in args.gap_grid.split(',')], 'min_len': [int(v) for v in args.min_len_grid.split(',')],
-                'link_gap': [int(v) for v in args.link_gap_grid.split(',')], 'link_iou': _grid_values(args.link_iou_grid),
-                'link_motion': args.link_motion, 'split_iou': _grid_values(args.split_iou_grid), 'split_gap': args.split_gap,
-                'split_motion': args.split_motion,
-                'dedup_frames': [int(v) for v in args.dedup_frames_grid.split(',')], 'dedup_iou': _grid_values(args.dedup_iou_grid),
-                'dedup_frac': args.dedup_frac,
-                'smooth_window': [int(v) for v in args.smooth_window_grid.split(',')], 'smooth_sigma': _grid_values(args.smooth_sigma_grid),
-                'smooth_kernel': args.smooth_kernel,
-                'low_score': _grid_values(args.low_score_grid) if args.low_score_grid else [], 'low_iou': _grid_values(args.low_iou_grid)}
-        identity = args.identity or args.rank_by == 'idf1'
-        hota = args.hota or args.rank_by == 'hota'
-        coverage = args.coverage or args.rank_by == 'mt'
-        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), identity=identity, rank_by=args.rank_by, hota=hota,
-                    coverage=coverage)
+                'max_age': _int_values(args.max_age), 'min_hits': _int_values(args.min_hits)}
+        for p in (SECOND,) + PASSES:
+            grid.update((a.key, a.parse(getattr(args, a.key + '_grid'))) for a in p.axes)
+            grid.update((s.key, getattr(args, s.key)) for s in p.singles)
+        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), rank_by=args.rank_by, **dict((m.option, True) for m in live[1:]))
         for lv in LEVELS:
             print('LEVEL_%d: %d settings tracked, best per class combined for each (max_age, min_hits)' % (lv, len(res['settings'])))
             for r in res['ranked'][lv][:args.top]:
-                extra = ('  IDF1 %9.5f' % r['IDF1'] if identity else '') + ('  HOTA %9.5f' % r['HOTA'] if hota else '')
-                extra += '  MT %9.5f  ML %9.5f  FM %d' % (r['MT'], r['ML'], r['FM']) if coverage else ''
-                print('  MOTA %9.5f%s  %s' % (r['MOTA'], extra, flag_line(r)))
+                print(''.join(m.line(r) for m in live) + '  ' + flag_line(r))
         if args.json:
+            doc = {'settings': res['settings'], 'tables': [r.as_json() for r in res['results']],
+                   'ranked': dict(('LEVEL_%d' % lv, v) for lv, v in res['ranked'].items())}
+            for m in live[1:]:
+                doc[m.tables] = [r.as_json() for r in res[m.results]]
+                doc['rank_by'] = args.rank_by
             with open(args.json, 'wt') as fp:
-                doc = {'settings': res['settings'], 'tables': [r.as_json() for r in res['results']],
-                       'ranked': dict(('LEVEL_%d' % lv, v) for lv, v in res['ranked'].items())}
-                if identity:
-                    doc['identity_tables'] = [r.as_json() for r in res['id_results']]
-                    doc['rank_by'] = args.rank_by
-                if hota:
-                    doc['hota_tables'] = [r.as_json() for r in res['hota_results']]
-                    doc['rank_by'] = args.rank_by
-                if coverage:
-                    doc['coverage_tables'] = [r.as_json() for r in res['coverage_results']]
-                    doc['rank_by'] = args.rank_by
                 json.dump(doc, fp)
         if res['best'][2] is not None:
             print(flag_line(res['best'][2]))
@@ -1375,29 +1363,16 @@ def main(argv=None):
     if not args.tracks:
         raise SystemExit('give at least one tracking JSON, or --sweep DETECTIONS.json')
     tracks = [load_tracks(p) for p in args.tracks]
-    results = evaluate_tracks(gt, tracks, args.iou_threshold)
-    id_results = evaluate_identity(gt, tracks, args.iou_threshold) if args.identity else [None] * len(results)
-    hota_results = evaluate_hota(gt, tracks, args.iou_threshold) if args.hota else [None] * len(results)
-    cov_results = evaluate_coverage(gt, tracks, args.iou_threshold) if args.coverage else [None] * len(results)
-    for path, r, ir, hr, cr in zip(args.tracks, results, id_results, hota_results, cov_results):
-        print(format_table(r, path))
-        if cr is not None:
-            print(format_coverage_table(cr, path))
-        if ir is not None:
-            print(format_identity_table(ir, path))
-        if hr is not None:
-            print(format_hota_table(hr, path))
+    scored = dict((m.name, globals()[m.evaluate](gt, tracks, args.iou_threshold)) for m in live)
+    for k, path in enumerate(args.tracks):
+        for m in _PRINT_ORDER:
+            if m in live:
+                print(m.table(scored[m.name][k], path))
     if args.json:
-        doc = dict((p, r.as_json()) for p, r in zip(args.tracks, results))
-        for p, ir in zip(args.tracks, id_results):
-            if ir is not None:
-                doc[p]['identity'] = ir.as_json()['table']
-        for p, hr in zip(args.tracks, hota_results):
-            if hr is not None:
-                doc[p]['hota'] = hr.as_json()['table']
-        for p, cr in zip(args.tracks, cov_results):
-            if cr is not None:
-                doc[p]['coverage'] = cr.as_json()['table']
+        doc = dict((p, r.as_json()) for p, r in zip(args.tracks, scored['mota']))
+        for m in live[1:]:
+            for p, r in zip(args.tracks, scored[m.name]):
+                doc[p][m.section] = r.as_json()['table']
         with open(args.json, 'wt') as fp:
             json.dump(doc, fp)
     return 0

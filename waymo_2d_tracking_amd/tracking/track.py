@@ -13,6 +13,7 @@ process only), and the post-passes of split.py, stitch.py, dedup.py, xclass.py, 
 for them.
 """
 import argparse
+import importlib
 import json
 import time
 
@@ -150,33 +151,37 @@ def smooths(args):
     return max(args.smooth_window) > 0
 
 
+def _stage(name):
+    return importlib.import_module('.' + name, __package__)
+
+
+def _split(args, packed, out, n_classes):
+    from . import utils as T
+    # the tracker writes the id counter + 1 for a birth; so does a new piece
+    out = _stage('split').split_one(packed, out, args.split_iou, args.split_gap, args.split_motion, T._GLOBAL_IDS['next'] + 1, n_classes)
+    T._GLOBAL_IDS['next'] += out['n_new']
+    return out
+
+
+# (whether the flags ask for the pass, what runs it - its module is imported then), in the order of the chain: splitting first, so
+# that the pieces of an impure track can be linked to the tracks they belong to - a new piece takes the next id of the tracker's
+# counter, as a birth does; then stitching, so that a merged track is length-filtered and gap-filled as one; then the suppression
+# of duplicates, which judges a stitched track at its full length and leaves gap filling and the length filter the survivors only -
+# inside a class first, then across the class pairs that are switched on; smoothing last, so that filled rows are smoothed too
+PASSES = (
+    (splits, _split),
+    (stitches, lambda args, packed, out, n: _stage('stitch').stitch_one(packed, out, args.link_gap, args.link_iou, args.link_motion, n)),
+    (dedups, lambda args, packed, out, n: _stage('dedup').dedup_one(packed, out, args.dedup_frames, args.dedup_iou, args.dedup_frac, n)),
+    (xclasses, lambda args, packed, out, n: _stage('xclass').xclass_one(packed, out, xclass_pairs(args), args.xclass_prio, args.xclass_measure, n)),
+    (refines, lambda args, packed, out, n: _stage('refine').refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, n)),
+    (smooths, lambda args, packed, out, n: _stage('smooth').smooth_one(packed, out, args.smooth_window, args.smooth_sigma, args.smooth_kernel, n)))
+
+
 def refined(args, packed, out):
-    """The tracker's rows after the post-passes the flags ask for: splitting first, so that the pieces of an impure track can be
-    linked to the tracks they belong to - a new piece takes the next id of the tracker's counter, as a birth does; then stitching,
-    so that a merged track is length-filtered and gap-filled as one; then the suppression of duplicates, which judges a stitched
-    track at its full length and leaves gap filling and the length filter the survivors only - inside a class first, then across
-    the class pairs that are switched on; smoothing last, so that filled rows are smoothed too."""
-    if splits(args):
-        from . import utils as T
-        from .split import split_one
-        # the tracker writes the id counter + 1 for a birth; so does a new piece
-        out = split_one(packed, out, args.split_iou, args.split_gap, args.split_motion, T._GLOBAL_IDS['next'] + 1, len(args.iou_threshold))
-        T._GLOBAL_IDS['next'] += out['n_new']
-    if stitches(args):
-        from .stitch import stitch_one
-        out = stitch_one(packed, out, args.link_gap, args.link_iou, args.link_motion, len(args.iou_threshold))
-    if dedups(args):
-        from .dedup import dedup_one
-        out = dedup_one(packed, out, args.dedup_frames, args.dedup_iou, args.dedup_frac, len(args.iou_threshold))
-    if xclasses(args):
-        from .xclass import xclass_one
-        out = xclass_one(packed, out, xclass_pairs(args), args.xclass_prio, args.xclass_measure, len(args.iou_threshold))
-    if refines(args):
-        from .refine import refine_one
-        out = refine_one(packed, out, args.interpolate_gap, args.min_track_len, args.track_score, len(args.iou_threshold))
-    if smooths(args):
-        from .smooth import smooth_one
-        out = smooth_one(packed, out, args.smooth_window, args.smooth_sigma, args.smooth_kernel, len(args.iou_threshold))
+    """The tracker's rows after the post-passes the flags ask for, in the order of PASSES."""
+    for asked, run in PASSES:
+        if asked(args):
+            out = run(args, packed, out, len(args.iou_threshold))
     return out
 
 
@@ -286,7 +291,7 @@ def main(argv=None):
         from . import utils as T
         packed = T.pack_streams(predictions)
         tracked_predictions = T.format_tracks(packed, refined(args, packed, tracked_byte(args, packed)))
-    elif splits(args) or refines(args) or stitches(args) or dedups(args) or xclasses(args) or smooths(args):
+    elif any(asked(args) for asked, _ in PASSES):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
