@@ -5,15 +5,9 @@ tests/test_dedup_cases.py runs the claims; tests/test_gpu_track_dedup.py compare
 import math
 
 import dedup_ref
+from track_cases import N_CLASSES, by_slot, result
 
-N_CLASSES = 4
 NAN = float('nan')
-
-
-def result(rows):
-    """rows: (slot, category, [x, y, w, h], score, object_id)"""
-    return {'frame': [r[0] for r in rows], 'category': [r[1] for r in rows], 'bbox': [list(r[2]) for r in rows],
-            'score': [r[3] for r in rows], 'object_id': [r[4] for r in rows]}
 
 
 def job(min_frames=0, dup_iou=0.7, dup_frac=0.5):
@@ -24,10 +18,6 @@ def job(min_frames=0, dup_iou=0.7, dup_frac=0.5):
 def track(object_id, slots, x, y=0.0, w=10.0, h=10.0, category=1, score=0.5):
     """one row per slot; x may be a function of the slot"""
     return [(slot, category, [float(x(slot)) if callable(x) else float(x), float(y), float(w), float(h)], score, object_id) for slot in slots]
-
-
-def by_slot(rows):
-    return sorted(rows, key=lambda r: r[0])           # stable: the order of first appearance is the order given
 
 
 def stream_trajectories(offsets, res, stream=0):

@@ -4,13 +4,7 @@ the list of refine_ref.refine() outputs, one per job - asserts that the case is 
 tests/test_refine_cases.py runs the claims on the reference alone; tests/test_gpu_track_refine.py compares the kernel with it."""
 import random
 
-N_CLASSES = 4
-
-
-def result(rows):
-    """rows: (slot, category, [x, y, w, h], score, object_id)"""
-    return {'frame': [r[0] for r in rows], 'category': [r[1] for r in rows], 'bbox': [list(r[2]) for r in rows],
-            'score': [r[3] for r in rows], 'object_id': [r[4] for r in rows]}
+from track_cases import N_CLASSES, result
 
 
 def job(max_gap=0, min_len=1, score_mode='keep'):

@@ -6,14 +6,7 @@ import math
 import random
 
 import smooth_ref
-
-N_CLASSES = 4
-
-
-def result(rows):
-    """rows: (slot, category, [x, y, w, h], score, object_id)"""
-    return {'frame': [r[0] for r in rows], 'category': [r[1] for r in rows], 'bbox': [list(r[2]) for r in rows],
-            'score': [r[3] for r in rows], 'object_id': [r[4] for r in rows]}
+from track_cases import N_CLASSES, result
 
 
 def job(window=0, weights=None, sigma=1.0, kernel='gaussian', n_weights=None):

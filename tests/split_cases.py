@@ -7,15 +7,9 @@ import random
 from fractions import Fraction
 
 import split_ref
+from track_cases import N_CLASSES, by_slot, result
 
-N_CLASSES = 4
 NAN = float('nan')
-
-
-def result(rows):
-    """rows: (slot, category, [x, y, w, h], score, object_id)"""
-    return {'frame': [r[0] for r in rows], 'category': [r[1] for r in rows], 'bbox': [list(r[2]) for r in rows],
-            'score': [r[3] for r in rows], 'object_id': [r[4] for r in rows]}
 
 
 def job(split_iou=0.0, split_gap=0, motion='linear', first_new_id=None):
@@ -29,10 +23,6 @@ def job(split_iou=0.0, split_gap=0, motion='linear', first_new_id=None):
 def line(oid, slots, v=40.0, y=0.0, cls=1, jump=None):
     """one object on a line: box [v * f, y, 50, 40] at every slot of `slots`; jump = {slot: dx}"""
     return [(f, cls, [v * f + (jump or {}).get(f, 0.0), y, 50.0, 40.0], 0.9, oid) for f in slots]
-
-
-def by_slot(rows):
-    return sorted(rows, key=lambda r: r[0])
 
 
 def pieces_of(done, res, oid):

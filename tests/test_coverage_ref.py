@@ -4,6 +4,7 @@ import math
 
 import coverage_ref
 from coverage_cases import ann, by_pattern, copies, stats_of
+from track_stage_support import predictions_of
 
 
 def _eval(anns, patterns, extra_rows=(), **kw):
@@ -104,12 +105,7 @@ def test_tracked_sequence_with_every_class_of_the_table():
     from waymo_2d_tracking_amd import synthetic as syn
     from waymo_2d_tracking_amd.tracking import utils as T
     dets, gt_json = syn.make_tracking_json(11, n_segments=1, n_frames=24, n_objects=40, integer_boxes=True)
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
+    packed = T.pack_streams(predictions_of(dets))
     out = O.track_streams(packed, 1, 1, [0.6, 0.6, 1.0, 0.6], [0.3, 0.3, 1.0, 0.3])
     ref = coverage_ref.evaluate(gt_json, json.loads(json.dumps(T.format_tracks(packed, out))))
     assert ref['table'][1][2] == dict(traj=116, mt=10, pt=101, ml=5, frag=179, MT=10 / 116, ML=5 / 116, FM=179)

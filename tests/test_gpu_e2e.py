@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from track_stage_support import predictions_of
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -43,12 +45,7 @@ def _synthetic_packed(seed, n_segments=2, n_frames=25, n_objects=30):
     from waymo_2d_tracking_amd import synthetic as syn
     from waymo_2d_tracking_amd.tracking import utils as T
     dets = syn.make_sequence_json(seed, n_segments=n_segments, n_frames=n_frames, n_objects=n_objects)
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    return T.pack_streams(predictions)
+    return T.pack_streams(predictions_of(dets))
 
 
 def test_track_streams_dev_with_category0_holes(oracle):

@@ -1,33 +1,14 @@
 """HIP tracking metric (csrc/mot_eval.hip through tracking/evaluate.py) against the plain-Python restatement tests/mot_ref.py:
 counts, per-row matches and switches, and the float64 IoU sums must be EQUAL - the summation order is part of the definition."""
 import json
-import math
 
 import numpy as np
 import pytest
 
 import mot_ref
+from mot_support import SETTINGS, _track, assert_mot_equals_reference as assert_equals_reference, same_number
 
 pytestmark = pytest.mark.gpu
-
-SETTINGS = [                       # (max_age, min_hits, score thresholds, tracker IoU thresholds): three different results
-    (2, 0, [0.3, 0.2, 1.0, 0.1], [0.01, 0.01, 1.0, 0.0]),
-    (1, 1, [0.6, 0.6, 1.0, 0.6], [0.3, 0.3, 1.0, 0.3]),
-    (3, 0, [0.0, 0.0, 0.0, 0.0], [0.1, 0.1, 0.1, 0.1]),
-]
-
-
-def _track(dets, max_age, min_hits, score_thr, iou_thr):
-    """Detections list -> the rows tracking/track.py would write, through a JSON round trip like a file."""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    out, _ = T.track_packed(packed, iou_thr, max_age, min_hits, score_thr)
-    return json.loads(json.dumps(T.format_tracks(packed, out)))
 
 
 @pytest.fixture(scope='module', params=[True, False], ids=['integer_boxes', 'fractional_boxes'])
@@ -37,28 +18,6 @@ def sequence(request):
                                            integer_boxes=request.param)
     results = [_track(dets, *s) for s in SETTINGS]
     return gt_json, results
-
-
-def same_number(a, b):
-    return (a == b) or (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b))
-
-
-def assert_equals_reference(got, ref, n_classes=4):
-    """MotResult (per_row=True) == mot_ref.evaluate() output: everything, exactly."""
-    assert got.stream_keys == ref['stream_keys']
-    for s, key in enumerate(got.stream_keys):
-        for c in range(1, n_classes + 1):
-            for li, lv in enumerate((1, 2)):
-                exp = ref['per_stream'][key][c][lv]
-                assert got.counts[s, c - 1, li].tolist() == [exp[f] for f in mot_ref.FIELDS], (key, c, lv)
-                assert got.iou_sum[s, c - 1, li] == exp['iou_sum'], (key, c, lv, got.iou_sum[s, c - 1, li], exp['iou_sum'])
-    assert got.hyp_match.tolist() == ref['hyp_match']
-    assert got.hyp_switch.tolist() == ref['hyp_switch']
-    assert got.ignored_rows == ref['ignored_rows']
-    for c, rows in ref['table'].items():
-        for lv, row in rows.items():
-            for name, v in row.items():
-                assert same_number(got.table[c][lv][name], v), (c, lv, name, got.table[c][lv][name], v)
 
 
 def test_device_equals_reference_on_tracked_sequences(sequence):

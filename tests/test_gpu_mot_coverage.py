@@ -7,7 +7,7 @@ import pytest
 
 import coverage_cases
 import coverage_ref
-from test_gpu_mot import SETTINGS, _track, same_number
+from mot_support import SETTINGS, _track, same_number
 
 pytestmark = pytest.mark.gpu
 

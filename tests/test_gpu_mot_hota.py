@@ -5,7 +5,8 @@ is added in the restatement's order (frame, then ground-truth row) and must be e
 non-negative terms that are bit-equal on both sides and differ only in the order they are added in (the kernel: per lane over the
 cells, then over the lanes), so they may differ by the standard bound for such a sum, relative 2 n 2^-53 with n its number of terms.
 Table values are a handful of correctly rounded operations on those sums (a quotient, a product, a square root, a mean of 19
-non-negative values): the same bound with 64 added to n covers them."""
+non-negative values): the same bound with 64 added to n covers them.  The comparator that holds these bounds is
+tests/mot_support.py's assert_hota_equals_reference: the sweep tests of the track post-passes use it too."""
 import ctypes
 import json
 import math
@@ -15,47 +16,11 @@ import numpy as np
 import pytest
 
 import hota_ref
-from test_gpu_mot_identity import SETTINGS, _copy_as_result, _track
+from mot_support import EPS, SETTINGS, _copy_as_result, _track, assert_hota_equals_reference as assert_equals_reference, same_number
 
 pytestmark = pytest.mark.gpu
 
 THR = hota_ref.DEFAULT_IOU_THRESHOLD
-EPS = 2.0 ** -53
-
-
-def same_number(a, b, rel=0.0):
-    if isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b):
-        return True
-    return a == b or abs(a - b) <= rel * abs(b)
-
-
-def assert_equals_reference(got, ref, n_classes=4):
-    """HotaResult == hota_ref.evaluate() output: counts, sums (see the module text), table and ignored rows."""
-    assert got.stream_keys == ref['stream_keys']
-    most_terms = 0
-    for s, key in enumerate(got.stream_keys):
-        for c in range(1, n_classes + 1):
-            for li, lv in enumerate((1, 2)):
-                exp = ref['per_stream'][key][c][lv]
-                assert got.hota_counts[s, c - 1, li].tolist() == [exp['gt'], exp['hyp']] + exp['tp'], (key, c, lv)
-                sums = got.hota_sums[s, c - 1, li]
-                assert sums[:, 3].tolist() == exp['loc'], (key, c, lv)
-                for a in range(19):
-                    n = exp['terms'][a]
-                    most_terms = max(most_terms, n)
-                    for q, name in enumerate(('ass', 'assre', 'asspr')):
-                        assert same_number(float(sums[a, q]), exp[name][a], 2 * n * EPS), (key, c, lv, a, name, float(sums[a, q]), exp[name][a])
-    assert got.ignored_rows == ref['ignored_rows']
-    assert set(got.table) == set(ref['table'])
-    rel = 2 * (most_terms * len(got.stream_keys) * n_classes + 64) * EPS
-    for c, rows in ref['table'].items():
-        for lv, row in rows.items():
-            mine = got.table[c][lv]
-            assert (mine['gt'], mine['hyp'], mine['tp']) == (row['gt'], row['hyp'], row['tp'])
-            for name in hota_ref.NAMES + ('HOTA(0)', 'LocA(0)'):
-                assert same_number(mine[name], row[name], rel), (c, lv, name, mine[name], row[name])
-            for name in hota_ref.NAMES:
-                assert all(same_number(x, y, rel) for x, y in zip(mine['per_alpha'][name], row['per_alpha'][name])), (c, lv, name)
 
 
 def assert_rows_equal_reference(gt_json, rows, got, ref, n_classes=4):

@@ -9,28 +9,11 @@ import numpy as np
 import pytest
 
 import mot_id_ref
+from mot_support import SETTINGS, _copy_as_result, _track, assert_mot_equals_reference, same_number
 
 pytestmark = pytest.mark.gpu
 
-SETTINGS = [                       # (max_age, min_hits, score thresholds, tracker IoU thresholds): the three of tests/test_gpu_mot.py
-    (2, 0, [0.3, 0.2, 1.0, 0.1], [0.01, 0.01, 1.0, 0.0]),
-    (1, 1, [0.6, 0.6, 1.0, 0.6], [0.3, 0.3, 1.0, 0.3]),
-    (3, 0, [0.0, 0.0, 0.0, 0.0], [0.1, 0.1, 0.1, 0.1]),
-]
 THR = mot_id_ref.DEFAULT_IOU_THRESHOLD
-
-
-def _track(dets, max_age, min_hits, score_thr, iou_thr):
-    """Detections list -> the rows tracking/track.py would write, through a JSON round trip like a file."""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    out, _ = T.track_packed(packed, iou_thr, max_age, min_hits, score_thr)
-    return json.loads(json.dumps(T.format_tracks(packed, out)))
 
 
 @pytest.fixture(scope='module', params=[True, False], ids=['integer_boxes', 'fractional_boxes'])
@@ -42,10 +25,6 @@ def sequence(request):
     results = [_track(dets, *s) for s in SETTINGS]
     refs = [mot_id_ref.evaluate(gt_json, r) for r in results]
     return gt_json, results, refs
-
-
-def same_number(a, b):
-    return (a == b) or (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b))
 
 
 def assert_equals_reference(got, ref, n_classes=4):
@@ -179,11 +158,6 @@ def _without_dont_care_on_counted(gt_json):
     return dict(gt_json, annotations=keep)
 
 
-def _copy_as_result(gt_json):
-    return [{'image_id': a['image_id'], 'bbox': a['bbox'], 'score': 1.0, 'category_id': a['category_id'], 'object_id': a['object_id']}
-            for a in gt_json['annotations'] if a['bbox'][2] >= 1 and a['bbox'][3] >= 1]
-
-
 def test_ground_truth_against_itself_and_against_nothing(sequence):
     from waymo_2d_tracking_amd.tracking import evaluate as E
     gt_json, _, _ = sequence
@@ -210,7 +184,6 @@ def test_empty_sides_through_all_four_forms():
     """The early returns of the library: a result without rows, a result whose rows all lie on frames the ground truth does not
     have, and a ground truth without streams.  Host and device form of both metrics, each against its reference."""
     import mot_ref
-    from test_gpu_mot import assert_equals_reference as assert_equals_mot_reference
     from waymo_2d_tracking_amd.tracking import evaluate as E
     anns = [{'image_id': 'seg/%d/FRONT' % f, 'bbox': [100 * i + 3 * f, 10, 50, 60], 'category_id': 1 + i, 'object_id': 'o%d' % i,
              'tracking_difficulty_level': 1 + i} for f in range(3) for i in range(2)]
@@ -228,7 +201,7 @@ def test_empty_sides_through_all_four_forms():
         mot = [E.evaluate_tracks(gt, tracks, per_row=True)[0], dev_mot.results(per_row=True)[0]]
         ident = [E.evaluate_identity(gt, tracks, per_row=True)[0], dev_id.results(per_row=True)[0]]
         for got in mot:
-            assert_equals_mot_reference(got, mot_exp)
+            assert_mot_equals_reference(got, mot_exp)
             assert np.array_equal(got.counts, mot[0].counts) and np.array_equal(got.iou_sum, mot[0].iou_sum), name
             assert np.array_equal(got.hyp_match, mot[0].hyp_match) and np.array_equal(got.hyp_switch, mot[0].hyp_switch), name
         for got in ident:

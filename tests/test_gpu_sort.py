@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from track_stage_support import predictions_of
 from waymo_2d_tracking_amd.tracking import utils as T
 
 pytestmark = pytest.mark.gpu
@@ -174,12 +175,7 @@ def test_synthetic_streams_vs_oracle(oracle, seed, n_objects, integer):
     """Waymo-shaped streams: 2 segments x 5 cameras; IDs, order and boxes identical to the oracle."""
     from waymo_2d_tracking_amd import synthetic as syn
     dets = syn.make_sequence_json(seed, n_segments=2, n_frames=40, n_objects=n_objects, integer_boxes=integer)
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
+    packed = T.pack_streams(predictions_of(dets))
     sthr, ithr = [0.3, 0.2, 1.0, 0.1], [0.01, 0.01, 1.0, 0.0]
     out, births = T.track_packed(packed, ithr, 2, 0, sthr)
     ref = oracle.track_streams(packed, 2, 0, sthr, ithr)
@@ -195,12 +191,7 @@ def test_full_size_properties():
     """Config 1 at full size (198 frames x 5 cameras, ~100 boxes/frame): invariants that need no oracle."""
     from waymo_2d_tracking_amd import synthetic as syn
     dets = syn.make_sequence_json(0, n_segments=1, n_frames=198, n_objects=100)
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
+    packed = T.pack_streams(predictions_of(dets))
     ithr = [0.01, 0.01, 1.0, 0.0]
     out, births = T.track_packed(packed, ithr, 2, 0, [0.0] * 4)
     out2, births2 = T.track_packed(packed, ithr, 2, 0, [0.0] * 4)
@@ -213,15 +204,6 @@ def test_full_size_properties():
     assert np.all(out['bbox'][:, 2] >= 1) and np.all(out['bbox'][:, 3] >= 1)             # utils.py:45
     assert np.all((out['score'] >= 0.2) & (out['score'] <= 1.0))                         # utils.py:49
     assert len(out['frame']) <= packed['x'].size                                         # one row per matched det at most
-
-
-def _pred_from_json(dets):
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    return predictions
 
 
 def test_edge_cases_empty_and_single(oracle):
@@ -261,7 +243,7 @@ def test_large_frames_use_the_global_cost_path(oracle):
     d = syn.stream_detections(rng, 12, 420, 'FRONT', clutter=0.05)
     d['cat'][:] = 1                                     # one class: N ~ 400 per frame, T up to ~ 3 N
     dets = syn.detections_json([('seg', 'FRONT', d)])
-    packed = T.pack_streams(_pred_from_json(dets))
+    packed = T.pack_streams(predictions_of(dets))
     ithr, sthr = [0.05, 0.01, 1.0, 0.0], [0.0] * 4
     out, births = T.track_packed(packed, ithr, 2, 0, sthr)
     ref = oracle.track_streams(packed, 2, 0, sthr, ithr)
@@ -322,12 +304,7 @@ def test_helper_waves_and_plain_kernel_both_equal_the_oracle(oracle, n_segments)
     from waymo_2d_tracking_amd import synthetic as syn
     from waymo_2d_tracking_amd.tracking import utils as T
     dets = syn.make_sequence_json(21, n_segments=n_segments, n_frames=12, n_objects=45)
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
+    packed = T.pack_streams(predictions_of(dets))
     assert len(packed['stream_frame_offsets']) - 1 == 5 * n_segments
     sthr, ithr = [0.0, 0.0, 0.0, 0.0], [0.01, 0.01, 0.3, 0.0]
     out, births = T.track_packed(packed, ithr, 2, 0, sthr)

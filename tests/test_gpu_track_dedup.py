@@ -1,8 +1,8 @@
 """HIP track deduplication (csrc/track_dedup.hip through tracking/dedup.py) against the plain-Python restatement
 tests/dedup_ref.py: keep, by, match, the row mask, the counts and the surviving rows must be EQUAL bit for bit - no float is
 produced, rows are only selected; the operation order of the IoU, the one multiplication of the fraction test and the strict
-strength order are part of the definition."""
-import ctypes as C
+strength order are part of the definition.  The comparator and the bodies shared with the other
+post-passes are in tests/track_stage_support.py."""
 import json
 import os
 
@@ -11,65 +11,23 @@ import pytest
 
 import dedup_cases
 import dedup_ref
-import hota_ref
-import mot_id_ref
 import mot_ref
 import refine_cases
 import refine_ref
 import stitch_cases
 import stitch_ref
-from test_gpu_mot_hota import assert_equals_reference as assert_hota_equals_reference
+import track_stage_support as H
+from mot_support import assert_hota_equals_reference
+from track_stage_support import COLUMNS, G4, G5, arrays, packed_for
 
 pytestmark = pytest.mark.gpu
 
+STAGE = H.STAGES['dedup']
+assert_same = STAGE.assert_same
 JOBS = [dedup_cases.job(min_frames=1, dup_iou=0.9, dup_frac=0.0),                             # the loosest: every injected copy is a duplicate
         dedup_cases.job(min_frames=[3, 2, 0, 1], dup_iou=[0.9, 0.5, 0.7, 0.8], dup_frac=[0.5, 1.0, 0.5, 0.25]),
         dedup_cases.job(min_frames=2, dup_iou=0.7, dup_frac=0.5),
         dedup_cases.job(min_frames=4, dup_iou=0.99, dup_frac=1.0)]                            # the strictest
-G4 = dict(score=[0.3, 0.3, 1.0, 0.2], iou=[0.01, 0.01, 1.0, 0.0])
-G5 = dict(score=[0.95, 0.6, 1.0, 0.9], iou=[0.01, 0.01, 1.0, 0.0])
-COLUMNS = ('frame', 'category', 'bbox', 'score', 'object_id')
-
-
-def packed_for(offsets):
-    """the part of a packed detection set that the pass reads, for hand-made slots"""
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
-
-
-def assert_same(got, ref, out):
-    """got: a dict of tracking/dedup.py; ref: dedup_ref.dedup() of `out`"""
-    assert got['keep'].tolist() == ref['keep'] and got['by'].tolist() == ref['by'] and got['match'].tolist() == ref['match']
-    assert got['row_keep'].tolist() == ref['row_keep']
-    assert got['n_dropped'].tolist() == ref['n_dropped'] and got['traj_offsets'].tolist() == ref['traj_offsets']
-    assert [(int(a), int(b), m) for a, b, m in got['dropped']] == ref['dropped']
-    mask = np.asarray(ref['row_keep'], bool)
-    for name in COLUMNS:                                                  # the surviving rows, in the caller's order, with their input bits
-        want = np.asarray(out[name])[mask]
-        assert got[name].dtype == want.dtype and got[name].shape == want.shape and got[name].tobytes() == want.tobytes(), name
-    assert [int(v) for v in got['frame']] == ref['frame'] and [int(v) for v in got['object_id']] == ref['object_id']
-    assert got['bbox'].tobytes() == np.asarray(ref['bbox'], np.float64).reshape(-1, 4).tobytes()
-    assert got['score'].tobytes() == np.asarray(ref['score'], np.float64).tobytes()
-
-
-def rows_of(ref):
-    """the surviving rows of a reference as the arrays the next pass and the writers take"""
-    return arrays(ref)
-
-
-def lds_limit():
-    from waymo_2d_tracking_amd import _lib
-    n = C.c_int32(0)
-    _lib.lib().wt_dedup_tracks_limits(C.byref(n))
-    return n.value
 
 
 def with_copies(packed, out):
@@ -98,11 +56,8 @@ def with_copies(packed, out):
 @pytest.fixture(scope='module')
 def tracked(golden_dir):
     """The two tracking fixtures tracked with max_age 2, with injected copies: [(packed, out, copies, the tracker's own rows)], g4 first."""
-    from waymo_2d_tracking_amd.tracking import utils as T
     sets = []
-    for name, cfg in (('sort_g4_input.json', G4), ('sort_g5_input.json', G5)):
-        packed = T.pack_streams(T.read_data_file(os.path.join(golden_dir, name), cfg['score']))
-        plain = T.track_packed(packed, cfg['iou'], 2, 0)[0]
+    for packed, plain in H.tracked_fixtures(golden_dir):
         plain = dict((k, plain[k]) for k in COLUMNS)
         out, copies = with_copies(packed, plain)
         sets.append((packed, out, copies, plain))
@@ -116,15 +71,7 @@ def tracked_refs(tracked):
 
 @pytest.mark.parametrize('name', sorted(dedup_cases.CASES))
 def test_case_equals_reference(name):
-    from waymo_2d_tracking_amd.tracking import dedup as D
-    offsets, result, jobs, claim = dedup_cases.CASES[name]()
-    refs = [dedup_ref.dedup(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    got = D.dedup_tracks(packed_for(offsets), [out], jobs)
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert_same(g, ref, out)
+    H.check_case(STAGE, name)
 
 
 def test_deep_chain_takes_one_round_per_link():
@@ -163,22 +110,11 @@ def test_settings_on_the_tracked_sequences_equal_the_reference(tracked, tracked_
 
 
 def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tracked, tracked_refs):
-    import torch
-    from waymo_2d_tracking_amd.tracking import dedup as D
     packed, out, _, plain = tracked[0]
     outs = [out, plain]                                                  # a second result over the same slots: without the copies
     plain_refs = [dedup_ref.dedup(packed['stream_frame_offsets'], plain, j) for j in JOBS]
-    refs = [tracked_refs[0], plain_refs]
     pairs = [(1, 0), (0, 1), (1, 3), (0, 2), (1, 1), (0, 0)]             # (result, job): results interleaved
-    jobs = [dict(JOBS[j], result=r) for r, j in pairs]
-    together = D.dedup_tracks(packed, outs, jobs)
-    dev = D.DeviceDedup(packed, outs, jobs)
-    dev.launch()
-    from_dev = dev.results()
-    for (r, j), a, b in zip(pairs, together, from_dev):
-        alone = D.dedup_tracks(packed, [outs[r]], [JOBS[j]])[0]
-        for got in (alone, a, b):
-            assert_same(got, refs[r][j], outs[r])
+    dev, jobs, from_dev = H.check_jobs_over_results(STAGE, packed, outs, [tracked_refs[0], plain_refs], JOBS, pairs)
     # the entries of the result a job does not name are -1
     p = dev.p
     grid = dict((k, dev.out[k].cpu().numpy().reshape(len(jobs), -1)) for k in ('keep', 'by', 'match', 'row_keep'))
@@ -187,47 +123,20 @@ def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tr
         assert (grid[k][0, :split] == -1).all() and (grid[k][1, split:] == -1).all()
     assert (grid['keep'][0, split:] >= 0).all() and (grid['keep'][1, :split] >= 0).all()
     assert (grid['row_keep'][0, :rows] == -1).all() and (grid['row_keep'][0, rows:] >= 0).all() and (grid['row_keep'][1, rows:] == -1).all()
-    # a second launch on the same buffers gives the same answer (the call initialises everything it reads)
-    dev.launch()
-    for a, b in zip(from_dev, dev.results()):
-        assert all(np.array_equal(a[k], b[k]) for k in ('object_id', 'keep', 'by', 'match', 'row_keep', 'n_dropped')) and a['dropped'] == b['dropped']
-    # a workspace one byte too small: WT_ERR_CAPACITY, nothing launched
-    from waymo_2d_tracking_amd import _lib
-    small = D.DeviceDedup(packed, outs, jobs, workspace_bytes=dev.ws_bytes - 1)
-    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
-        small.launch()
-    torch.cuda.synchronize()
+    H.check_relaunch_and_short_workspace(STAGE, dev, from_dev, packed, outs, jobs, lambda a, b: all(
+        np.array_equal(a[k], b[k]) for k in ('object_id', 'keep', 'by', 'match', 'row_keep', 'n_dropped')) and a['dropped'] == b['dropped'])
 
 
 def test_shuffled_input_gives_the_same_decision_per_row(tracked, tracked_refs):
-    from waymo_2d_tracking_amd.tracking import dedup as D
-    packed, out, _, _ = tracked[0]
-    perm = np.random.default_rng(4).permutation(len(out['frame']))
-    shuffled = dict((k, v[perm]) for k, v in out.items())
-    got = D.dedup_tracks(packed, [shuffled], JOBS[1:3])
-    for g, j, ref in zip(got, JOBS[1:3], tracked_refs[0][1:3]):
-        assert_same(g, dedup_ref.dedup(packed['stream_frame_offsets'], shuffled, j), shuffled)
+    def per_row(g, ref, perm):
         # every row gets the decision it gets in the unshuffled input, in the caller's order
         assert g['row_keep'].tolist() == [ref['row_keep'][i] for i in perm]
+    H.check_shuffled(STAGE, tracked[0][0], tracked[0][1], JOBS[1:3], tracked_refs[0][1:3], per_row)
 
 
 @pytest.mark.parametrize('above', [0, 1], ids=['tables_in_lds', 'tables_in_workspace'])
 def test_trajectory_counts_on_either_side_of_the_lds_limit(above):
-    from waymo_2d_tracking_amd.tracking import dedup as D
-    limit = lds_limit()
-    assert 64 < limit <= 4096
-    offsets, result, jobs, claim = dedup_cases.many_trajectories(limit + above)
-    refs = [dedup_ref.dedup(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    p = D._prepare(packed_for(offsets), [out], jobs, 4)
-    assert p['n_traj'].tolist() == [[limit + above]]
-    for g, ref in zip(D.dedup_tracks(packed_for(offsets), [out], jobs), refs):
-        assert_same(g, ref, out)
-    dev = D.DeviceDedup(packed_for(offsets), [out], jobs)
-    dev.launch()
-    for g, ref in zip(dev.results(), refs):
-        assert_same(g, ref, out)
+    H.check_either_side_of_the_lds_limit(STAGE, above)
 
 
 def test_same_local_index_in_two_jobs_does_not_interfere():
@@ -337,7 +246,7 @@ def test_stitch_then_dedup_then_refine():
     assert_same(deduped, d_ref, s_rows)
     assert deduped['dropped'] == [(30, 21, 4)] and deduped['object_id'].tolist() == [21] * 8
     refined = R.refine_tracks(packed, [deduped], [fill])[0]
-    r_ref = refine_ref.refine(offsets, rows_of(d_ref), fill)
+    r_ref = refine_ref.refine(offsets, arrays(d_ref), fill)
     assert refined['frame'].tolist() == r_ref['frame'] == list(range(10)) and [int(v) for v in refined['object_id']] == r_ref['object_id']
     assert refined['bbox'].tobytes() == np.asarray(r_ref['bbox'], np.float64).tobytes()
 
@@ -353,22 +262,6 @@ def duplicated_detections(dets, every=2, shift=3.0, factor=0.9):
     return list(dets) + extra
 
 
-def _expected_file(path, score_thr, iou_thr, max_age, link, dup, refine):
-    """what track.py has to write: the tracker's rows through the reference stitching, deduplication and refinement - each where its
-    flags are given - and format_tracks"""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    packed = T.pack_streams(T.read_data_file(path, score_thr))
-    out, _ = T.track_packed(packed, iou_thr, max_age, 0)
-    rows = dict((k, out[k]) for k in COLUMNS)
-    if link is not None:
-        rows = dict(rows, object_id=np.asarray(stitch_ref.stitch(packed['stream_frame_offsets'], rows, link)['object_id'], dtype=np.asarray(out['object_id']).dtype))
-    ref = dedup_ref.dedup(packed['stream_frame_offsets'], rows, dup)
-    rows = rows_of(ref)
-    if refine is not None:
-        rows = rows_of(refine_ref.refine(packed['stream_frame_offsets'], rows, refine))
-    return T.format_tracks(packed, rows), ref, len(out['frame'])
-
-
 @pytest.mark.parametrize('fixture,cfg', [('sort_g5_input.json', G5), ('sort_g4_input.json', G4)])
 def test_cli_writes_the_deduplicated_file(golden_dir, tmp_path, fixture, cfg):
     from waymo_2d_tracking_amd.tracking import track, utils as T
@@ -378,12 +271,14 @@ def test_cli_writes_the_deduplicated_file(golden_dir, tmp_path, fixture, cfg):
     with open(path, 'wt') as fp:
         json.dump(duplicated_detections(raw), fp)
     base = ['--input', path, '--max-age=2', '--score-threshold=' + ','.join(map(str, cfg['score']))]
-    runs = [(['--dedup-frames', '3', '--dedup-iou', '0.5'], None, dedup_cases.job(min_frames=3, dup_iou=0.5), None),
+    runs = [(['--dedup-frames', '3', '--dedup-iou', '0.5'], {'dedup': dedup_cases.job(min_frames=3, dup_iou=0.5)}),
             (['--link-gap=4', '--link-iou=0.2', '--dedup-frames=2,2,0,3', '--dedup-iou=0.6', '--dedup-frac=0.75,0.5,0.5,0.5', '--interpolate-gap=2',
-              '--min-track-len=3'], stitch_cases.job(max_link=4, link_iou=0.2),
-             dedup_cases.job(min_frames=[2, 2, 0, 3], dup_iou=0.6, dup_frac=[0.75, 0.5, 0.5, 0.5]), refine_cases.job(max_gap=2, min_len=3))]
-    for k, (flags, link, dup, refine) in enumerate(runs):
-        expected, ref, n_tracked = _expected_file(path, cfg['score'], cfg['iou'], 2, link, dup, refine)
+              '--min-track-len=3'],
+             {'stitch': stitch_cases.job(max_link=4, link_iou=0.2), 'dedup': dedup_cases.job(min_frames=[2, 2, 0, 3], dup_iou=0.6, dup_frac=[0.75, 0.5, 0.5, 0.5]),
+              'refine': refine_cases.job(max_gap=2, min_len=3)})]
+    for k, (flags, passes) in enumerate(runs):
+        expected, refs, tracker_rows, _ = H._expected_file(path, cfg['score'], cfg['iou'], 2, passes)
+        ref, n_tracked = refs['dedup'], len(tracker_rows['frame'])
         print('%s run %d: %d tracked rows, %d tracks dropped' % (fixture, k, n_tracked, sum(ref['n_dropped'])))
         if 'g4' in fixture:
             assert sum(ref['n_dropped']) >= 1 and len(ref['frame']) < n_tracked              # the flags are live on this input
@@ -395,20 +290,8 @@ def test_cli_writes_the_deduplicated_file(golden_dir, tmp_path, fixture, cfg):
 
 
 def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
-    from waymo_2d_tracking_amd.tracking import track, utils as T
-    for fixture, score in (('sort_g5_input.json', '0.95,0.6,1.0,0.9'), ('sort_g4_input.json', '0.3,0.3,1.0,0.2')):
-        path = os.path.join(golden_dir, fixture)
-        flags = ['--input', path, '--max-age=2', '--score-threshold=' + score]
-        T.reset_global_ids(0)
-        untouched = json.dumps(T.track_all(T.read_data_file(path, [float(v) for v in score.split(',')]), [0.01, 0.01, 1.0, 0.0], 2, 0))
-        written = []
-        for i, extra in enumerate(([], ['--python-io'], ['--dedup-frames=0', '--dedup-iou=0.1', '--dedup-frac=0.0'], ['--dedup-frames=0,0,0,0', '--python-io'])):
-            T.reset_global_ids(0)
-            assert track.main(flags + ['--output', str(tmp_path / ('t%d.json' % i))] + extra) == 0
-            written.append((tmp_path / ('t%d.json' % i)).read_text())
-        assert written[1] == untouched and written[0] == written[1] == written[2] == written[3]
-    exp = json.load(open(os.path.join(golden_dir, 'sort_g4_expected_a.json')))['tracks']
-    assert [(r['image_id'], r['category_id'], r['object_id']) for r in json.loads(written[0])] == [(r['image_id'], r['category_id'], r['object_id']) for r in exp]
+    from waymo_2d_tracking_amd.tracking import track
+    H.check_cli_default_flags(golden_dir, tmp_path, (['--dedup-frames=0', '--dedup-iou=0.1', '--dedup-frac=0.0'], ['--dedup-frames=0,0,0,0', '--python-io']))
     args = track.build_parser().parse_args([])
     assert args.dedup_frames == [0] and args.dedup_iou == [0.7] and args.dedup_frac == [0.5] and not track.dedups(args)
 
@@ -416,16 +299,11 @@ def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
 @pytest.fixture(scope='module')
 def sweep_set(tmp_path_factory):
     """synthetic detections with a second, lower-scored detection 3 px beside every second wide box of classes 1 and 2"""
-    from waymo_2d_tracking_amd import synthetic as syn
-    dets, gt_json = syn.make_tracking_json(23, n_segments=1, n_frames=12, n_objects=12, cameras=('FRONT', 'SIDE_LEFT'))
-    dets = duplicated_detections(dets, every=2, shift=3.0, factor=0.95)
-    path = tmp_path_factory.mktemp('dedup_sweep') / 'det.json'
-    path.write_text(json.dumps(dets))
-    return str(path), dets, gt_json
+    return H.sweep_set(tmp_path_factory, 'dedup_sweep', edit=lambda dets: duplicated_detections(dets, every=2, shift=3.0, factor=0.95))
 
 
 def test_sweep_with_dedup_grids_equals_the_references(sweep_set):
-    from waymo_2d_tracking_amd.tracking import evaluate as E, utils as T
+    from waymo_2d_tracking_amd.tracking import evaluate as E
     path, dets, gt_json = sweep_set
     grid = {'score': [0.3, 0.6], 'iou': [0.01], 'max_age': [1, 2], 'min_hits': [0], 'link_gap': [0, 3], 'link_iou': [0.3], 'dedup_frames': [0, 3],
             'dedup_iou': [0.5, 0.7], 'dedup_frac': 0.5, 'gap': [0, 2], 'min_len': [1]}
@@ -433,31 +311,15 @@ def test_sweep_with_dedup_grids_equals_the_references(sweep_set):
     assert len(res['settings']) == 64
     assert res['settings'][13] == {'max_age': 1, 'min_hits': 0, 'score': 0.3, 'iou': 0.01, 'link_gap': 3, 'link_iou': 0.3, 'dedup_frames': 3, 'dedup_iou': 0.5,
                                    'interp_gap': 2, 'min_len': 1}
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    cache, tracked_cache = {}, {}
-
-    def reference(s):
-        key = tuple(sorted(s.items()))
-        if key not in cache:
-            tkey = (s['iou'], s['max_age'], s['min_hits'], s['score'])
-            if tkey not in tracked_cache:
-                tracked_cache[tkey] = T.track_packed(packed, [s['iou']] * 4, s['max_age'], s['min_hits'], [s['score']] * 4)[0]
-            out = dict((k, tracked_cache[tkey][k]) for k in COLUMNS)
-            linked = dict(out, object_id=np.asarray(stitch_ref.stitch(packed['stream_frame_offsets'], out, stitch_cases.job(max_link=s['link_gap'], link_iou=s['link_iou']))['object_id'], np.int64))
-            kept = rows_of(dedup_ref.dedup(packed['stream_frame_offsets'], linked, dedup_cases.job(min_frames=s['dedup_frames'], dup_iou=s['dedup_iou'], dup_frac=0.5)))
-            rows = json.loads(json.dumps(T.format_tracks(packed, rows_of(refine_ref.refine(packed['stream_frame_offsets'], kept, refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len']))))))
-            cache[key] = (mot_ref.evaluate(gt_json, rows)['table'], mot_id_ref.evaluate(gt_json, rows)['table'], hota_ref.evaluate(gt_json, rows))
-        return cache[key]
+    reference = H.sweep_reference(dets, gt_json, lambda s: {
+        'stitch': stitch_cases.job(max_link=s['link_gap'], link_iou=s['link_iou']),
+        'dedup': dedup_cases.job(min_frames=s['dedup_frames'], dup_iou=s['dedup_iou'], dup_frac=0.5),
+        'refine': refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len'])})
     fps = {}
     same = lambda a, b: a == b or (a != a and b != b)
     for k, s in enumerate(res['settings']):
         mot, ident, hota = reference(s)
-        # counts equal, sums and table within the bound of their addition order (the module text of test_gpu_mot_hota.py)
+        # counts equal, sums and table within the bound of their addition order (the module text of mot_support.py)
         assert_hota_equals_reference(res['hota_results'][k], hota)
         for c in E.ALL_CLASSES:
             assert [res['results'][k].table[c][2][f] for f in mot_ref.FIELDS] == [mot[c][2][f] for f in mot_ref.FIELDS], (k, c)

@@ -1,7 +1,7 @@
 """HIP track refinement (csrc/track_refine.hip through tracking/refine.py) against the plain-Python restatement
 tests/refine_ref.py: rows, their order, the trace column, job_row_offsets and frame_row_offsets must be EQUAL bit for bit -
-the unfused interpolation and the order of the score sum are part of the definition."""
-import ctypes as C
+the unfused interpolation and the order of the score sum are part of the definition.  The comparator and
+the bodies shared with the other post-passes are in tests/track_stage_support.py."""
 import json
 import os
 
@@ -11,44 +11,16 @@ import pytest
 import mot_ref
 import refine_cases
 import refine_ref
+import track_stage_support as H
+from track_stage_support import arrays, packed_for
 
 pytestmark = pytest.mark.gpu
 
+STAGE = H.STAGES['refine']
+assert_same = STAGE.assert_same
 TRACKER = [(3, 0, [0.3, 0.2, 1.0, 0.1], [0.01, 0.01, 1.0, 0.0]), (2, 1, [0.5, 0.5, 1.0, 0.5], [0.1, 0.1, 1.0, 0.1])]
 JOBS = [refine_cases.job(max_gap=1, min_len=2), refine_cases.job(max_gap=[2, 1, 0, 3], min_len=[1, 3, 1, 2], score_mode='mean'),
         refine_cases.job(max_gap=3), refine_cases.job(min_len=4, score_mode='mean')]
-
-
-def packed_for(offsets):
-    """the part of a packed detection set that refinement reads, for hand-made slots"""
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
-
-
-def assert_same(got, ref):
-    assert got['frame'].tolist() == ref['frame']
-    assert got['source'].tolist() == ref['source']
-    assert got['category'].tolist() == ref['category']
-    assert [int(v) for v in got['object_id']] == ref['object_id']
-    assert got['bbox'].dtype == np.float64 and got['score'].dtype == np.float64
-    assert got['bbox'].tobytes() == np.asarray(ref['bbox'], np.float64).reshape(-1, 4).tobytes()
-    assert got['score'].tobytes() == np.asarray(ref['score'], np.float64).tobytes()
-    assert got['frame_row_offsets'].tolist() == ref['frame_row_offsets']
-
-
-def lds_limit():
-    from waymo_2d_tracking_amd import _lib
-    n = C.c_int32(0)
-    _lib.lib().wt_refine_tracks_limits(C.byref(n))
-    return n.value
 
 
 @pytest.fixture(scope='module')
@@ -57,12 +29,7 @@ def tracked():
     from waymo_2d_tracking_amd import synthetic as syn
     from waymo_2d_tracking_amd.tracking import utils as T
     dets, _ = syn.make_tracking_json(31, n_segments=1, n_frames=16, n_objects=30, integer_boxes=False)
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
+    packed = T.pack_streams(H.predictions_of(dets))
     outs = [T.track_packed(packed, iou, max_age, min_hits, score)[0] for max_age, min_hits, score, iou in TRACKER]
     return packed, outs
 
@@ -101,16 +68,9 @@ def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tr
     from waymo_2d_tracking_amd.tracking import refine as R
     packed, outs = tracked
     pairs = [(1, 0), (0, 1), (1, 3), (0, 2), (1, 1)]                          # (result, job): results interleaved, one job twice
-    jobs = [dict(JOBS[j], result=r) for r, j in pairs]
-    together = R.refine_tracks(packed, outs, jobs)
-    dev = R.DeviceRefine(packed, outs, jobs)
-    dev.launch()
-    from_dev = dev.results()
+    dev, jobs, from_dev = H.check_jobs_over_results(STAGE, packed, outs, tracked_refs, JOBS, pairs)
     rows = [0]
-    for (r, j), a, b in zip(pairs, together, from_dev):
-        alone = R.refine_tracks(packed, [outs[r]], [JOBS[j]])[0]
-        for other in (alone, a, b):
-            assert_same(other, tracked_refs[r][j])
+    for r, j in pairs:
         rows.append(rows[-1] + len(tracked_refs[r][j]['frame']))
     assert dev.job_row_offsets.cpu().tolist() == rows
     # a second plan + emit on the same buffers gives the same answer (the calls initialise everything they read)
@@ -132,46 +92,22 @@ def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tr
 
 
 def test_unsorted_input_equals_the_sorted_one(tracked, tracked_refs):
-    from waymo_2d_tracking_amd.tracking import refine as R
-    packed, outs = tracked
-    perm = np.random.default_rng(4).permutation(len(outs[0]['frame']))
-    shuffled = dict((k, v[perm]) for k, v in outs[0].items())
-    got = R.refine_tracks(packed, [shuffled], JOBS[:2])
-    for g, j, ref in zip(got, JOBS, tracked_refs[0]):
-        assert_same(g, refine_ref.refine(packed['stream_frame_offsets'], shuffled, j))
+    def per_row(g, ref, perm):
         # the rows are those of the sorted input wherever the order inside a slot does not matter: the filled ones, as a set
         key = lambda r: sorted(zip(r['frame'], r['object_id'], [tuple(b) for b in r['bbox']], r['score']))
         assert key({k: (v.tolist() if k != 'object_id' else [int(x) for x in v]) for k, v in g.items()}) == key(ref)
+    packed, outs = tracked
+    H.check_shuffled(STAGE, packed, outs[0], JOBS[:2], tracked_refs[0][:2], per_row)
 
 
 @pytest.mark.parametrize('name', sorted(refine_cases.CASES))
 def test_case_equals_reference(name):
-    from waymo_2d_tracking_amd.tracking import refine as R
-    offsets, result, jobs, claim = refine_cases.CASES[name]()
-    refs = [refine_ref.refine(offsets, result, j) for j in jobs]
-    claim(refs)
-    got = R.refine_tracks(packed_for(offsets), [arrays(result)], jobs)
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert_same(g, ref)
+    H.check_case(STAGE, name)
 
 
 @pytest.mark.parametrize('above', [0, 1], ids=['tables_in_lds', 'tables_in_workspace'])
 def test_trajectory_counts_on_either_side_of_the_lds_limit(above):
-    from waymo_2d_tracking_amd.tracking import refine as R
-    limit = lds_limit()
-    assert 64 < limit <= 4096
-    offsets, result, jobs, claim = refine_cases.many_trajectories(limit + above)
-    refs = [refine_ref.refine(offsets, result, j) for j in jobs]
-    claim(refs)
-    p = R._prepare(packed_for(offsets), [arrays(result)], jobs, 4)
-    assert p['n_traj'].tolist() == [[limit + above]]
-    for g, ref in zip(R.refine_tracks(packed_for(offsets), [arrays(result)], jobs), refs):
-        assert_same(g, ref)
-    dev = R.DeviceRefine(packed_for(offsets), [arrays(result)], jobs)
-    dev.launch()
-    for g, ref in zip(dev.results(), refs):
-        assert_same(g, ref)
+    H.check_either_side_of_the_lds_limit(STAGE, above)
 
 
 def test_same_local_index_in_two_jobs_does_not_link():
@@ -225,21 +161,13 @@ def test_filling_a_missed_frame_removes_the_false_negative():
         assert (a['gt'], a['tp'], a['fn'], a['fp'], a['idsw']) == (8, 8, 0, 0, 0)
 
 
-def _expected_file(path, score_thr, iou_thr, max_age, job):
-    """what track.py has to write: the tracker's rows through the reference refinement and format_tracks"""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    packed = T.pack_streams(T.read_data_file(path, score_thr))
-    out, _ = T.track_packed(packed, iou_thr, max_age, 0)
-    ref = refine_ref.refine(packed['stream_frame_offsets'], out, job)
-    return T.format_tracks(packed, arrays(ref)), len(out['frame']), ref
-
-
 @pytest.mark.parametrize('fixture,max_age', [('sort_g5_input.json', 1), ('sort_g4_input.json', 3)])
 def test_cli_writes_the_refined_file(golden_dir, tmp_path, fixture, max_age):
     from waymo_2d_tracking_amd.tracking import track, utils as T
     path = os.path.join(golden_dir, fixture)
     score = [0.95, 0.6, 1.0, 0.9] if 'g5' in fixture else [0.3, 0.3, 1.0, 0.2]
-    expected, n_tracked, ref = _expected_file(path, score, [0.01, 0.01, 1.0, 0.0], max_age, refine_cases.job(max_gap=1, min_len=2))
+    expected, refs, out, _ = H._expected_file(path, score, [0.01, 0.01, 1.0, 0.0], max_age, {'refine': refine_cases.job(max_gap=1, min_len=2)})
+    ref, n_tracked = refs['refine'], len(out['frame'])
     if 'g4' in fixture:
         assert any(s < 0 for s in ref['source']) and len([s for s in ref['source'] if s >= 0]) < n_tracked
     flags = ['--input', path, '--max-age=%d' % max_age, '--score-threshold=' + ','.join(map(str, score)), '--interpolate-gap', '1', '--min-track-len', '2']
@@ -251,52 +179,23 @@ def test_cli_writes_the_refined_file(golden_dir, tmp_path, fixture, max_age):
 
 
 def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
-    from waymo_2d_tracking_amd.tracking import track, utils as T
-    for fixture, score in (('sort_g5_input.json', '0.95,0.6,1.0,0.9'), ('sort_g4_input.json', '0.3,0.3,1.0,0.2')):
-        path = os.path.join(golden_dir, fixture)
-        flags = ['--input', path, '--max-age=2', '--score-threshold=' + score]
-        T.reset_global_ids(0)
-        unrefined = json.dumps(T.track_all(T.read_data_file(path, [float(v) for v in score.split(',')]), [0.01, 0.01, 1.0, 0.0], 2, 0))
-        written = []
-        for i, extra in enumerate(([], ['--python-io'], ['--interpolate-gap=0', '--min-track-len=1,1,1,1', '--track-score=keep'])):
-            T.reset_global_ids(0)
-            assert track.main(flags + ['--output', str(tmp_path / ('t%d.json' % i))] + extra) == 0
-            written.append((tmp_path / ('t%d.json' % i)).read_text())
-        assert written[1] == unrefined and written[0] == written[1] == written[2]
-    exp = json.load(open(os.path.join(golden_dir, 'sort_g4_expected_a.json')))['tracks']
-    assert [(r['image_id'], r['category_id'], r['object_id']) for r in json.loads(written[0])] == [(r['image_id'], r['category_id'], r['object_id']) for r in exp]
+    H.check_cli_default_flags(golden_dir, tmp_path, (['--interpolate-gap=0', '--min-track-len=1,1,1,1', '--track-score=keep'],))
 
 
 @pytest.fixture(scope='module')
 def sweep_set(tmp_path_factory):
-    from waymo_2d_tracking_amd import synthetic as syn
-    dets, gt_json = syn.make_tracking_json(23, n_segments=1, n_frames=10, n_objects=12, cameras=('FRONT', 'SIDE_LEFT'))
-    path = tmp_path_factory.mktemp('refine_sweep') / 'det.json'
-    path.write_text(json.dumps(dets))
-    return str(path), dets, gt_json
+    return H.sweep_set(tmp_path_factory, 'refine_sweep', n_frames=10)
 
 
 def test_sweep_with_refinement_grids_equals_the_references(sweep_set):
-    from waymo_2d_tracking_amd.tracking import evaluate as E, utils as T
+    from waymo_2d_tracking_amd.tracking import evaluate as E
     path, dets, gt_json = sweep_set
     grid = {'score': [0.3, 0.6], 'iou': [0.01], 'max_age': [1, 3], 'min_hits': [0], 'gap': [0, 1], 'min_len': [1, 2]}
     res = E.sweep(path, E.load_ground_truth(gt_json), grid)
     assert len(res['settings']) == 16 and res['settings'][1] == {'max_age': 1, 'min_hits': 0, 'score': 0.3, 'iou': 0.01, 'interp_gap': 0, 'min_len': 2}
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    cache = {}
-
-    def reference(max_age, min_hits, score, iou, gap, length):
-        key = (max_age, min_hits, score, iou, gap, length)
-        if key not in cache:
-            out, _ = T.track_packed(packed, [iou] * 4, max_age, min_hits, [score] * 4)
-            ref = refine_ref.refine(packed['stream_frame_offsets'], out, refine_cases.job(max_gap=gap, min_len=length))
-            cache[key] = mot_ref.evaluate(gt_json, json.loads(json.dumps(T.format_tracks(packed, arrays(ref)))))['table']
-        return cache[key]
+    of_setting = H.sweep_reference(dets, gt_json, lambda s: {'refine': refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len'])}, metrics=('mot',))
+    reference = lambda max_age, min_hits, score, iou, gap, length: of_setting(
+        {'max_age': max_age, 'min_hits': min_hits, 'score': score, 'iou': iou, 'interp_gap': gap, 'min_len': length})[0]
     picked = set()
     for lv in (1, 2):
         assert len(res['ranked'][lv]) == 2

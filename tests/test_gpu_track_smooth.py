@@ -2,81 +2,34 @@
 tests/smooth_ref.py: every smoothed value and every pair count must be EQUAL bit for bit (two NaNs count as equal) - the order of
 the distances, the sum of the pair before the product and the unfused accumulation are part of the definition (DESIGN.md
 section 22)."""
-import ctypes as C
 import json
 import os
 
 import numpy as np
 import pytest
 
-import hota_ref
 import mot_ref
 import refine_cases
 import refine_ref
 import smooth_cases
 import smooth_ref
 import stitch_cases
-import stitch_ref
-from test_gpu_mot_hota import assert_equals_reference as assert_hota_equals_reference
+import track_stage_support as H
+from mot_support import assert_hota_equals_reference
+from track_stage_support import G4, G5, arrays, gt_box, packed_for, same_bits, with_boxes
 
 pytestmark = pytest.mark.gpu
 
+STAGE = H.STAGES['smooth']
+assert_same = STAGE.assert_same
 JOBS = [smooth_cases.job(window=2, sigma=1.0), smooth_cases.job(window=[3, 1, 0, 2], sigma=1.5, n_weights=6), smooth_cases.job(window=1, kernel='box'),
         smooth_cases.job(window=3, weights=[1.0, 0.5, 0.25, 0.125])]
-G4 = dict(score=[0.3, 0.3, 1.0, 0.2], iou=[0.01, 0.01, 1.0, 0.0])
-G5 = dict(score=[0.95, 0.6, 1.0, 0.9], iou=[0.01, 0.01, 1.0, 0.0])
-
-
-def packed_for(offsets):
-    """the part of a packed detection set that smoothing reads, for hand-made slots"""
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
-
-
-def same_bits(a, b):
-    """float64 arrays equal bit for bit, two NaNs counting as equal"""
-    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
-    return a.shape == b.shape and bool(((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))).all())
-
-
-def assert_same(got, ref, out):
-    """got: a dict of tracking/smooth.py; ref: smooth_ref.smooth() of `out`"""
-    assert got['bbox'].dtype == np.float64 and got['bbox'].shape == (len(ref['bbox']), 4)
-    assert same_bits(got['bbox'], np.asarray(ref['bbox'], np.float64).reshape(-1, 4))
-    assert got['pairs'].dtype == np.int32 and got['pairs'].tolist() == ref['pairs']
-    for name in ('frame', 'category', 'score', 'object_id'):             # no row is added, removed, moved or otherwise changed
-        assert got[name].dtype == np.asarray(out[name]).dtype and got[name].tobytes() == np.asarray(out[name]).tobytes(), name
-
-
-def with_boxes(out, ref):
-    """the input rows with the reference's boxes: what the writers take"""
-    return dict(out, bbox=np.asarray(ref['bbox'], np.float64).reshape(-1, 4))
-
-
-def lds_limit():
-    from waymo_2d_tracking_amd import _lib
-    n = C.c_int32(0)
-    _lib.lib().wt_smooth_tracks_limits(C.byref(n))
-    return n.value
 
 
 @pytest.fixture(scope='module')
 def tracked(golden_dir):
     """The two tracking fixtures tracked with max_age 2: [(packed, out)], g4 first."""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    sets = []
-    for name, cfg in (('sort_g4_input.json', G4), ('sort_g5_input.json', G5)):
-        packed = T.pack_streams(T.read_data_file(os.path.join(golden_dir, name), cfg['score']))
-        sets.append((packed, T.track_packed(packed, cfg['iou'], 2, 0)[0]))
-    return sets
+    return H.tracked_fixtures(golden_dir)
 
 
 @pytest.fixture(scope='module')
@@ -86,15 +39,7 @@ def tracked_refs(tracked):
 
 @pytest.mark.parametrize('name', sorted(smooth_cases.CASES))
 def test_case_equals_reference(name):
-    from waymo_2d_tracking_amd.tracking import smooth as S
-    offsets, result, jobs, claim = smooth_cases.CASES[name]()
-    refs = [smooth_ref.smooth(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    got = S.smooth_tracks(packed_for(offsets), [out], jobs)
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert_same(g, ref, out)
+    H.check_case(STAGE, name)
 
 
 def test_all_zero_windows_reproduce_the_tracked_sequences(tracked):
@@ -126,65 +71,28 @@ def test_settings_on_the_tracked_sequences_equal_the_reference(tracked, tracked_
 
 
 def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tracked, tracked_refs):
-    import torch
-    from waymo_2d_tracking_amd.tracking import smooth as S, utils as T
+    from waymo_2d_tracking_amd.tracking import utils as T
     packed, out = tracked[0]
     other = T.track_packed(packed, G4['iou'], 3, 0)[0]                    # a second result over the same slots
     outs = [out, other]
     other_refs = [smooth_ref.smooth(packed['stream_frame_offsets'], other, j) for j in JOBS]
-    refs = [tracked_refs[0], other_refs]
     pairs = [(1, 0), (0, 1), (1, 3), (0, 2), (1, 1), (0, 2)]             # (result, job): results interleaved, one job twice
-    jobs = [dict(JOBS[j], result=r) for r, j in pairs]
-    together = S.smooth_tracks(packed, outs, jobs)
-    dev = S.DeviceSmooth(packed, outs, jobs)
-    dev.launch()
-    from_dev = dev.results()
-    for (r, j), a, b in zip(pairs, together, from_dev):
-        alone = S.smooth_tracks(packed, [outs[r]], [JOBS[j]])[0]
-        for got in (alone, a, b):
-            assert_same(got, refs[r][j], outs[r])
+    dev, jobs, from_dev = H.check_jobs_over_results(STAGE, packed, outs, [tracked_refs[0], other_refs], JOBS, pairs)
     assert dev.n_out == 3 * len(out['frame']) + 3 * len(other['frame'])
-    # a second launch on the same buffers gives the same answer (the call initialises everything it reads)
-    dev.launch()
-    for a, b in zip(from_dev, dev.results()):
-        assert same_bits(a['bbox'], b['bbox']) and np.array_equal(a['pairs'], b['pairs'])
-    # a workspace that is too small: WT_ERR_CAPACITY, nothing launched
-    from waymo_2d_tracking_amd import _lib
-    small = S.DeviceSmooth(packed, outs, jobs, workspace_bytes=dev.ws_bytes - 1)
-    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
-        small.launch()
-    torch.cuda.synchronize()
+    H.check_relaunch_and_short_workspace(STAGE, dev, from_dev, packed, outs, jobs,
+                                         lambda a, b: same_bits(a['bbox'], b['bbox']) and np.array_equal(a['pairs'], b['pairs']))
 
 
 def test_unsorted_input_equals_the_sorted_one(tracked, tracked_refs):
-    from waymo_2d_tracking_amd.tracking import smooth as S
-    packed, out = tracked[0]
-    perm = np.random.default_rng(4).permutation(len(out['frame']))
-    shuffled = dict((k, v[perm]) for k, v in out.items())
-    got = S.smooth_tracks(packed, [shuffled], JOBS[1:3])
-    for g, j, ref in zip(got, JOBS[1:3], tracked_refs[0][1:3]):
-        assert_same(g, smooth_ref.smooth(packed['stream_frame_offsets'], shuffled, j), shuffled)
+    def per_row(g, ref, perm):
         # the rows keep the caller's order, and every row gets the box it gets in the sorted input
         assert same_bits(g['bbox'], np.asarray(ref['bbox'], np.float64)[perm]) and g['pairs'].tolist() == [ref['pairs'][i] for i in perm]
+    H.check_shuffled(STAGE, *tracked[0], JOBS[1:3], tracked_refs[0][1:3], per_row)
 
 
 @pytest.mark.parametrize('above', [0, 1], ids=['table_in_lds', 'table_in_workspace'])
 def test_trajectory_counts_on_either_side_of_the_lds_limit(above):
-    from waymo_2d_tracking_amd.tracking import smooth as S
-    limit = lds_limit()
-    assert 64 < limit <= 4096
-    offsets, result, jobs, claim = smooth_cases.many_trajectories(limit + above)
-    refs = [smooth_ref.smooth(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    p = S._prepare(packed_for(offsets), [out], jobs, 4)
-    assert p['n_traj'].tolist() == [[limit + above]]
-    for g, ref in zip(S.smooth_tracks(packed_for(offsets), [out], jobs), refs):
-        assert_same(g, ref, out)
-    dev = S.DeviceSmooth(packed_for(offsets), [out], jobs)
-    dev.launch()
-    for g, ref in zip(dev.results(), refs):
-        assert_same(g, ref, out)
+    H.check_either_side_of_the_lds_limit(STAGE, above)
 
 
 def test_two_jobs_on_one_result_do_not_interfere():
@@ -244,10 +152,6 @@ def test_invalid_input_is_refused():
     assert S._host_call(p, o) == 0
 
 
-def gt_box(o, f):
-    return [100.0 * o + 8.0 * f, 50.0 + 4.0 * f, 40.0, 30.0]
-
-
 def test_smoothing_improves_the_localisation_and_nothing_else():
     """Two objects moving on a line; the hypotheses are the truth with x shifted by +3, -3, +3, ...  Under the box of width 1 the
     interior shifts become -1, +1, ... - a third: every IoU but the ends' rises, so MOTP and LocA rise; matches and ids stay."""
@@ -276,41 +180,21 @@ def test_smoothing_improves_the_localisation_and_nothing_else():
     assert got['object_id'].tobytes() == out['object_id'].tobytes()
 
 
-def as_rows(r):
-    return {'frame': np.asarray(r['frame'], np.int64), 'category': np.asarray(r['category'], np.int32), 'bbox': np.asarray(r['bbox'], np.float64).reshape(-1, 4),
-            'score': np.asarray(r['score'], np.float64), 'object_id': np.asarray(r['object_id'], np.int64)}
-
-
-def _expected_file(path, score_thr, iou_thr, max_age, smooth, link=None, refine=None):
-    """what track.py has to write: the tracker's rows through the reference stitching, the reference refinement, the reference
-    smoothing - in this order - and format_tracks"""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    packed = T.pack_streams(T.read_data_file(path, score_thr))
-    rows, _ = T.track_packed(packed, iou_thr, max_age, 0)
-    n_tracked = len(rows['frame'])
-    if link is not None:
-        ref = stitch_ref.stitch(packed['stream_frame_offsets'], rows, link)
-        rows = dict(rows, object_id=np.asarray(ref['object_id'], dtype=np.asarray(rows['object_id']).dtype))
-    if refine is not None:
-        rows = as_rows(refine_ref.refine(packed['stream_frame_offsets'], rows, refine))
-    ref = smooth_ref.smooth(packed['stream_frame_offsets'], rows, smooth)
-    return T.format_tracks(packed, with_boxes(rows, ref)), ref, n_tracked, len(rows['frame'])
-
-
 @pytest.mark.parametrize('fixture,cfg', [('sort_g5_input.json', G5), ('sort_g4_input.json', G4)])
 def test_cli_writes_the_smoothed_file(golden_dir, tmp_path, fixture, cfg):
     from waymo_2d_tracking_amd.tracking import track, utils as T
     path = os.path.join(golden_dir, fixture)
     base = ['--input', path, '--max-age=2', '--score-threshold=' + ','.join(map(str, cfg['score']))]
-    runs = [(['--smooth-window', '2'], smooth_cases.job(window=2, sigma=1.0), None, None),
+    runs = [(['--smooth-window', '2'], {'smooth': smooth_cases.job(window=2, sigma=1.0)}),
             (['--smooth-window=3,1,0,2', '--smooth-sigma=1.5,1.0,1.0,0.7', '--link-gap=6,6,0,6', '--link-iou=0.1', '--link-motion=linear', '--interpolate-gap=2',
               '--min-track-len=3'],
-             {'window': [3, 1, 0, 2], 'weights': [smooth_ref.gaussian(s, 4) for s in (1.5, 1.0, 1.0, 0.7)]},
-             stitch_cases.job(max_link=[6, 6, 0, 6], link_iou=0.1, motion='linear'), refine_cases.job(max_gap=2, min_len=3)),
-            (['--smooth-window=1', '--smooth-kernel=box', '--smooth-sigma=7', '--interpolate-gap=2'], smooth_cases.job(window=1, kernel='box'), None,
-             refine_cases.job(max_gap=2))]
-    for k, (flags, smooth, link, refine) in enumerate(runs):
-        expected, ref, n_tracked, n_rows = _expected_file(path, cfg['score'], cfg['iou'], 2, smooth, link, refine)
+             {'smooth': {'window': [3, 1, 0, 2], 'weights': [smooth_ref.gaussian(s, 4) for s in (1.5, 1.0, 1.0, 0.7)]},
+              'stitch': stitch_cases.job(max_link=[6, 6, 0, 6], link_iou=0.1, motion='linear'), 'refine': refine_cases.job(max_gap=2, min_len=3)}),
+            (['--smooth-window=1', '--smooth-kernel=box', '--smooth-sigma=7', '--interpolate-gap=2'],
+             {'smooth': smooth_cases.job(window=1, kernel='box'), 'refine': refine_cases.job(max_gap=2)})]
+    for k, (flags, passes) in enumerate(runs):               # the reference passes run in the order of the command line's, not in the one given here
+        expected, refs, out, _ = H._expected_file(path, cfg['score'], cfg['iou'], 2, passes)
+        ref, n_tracked, n_rows = refs['smooth'], len(out['frame']), len(refs['smooth']['bbox'])
         if 'g4' in fixture:                                                              # the flags are live on this input
             assert sum(1 for n in ref['pairs'] if n) > 0 and (k != 1 or n_rows != n_tracked)
         for name, extra in (('native%d.json' % k, []), ('python%d.json' % k, ['--python-io'])):
@@ -328,29 +212,15 @@ def test_the_order_of_the_passes_matters_on_the_fixture(golden_dir):
     rows, _ = T.track_packed(packed, G4['iou'], 2, 0)
     offsets = packed['stream_frame_offsets']
     smooth, refine = smooth_cases.job(window=1, kernel='box'), refine_cases.job(max_gap=2)
-    a = smooth_ref.smooth(offsets, as_rows(refine_ref.refine(offsets, rows, refine)), smooth)
+    a = smooth_ref.smooth(offsets, arrays(refine_ref.refine(offsets, rows, refine)), smooth)
     b = refine_ref.refine(offsets, with_boxes(rows, smooth_ref.smooth(offsets, rows, smooth)), refine)
     assert len(a['bbox']) == len(b['bbox']) and a['bbox'] != [list(r) for r in b['bbox']]
 
 
 def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
-    import sys
-    from waymo_2d_tracking_amd.tracking import track, utils as T
-    sys.modules.pop('waymo_2d_tracking_amd.tracking.smooth', None)
-    for fixture, score in (('sort_g5_input.json', '0.95,0.6,1.0,0.9'), ('sort_g4_input.json', '0.3,0.3,1.0,0.2')):
-        path = os.path.join(golden_dir, fixture)
-        flags = ['--input', path, '--max-age=2', '--score-threshold=' + score]
-        T.reset_global_ids(0)
-        unsmoothed = json.dumps(T.track_all(T.read_data_file(path, [float(v) for v in score.split(',')]), [0.01, 0.01, 1.0, 0.0], 2, 0))
-        written = []
-        for i, extra in enumerate(([], ['--python-io'], ['--smooth-window=0', '--smooth-sigma=2.5', '--smooth-kernel=box'], ['--smooth-window=0,0,0,0', '--python-io'])):
-            T.reset_global_ids(0)
-            assert track.main(flags + ['--output', str(tmp_path / ('t%d.json' % i))] + extra) == 0
-            written.append((tmp_path / ('t%d.json' % i)).read_text())
-        assert written[1] == unsmoothed and written[0] == written[1] == written[2] == written[3]
-    assert 'waymo_2d_tracking_amd.tracking.smooth' not in sys.modules                  # with the defaults the module is not even imported
-    exp = json.load(open(os.path.join(golden_dir, 'sort_g4_expected_a.json')))['tracks']
-    assert [(r['image_id'], r['category_id'], r['object_id']) for r in json.loads(written[0])] == [(r['image_id'], r['category_id'], r['object_id']) for r in exp]
+    from waymo_2d_tracking_amd.tracking import track
+    H.check_cli_default_flags(golden_dir, tmp_path, (['--smooth-window=0', '--smooth-sigma=2.5', '--smooth-kernel=box'], ['--smooth-window=0,0,0,0', '--python-io']),
+                              module='waymo_2d_tracking_amd.tracking.smooth')      # with the defaults the module is not even imported
     args = track.build_parser().parse_args([])
     assert args.smooth_window == [0] and args.smooth_sigma == [1.0] and args.smooth_kernel == 'gaussian' and not track.smooths(args)
 
@@ -358,46 +228,24 @@ def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
 @pytest.fixture(scope='module')
 def sweep_set(tmp_path_factory):
     """detections without classes 1 and 2 in two frames: tracks with holes under max_age 2, so that the refinement axis adds rows"""
-    from waymo_2d_tracking_amd import synthetic as syn
-    dets, gt_json = syn.make_tracking_json(23, n_segments=1, n_frames=12, n_objects=12, cameras=('FRONT', 'SIDE_LEFT'))
-    frames = sorted(set(int(e['image_id'].split('/')[1]) for e in dets))
-    drop = set(frames[4:5]) | set(frames[8:9])
-    dets = [e for e in dets if not (int(e['image_id'].split('/')[1]) in drop and e['category_id'] != 4)]
-    path = tmp_path_factory.mktemp('smooth_sweep') / 'det.json'
-    path.write_text(json.dumps(dets))
-    return str(path), dets, gt_json
+    return H.sweep_set(tmp_path_factory, 'smooth_sweep', edit=lambda dets: H.without_frames(dets, (4, 8)))
 
 
 def test_sweep_with_smooth_grids_equals_the_references(sweep_set):
-    from waymo_2d_tracking_amd.tracking import evaluate as E, utils as T
+    from waymo_2d_tracking_amd.tracking import evaluate as E
     path, dets, gt_json = sweep_set
     grid = {'score': [0.3, 0.6], 'iou': [0.01], 'max_age': [2], 'min_hits': [0], 'gap': [0, 2], 'min_len': [1],
             'smooth_window': [0, 1, 2], 'smooth_sigma': [1.0, 2.0]}
     res = E.sweep(path, E.load_ground_truth(gt_json), grid, hota=True)
     assert len(res['settings']) == 24
     assert res['settings'][9] == {'max_age': 2, 'min_hits': 0, 'score': 0.3, 'iou': 0.01, 'interp_gap': 2, 'min_len': 1, 'smooth_window': 1, 'smooth_sigma': 2.0}
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    offsets = packed['stream_frame_offsets']
-    cache = {}
-
-    def reference(s):
-        key = tuple(sorted(s.items()))
-        if key not in cache:
-            out, _ = T.track_packed(packed, [s['iou']] * 4, s['max_age'], s['min_hits'], [s['score']] * 4)
-            rows = as_rows(refine_ref.refine(offsets, out, refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len'])))
-            smoothed = with_boxes(rows, smooth_ref.smooth(offsets, rows, smooth_cases.job(window=s['smooth_window'], sigma=s['smooth_sigma'])))
-            written = json.loads(json.dumps(T.format_tracks(packed, smoothed)))
-            cache[key] = (mot_ref.evaluate(gt_json, written)['table'], hota_ref.evaluate(gt_json, written))
-        return cache[key]
+    reference = H.sweep_reference(dets, gt_json, lambda s: {'refine': refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len']),
+                                                            'smooth': smooth_cases.job(window=s['smooth_window'], sigma=s['smooth_sigma'])},
+                                  metrics=('mot', 'hota'))
     loca = {}
     for k, s in enumerate(res['settings']):
         mot, hota = reference(s)
-        # counts equal, sums and table within the bound of their addition order (the module text of test_gpu_mot_hota.py)
+        # counts equal, sums and table within the bound of their addition order (the module text of mot_support.py)
         assert_hota_equals_reference(res['hota_results'][k], hota)
         for c in E.ALL_CLASSES:
             assert [res['results'][k].table[c][2][f] for f in mot_ref.FIELDS] == [mot[c][2][f] for f in mot_ref.FIELDS], (k, c)

@@ -1,8 +1,7 @@
 """HIP track splitting (csrc/track_split.hip through tracking/split.py) against the plain-Python restatement tests/split_ref.py:
 object ids, pieces, piece numbers, the tests of every pair, the breaks and the new pieces per stream must be EQUAL bit for bit (a
 NaN test equals a NaN test) - the unfused extrapolations and the operation order of the IoU are part of the definition (DESIGN.md
-section 25)."""
-import ctypes as C
+section 25).  The comparator and the bodies shared with the other post-passes are in tests/track_stage_support.py."""
 import json
 import os
 
@@ -10,83 +9,30 @@ import numpy as np
 import pytest
 
 import dedup_cases
-import dedup_ref
-import hota_ref
 import mot_id_ref
 import mot_ref
 import refine_cases
-import refine_ref
 import smooth_cases
-import smooth_ref
 import split_cases
 import split_ref
 import stitch_cases
 import stitch_ref
-from test_gpu_mot_hota import assert_equals_reference as assert_hota_equals_reference
+import track_stage_support as H
+from mot_support import assert_hota_equals_reference
+from track_stage_support import G4, G5, arrays, packed_for, same_bits, with_ids
 
 pytestmark = pytest.mark.gpu
 
+STAGE = H.STAGES['split']
+assert_same = STAGE.assert_same
 JOBS = [split_cases.job(0.3), split_cases.job([0.5, 0.2, 0.0, 0.3], [0, 1, 1, 0]), split_cases.job(0.3, 1, motion='hold'),
         split_cases.job(0.0, 1, first_new_id=100000)]
-G4 = dict(score=[0.3, 0.3, 1.0, 0.2], iou=[0.01, 0.01, 1.0, 0.0])
-G5 = dict(score=[0.95, 0.6, 1.0, 0.9], iou=[0.01, 0.01, 1.0, 0.0])
-
-
-def packed_for(offsets):
-    """the part of a packed detection set that splitting reads, for hand-made slots"""
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
-
-
-def same_bits(got, ref):
-    """float64 arrays equal bit for bit, any NaN equal to any NaN"""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64).reshape(np.shape(got))
-    nan = np.isnan(got) & np.isnan(ref)
-    return got.dtype == np.float64 and bool((nan | (got.view(np.int64) == ref.view(np.int64))).all())
-
-
-def assert_same(got, ref, out):
-    """got: a dict of tracking/split.py; ref: split_ref.split() of `out`"""
-    assert [int(v) for v in got['object_id']] == ref['object_id']
-    assert got['piece'].dtype == np.int32 and got['piece'].tolist() == ref['piece']
-    assert got['new'].dtype == np.int64 and got['new'].tolist() == ref['new']
-    assert got['test'].shape == (len(ref['test']), 2) and same_bits(got['test'], ref['test'])
-    assert got['breaks'].dtype == np.int32 and got['breaks'].tolist() == ref['breaks']
-    assert got['n_new_pieces'].tolist() == ref['n_new_pieces'] and got['traj_offsets'].tolist() == ref['traj_offsets'] and got['n_new'] == ref['n_new']
-    for name in ('frame', 'category', 'bbox', 'score'):                  # no row is added, removed, moved or changed
-        assert got[name].dtype == np.asarray(out[name]).dtype and got[name].tobytes() == np.asarray(out[name]).tobytes(), name
-    assert got['object_id'].dtype == np.asarray(out['object_id']).dtype
-
-
-def with_ids(out, ref):
-    """the input rows with the reference's object ids: what the later passes and the writers take"""
-    return dict(out, object_id=np.asarray(ref['object_id'], dtype=np.asarray(out['object_id']).dtype))
-
-
-def lds_limit():
-    from waymo_2d_tracking_amd import _lib
-    n = C.c_int32(0)
-    _lib.lib().wt_split_tracks_limits(C.byref(n))
-    return n.value
 
 
 @pytest.fixture(scope='module')
 def tracked(golden_dir):
     """The two tracking fixtures tracked with max_age 2: [(packed, out)], g4 first."""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    sets = []
-    for name, cfg in (('sort_g4_input.json', G4), ('sort_g5_input.json', G5)):
-        packed = T.pack_streams(T.read_data_file(os.path.join(golden_dir, name), cfg['score']))
-        sets.append((packed, T.track_packed(packed, cfg['iou'], 2, 0)[0]))
-    return sets
+    return H.tracked_fixtures(golden_dir)
 
 
 @pytest.fixture(scope='module')
@@ -96,15 +42,7 @@ def tracked_refs(tracked):
 
 @pytest.mark.parametrize('name', sorted(split_cases.CASES))
 def test_case_equals_reference(name):
-    from waymo_2d_tracking_amd.tracking import split as S
-    offsets, result, jobs, claim = split_cases.CASES[name]()
-    refs = [split_ref.split(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    got = S.split_tracks(packed_for(offsets), [out], jobs)
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert_same(g, ref, out)
+    H.check_case(STAGE, name)
 
 
 @pytest.mark.parametrize('n,empty_stream', [(63, False), (64, False), (65, False), (65, True), (257, True)])
@@ -120,26 +58,15 @@ def test_many_trajectories_in_a_slot_and_scans_across_lanes_chunks_and_streams(n
 
 @pytest.mark.parametrize('above', [0, 1], ids=['tables_in_lds', 'tables_in_workspace'])
 def test_trajectory_counts_on_either_side_of_the_lds_limit(above):
-    from waymo_2d_tracking_amd.tracking import split as S
-    limit = lds_limit()
-    assert 64 < limit <= 4096
-    n = limit + above
-    rows = []                                                            # four rows per trajectory; every third jumps after its second
-    for f in range(4):
-        rows += [(f, 1 + k % 4, [4.0 * f + (400.0 if (k % 3 == 0 and f >= 2) else 0.0), 60.0 * k, 50.0, 40.0], 0.9, k) for k in range(n)]
-    result = split_cases.result(rows)
-    jobs = [split_cases.job(0.3, motion='hold'), split_cases.job([0.3, 0.0, 0.3, 0.3], motion='hold')]
-    refs = [split_ref.split([0, 4], result, j) for j in jobs]
-    assert refs[0]['breaks'] == [1 if k % 3 == 0 else 0 for k in range(n)] and refs[0]['n_new'] == (n + 2) // 3
-    out = arrays(result)
-    p = S._prepare(packed_for([0, 4]), [out], jobs, 4)
-    assert p['n_traj'].tolist() == [[n]]
-    for g, ref in zip(S.split_tracks(packed_for([0, 4]), [out], jobs), refs):
-        assert_same(g, ref, out)
-    dev = S.DeviceSplit(packed_for([0, 4]), [out], jobs)
-    dev.launch()
-    for g, ref in zip(dev.results(), refs):
-        assert_same(g, ref, out)
+    def jumping_trajectories(n):
+        rows = []                                                        # four rows per trajectory; every third jumps after its second
+        for f in range(4):
+            rows += [(f, 1 + k % 4, [4.0 * f + (400.0 if (k % 3 == 0 and f >= 2) else 0.0), 60.0 * k, 50.0, 40.0], 0.9, k) for k in range(n)]
+
+        def claim(refs):
+            assert refs[0]['breaks'] == [1 if k % 3 == 0 else 0 for k in range(n)] and refs[0]['n_new'] == (n + 2) // 3
+        return [0, 4], split_cases.result(rows), [split_cases.job(0.3, motion='hold'), split_cases.job([0.3, 0.0, 0.3, 0.3], motion='hold')], claim
+    H.check_either_side_of_the_lds_limit(STAGE, above, make_case=jumping_trajectories)
 
 
 def test_all_off_reproduces_the_tracked_sequences(tracked):
@@ -165,23 +92,14 @@ def test_settings_on_the_tracked_sequences_equal_the_reference(tracked, tracked_
 
 
 def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tracked, tracked_refs):
-    import torch
-    from waymo_2d_tracking_amd.tracking import split as S, utils as T
+    from waymo_2d_tracking_amd.tracking import utils as T
     packed, out = tracked[0]
     other = T.track_packed(packed, G4['iou'], 3, 0)[0]                    # a second result over the same slots
     outs = [out, other]
     other_refs = [split_ref.split(packed['stream_frame_offsets'], other, j) for j in JOBS]
-    refs = [tracked_refs[0], other_refs]
     pairs = [(1, 0), (0, 1), (1, 3), (0, 2), (1, 1), (0, 2)]             # (result, job): results interleaved, one job twice
-    jobs = [dict(JOBS[j], result=r) for r, j in pairs]
-    together = S.split_tracks(packed, outs, jobs)
-    dev = S.DeviceSplit(packed, outs, jobs)
-    dev.launch()
-    from_dev = dev.results()
-    for (r, j), a, b in zip(pairs, together, from_dev):
-        alone = S.split_tracks(packed, [outs[r]], [JOBS[j]])[0]
-        for got in (alone, a, b):
-            assert_same(got, refs[r][j], outs[r])                         # the piece numbers restart with every job
+    # every job equals its reference: the piece numbers restart with every job
+    dev, jobs, from_dev = H.check_jobs_over_results(STAGE, packed, outs, [tracked_refs[0], other_refs], JOBS, pairs)
     # the entries of the result a job does not name are -1 (-1.0)
     p = dev.p
     J = len(jobs)
@@ -193,28 +111,15 @@ def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tr
     assert (piece[0, :rows] == -1).all() and (piece[0, rows:] >= 0).all() and (new[0, :rows] == -1).all() and (test[0, :rows] == -1.0).all()
     assert (breaks[0, :cut] == -1).all() and (breaks[0, cut:] >= 0).all()
     assert (piece[1, rows:] == -1).all() and (piece[1, :rows] >= 0).all() and (breaks[1, cut:] == -1).all() and (test[1, rows:] == -1.0).all()
-    # a second launch on the same buffers gives the same answer (the call initialises everything it reads)
-    dev.launch()
-    for a, b in zip(from_dev, dev.results()):
-        assert all(np.array_equal(a[k], b[k]) for k in ('object_id', 'piece', 'new', 'breaks', 'n_new_pieces')) and same_bits(a['test'], b['test'])
-    # a workspace that is one byte short: WT_ERR_CAPACITY, nothing launched
-    from waymo_2d_tracking_amd import _lib
-    small = S.DeviceSplit(packed, outs, jobs, workspace_bytes=dev.ws_bytes - 1)
-    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
-        small.launch()
-    torch.cuda.synchronize()
+    H.check_relaunch_and_short_workspace(STAGE, dev, from_dev, packed, outs, jobs, lambda a, b: all(
+        np.array_equal(a[k], b[k]) for k in ('object_id', 'piece', 'new', 'breaks', 'n_new_pieces')) and same_bits(a['test'], b['test']))
 
 
 def test_unsorted_input_equals_the_sorted_one(tracked, tracked_refs):
-    from waymo_2d_tracking_amd.tracking import split as S
-    packed, out = tracked[0]
-    perm = np.random.default_rng(4).permutation(len(out['frame']))
-    shuffled = dict((k, v[perm]) for k, v in out.items())
-    got = S.split_tracks(packed, [shuffled], JOBS[1:3])
-    for g, j, ref in zip(got, JOBS[1:3], tracked_refs[0][1:3]):
-        assert_same(g, split_ref.split(packed['stream_frame_offsets'], shuffled, j), shuffled)
+    def per_row(g, ref, perm):
         # the rows keep the caller's order; the pieces are those of the sorted input
         assert g['piece'].tolist() == [ref['piece'][i] for i in perm]
+    H.check_shuffled(STAGE, *tracked[0], JOBS[1:3], tracked_refs[0][1:3], per_row)
 
 
 def swap_chain():
@@ -249,42 +154,20 @@ def test_split_then_stitch_removes_the_identity_swap():
     assert scores[2] == (0, 1.0)                                         # split + stitch: no switch, every identity whole
 
 
-def as_rows(r):
-    return {'frame': np.asarray(r['frame'], np.int64), 'category': np.asarray(r['category'], np.int32), 'bbox': np.asarray(r['bbox'], np.float64).reshape(-1, 4),
-            'score': np.asarray(r['score'], np.float64), 'object_id': np.asarray(r['object_id'], np.int64)}
-
-
-def _expected_file(path, score_thr, iou_thr, max_age, split, link=None, dedup=None, refine=None, smooth=None):
-    """what track.py has to write: the tracker's rows through the reference splitting, stitching, deduplication, refinement and
-    smoothing - in this order - and format_tracks; new ids from the id counter"""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    packed = T.pack_streams(T.read_data_file(path, score_thr))
-    out, births = T.track_packed(packed, iou_thr, max_age, 0)
-    ref = split_ref.split(packed['stream_frame_offsets'], out, dict(split, first_new_id=births + 1))     # a birth is written as the counter + 1
-    rows = with_ids(out, ref)
-    if link is not None:
-        rows = with_ids(rows, stitch_ref.stitch(packed['stream_frame_offsets'], rows, link))
-    if dedup is not None:
-        rows = as_rows(dedup_ref.dedup(packed['stream_frame_offsets'], rows, dedup))
-    if refine is not None:
-        rows = as_rows(refine_ref.refine(packed['stream_frame_offsets'], rows, refine))
-    if smooth is not None:
-        rows = dict(rows, bbox=np.asarray(smooth_ref.smooth(packed['stream_frame_offsets'], rows, smooth)['bbox'], np.float64).reshape(-1, 4))
-    return T.format_tracks(packed, rows), ref, int(np.asarray(out['object_id']).max()) + 1, births
-
-
 @pytest.mark.parametrize('fixture,cfg', [('sort_g5_input.json', G5), ('sort_g4_input.json', G4)])
 def test_cli_writes_the_split_file(golden_dir, tmp_path, fixture, cfg):
     from waymo_2d_tracking_amd.tracking import track, utils as T
     path = os.path.join(golden_dir, fixture)
     base = ['--input', path, '--max-age=2', '--score-threshold=' + ','.join(map(str, cfg['score']))]
-    runs = [(['--split-iou', '0.3'], split_cases.job(0.3), None, None, None, None),
+    runs = [(['--split-iou', '0.3'], {'split': split_cases.job(0.3)}),
             (['--split-iou=0.3,0.3,0,0.5', '--split-gap=1', '--split-motion=hold', '--link-gap=3', '--link-iou=0.3', '--link-motion=linear',
               '--dedup-frames=3', '--dedup-iou=0.5', '--interpolate-gap=2', '--min-track-len=2', '--smooth-window=1', '--smooth-kernel=box'],
-             split_cases.job([0.3, 0.3, 0.0, 0.5], 1, motion='hold'), stitch_cases.job(max_link=3, link_iou=0.3, motion='linear'),
-             dedup_cases.job(min_frames=3, dup_iou=0.5), refine_cases.job(max_gap=2, min_len=2), smooth_cases.job(window=1, kernel='box'))]
-    for k, (flags, split, link, dedup, refine, smooth) in enumerate(runs):     # the second run: all five passes, in their order
-        expected, ref, next_id, births = _expected_file(path, cfg['score'], cfg['iou'], 2, split, link, dedup, refine, smooth)
+             {'split': split_cases.job([0.3, 0.3, 0.0, 0.5], 1, motion='hold'), 'stitch': stitch_cases.job(max_link=3, link_iou=0.3, motion='linear'),
+              'dedup': dedup_cases.job(min_frames=3, dup_iou=0.5), 'refine': refine_cases.job(max_gap=2, min_len=2),
+              'smooth': smooth_cases.job(window=1, kernel='box')})]
+    for k, (flags, passes) in enumerate(runs):                               # the second run: all five passes, in their order; new ids from the id counter
+        expected, refs, out, births = H._expected_file(path, cfg['score'], cfg['iou'], 2, passes)
+        ref, next_id = refs['split'], int(np.asarray(out['object_id']).max()) + 1
         assert next_id <= births + 1                                         # no tracked id lies above the id counter
         if 'g4' in fixture and k == 1:
             assert ref['n_new'] > 0                                          # the flags are live on this input
@@ -297,21 +180,9 @@ def test_cli_writes_the_split_file(golden_dir, tmp_path, fixture, cfg):
 
 
 def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
-    import sys
-    from waymo_2d_tracking_amd.tracking import track, utils as T
-    for fixture, score in (('sort_g5_input.json', '0.95,0.6,1.0,0.9'), ('sort_g4_input.json', '0.3,0.3,1.0,0.2')):
-        path = os.path.join(golden_dir, fixture)
-        flags = ['--input', path, '--max-age=2', '--score-threshold=' + score]
-        T.reset_global_ids(0)
-        unsplit = json.dumps(T.track_all(T.read_data_file(path, [float(v) for v in score.split(',')]), [0.01, 0.01, 1.0, 0.0], 2, 0))
-        written = []
-        sys.modules.pop('waymo_2d_tracking_amd.tracking.split', None)
-        for i, extra in enumerate(([], ['--python-io'], ['--split-iou=0', '--split-gap=0', '--split-motion=hold'], ['--split-iou=0,0,0,0', '--python-io'])):
-            T.reset_global_ids(0)
-            assert track.main(flags + ['--output', str(tmp_path / ('t%d.json' % i))] + extra) == 0
-            written.append((tmp_path / ('t%d.json' % i)).read_text())
-        assert 'waymo_2d_tracking_amd.tracking.split' not in sys.modules        # with the flags off the pass is not even imported
-        assert written[1] == unsplit and written[0] == written[1] == written[2] == written[3]
+    from waymo_2d_tracking_amd.tracking import track
+    H.check_cli_default_flags(golden_dir, tmp_path, (['--split-iou=0', '--split-gap=0', '--split-motion=hold'], ['--split-iou=0,0,0,0', '--python-io']),
+                              module='waymo_2d_tracking_amd.tracking.split')       # with the flags off the pass is not even imported
     args = track.build_parser().parse_args([])
     assert args.split_iou == [0.0] and args.split_gap == [0] and args.split_motion == 'linear' and not track.splits(args)
 
@@ -319,15 +190,11 @@ def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
 @pytest.fixture(scope='module')
 def sweep_set(tmp_path_factory):
     """synthetic detections of one segment and two cameras"""
-    from waymo_2d_tracking_amd import synthetic as syn
-    dets, gt_json = syn.make_tracking_json(23, n_segments=1, n_frames=12, n_objects=12, cameras=('FRONT', 'SIDE_LEFT'))
-    path = tmp_path_factory.mktemp('split_sweep') / 'det.json'
-    path.write_text(json.dumps(dets))
-    return str(path), dets, gt_json
+    return H.sweep_set(tmp_path_factory, 'split_sweep')
 
 
 def test_sweep_with_a_split_grid_equals_the_references(sweep_set):
-    from waymo_2d_tracking_amd.tracking import evaluate as E, utils as T
+    from waymo_2d_tracking_amd.tracking import evaluate as E
     path, dets, gt_json = sweep_set
     grid = {'score': [0.3, 0.6], 'iou': [0.01], 'max_age': [1, 2], 'min_hits': [0], 'split_iou': [0.0, 0.3, 0.9], 'split_gap': 2,
             'link_gap': [0, 2], 'link_iou': [0.3], 'gap': [0, 1], 'min_len': [1]}
@@ -335,27 +202,9 @@ def test_sweep_with_a_split_grid_equals_the_references(sweep_set):
     assert len(res['settings']) == 48
     assert res['settings'][5] == {'max_age': 1, 'min_hits': 0, 'score': 0.3, 'iou': 0.01, 'split_iou': 0.3, 'link_gap': 0, 'link_iou': 0.3,
                                   'interp_gap': 1, 'min_len': 1}
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    cache = {}
-
-    def reference(s):
-        key = tuple(sorted(s.items()))
-        if key not in cache:
-            out, _ = T.track_packed(packed, [s['iou']] * 4, s['max_age'], s['min_hits'], [s['score']] * 4)
-            cut = with_ids(out, split_ref.split(packed['stream_frame_offsets'], out, split_cases.job(s['split_iou'], 2)))
-            linked = with_ids(cut, stitch_ref.stitch(packed['stream_frame_offsets'], cut, stitch_cases.job(max_link=s['link_gap'], link_iou=s['link_iou'])))
-            ref = refine_ref.refine(packed['stream_frame_offsets'], linked, refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len']))
-            rows = json.loads(json.dumps(T.format_tracks(packed, {
-                'frame': np.asarray(ref['frame'], np.int64), 'category': np.asarray(ref['category'], np.int32),
-                'bbox': np.asarray(ref['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(ref['score'], np.float64),
-                'object_id': np.asarray(ref['object_id'], np.int64)})))
-            cache[key] = (mot_ref.evaluate(gt_json, rows)['table'], mot_id_ref.evaluate(gt_json, rows)['table'], hota_ref.evaluate(gt_json, rows))
-        return cache[key]
+    reference = H.sweep_reference(dets, gt_json, lambda s: {'split': split_cases.job(s['split_iou'], 2),
+                                                            'stitch': stitch_cases.job(max_link=s['link_gap'], link_iou=s['link_iou']),
+                                                            'refine': refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len'])})
     same = lambda a, b: a == b or (a != a and b != b)
     hyp_ids = {}
     for k, s in enumerate(res['settings']):

@@ -1,79 +1,33 @@
 """HIP track stitching (csrc/track_stitch.hip through tracking/stitch.py) against the plain-Python restatement
 tests/stitch_ref.py: object ids, pred, root, affinity, the row labels and the link counts must be EQUAL bit for bit - the unfused
 extrapolation, the operation order of the IoU and the strict order of the candidates are part of the definition (DESIGN.md
-section 21)."""
-import ctypes as C
+section 21).  The comparator and the bodies shared with the other post-passes are in tests/track_stage_support.py."""
 import json
 import os
 
 import numpy as np
 import pytest
 
-import hota_ref
-import mot_id_ref
 import mot_ref
 import refine_cases
-import refine_ref
 import stitch_cases
 import stitch_ref
-from test_gpu_mot_hota import assert_equals_reference as assert_hota_equals_reference
+import track_stage_support as H
+from mot_support import assert_hota_equals_reference
+from track_stage_support import G4, G5, arrays, gt_box, packed_for
 
 pytestmark = pytest.mark.gpu
 
+STAGE = H.STAGES['stitch']
+assert_same = STAGE.assert_same
 JOBS = [stitch_cases.job(max_link=2, link_iou=0.3), stitch_cases.job(max_link=[5, 2, 0, 3], link_iou=[0.1, 0.5, 0.3, 0.3], motion='linear'),
         stitch_cases.job(max_link=6, link_iou=0.0), stitch_cases.job(max_link=4, link_iou=0.2, motion='linear')]
-G4 = dict(score=[0.3, 0.3, 1.0, 0.2], iou=[0.01, 0.01, 1.0, 0.0])
-G5 = dict(score=[0.95, 0.6, 1.0, 0.9], iou=[0.01, 0.01, 1.0, 0.0])
-
-
-def packed_for(offsets):
-    """the part of a packed detection set that stitching reads, for hand-made slots"""
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
-
-
-def assert_same(got, ref, out):
-    """got: a dict of tracking/stitch.py; ref: stitch_ref.stitch() of `out`"""
-    assert [int(v) for v in got['object_id']] == ref['object_id']
-    assert got['pred'].tolist() == ref['pred'] and got['root'].tolist() == ref['root']
-    assert got['affinity'].dtype == np.float64 and got['affinity'].tobytes() == np.asarray(ref['affinity'], np.float64).tobytes()
-    assert got['row_root'].tolist() == ref['row_root']
-    assert got['n_links'].tolist() == ref['n_links'] and got['traj_offsets'].tolist() == ref['traj_offsets']
-    assert [(f, t, n, a) for f, t, n, a in got['links']] == ref['links']
-    for name in ('frame', 'category', 'bbox', 'score'):                  # no row is added, removed, moved or changed
-        assert got[name].dtype == np.asarray(out[name]).dtype and got[name].tobytes() == np.asarray(out[name]).tobytes(), name
-    assert got['object_id'].dtype == np.asarray(out['object_id']).dtype
-
-
-def with_ids(out, ref):
-    """the input rows with the reference's object ids: what tracking/refine.py and the writers take"""
-    return dict(out, object_id=np.asarray(ref['object_id'], dtype=np.asarray(out['object_id']).dtype))
-
-
-def lds_limit():
-    from waymo_2d_tracking_amd import _lib
-    n = C.c_int32(0)
-    _lib.lib().wt_stitch_tracks_limits(C.byref(n))
-    return n.value
 
 
 @pytest.fixture(scope='module')
 def tracked(golden_dir):
     """The two tracking fixtures tracked with max_age 2 (a track ends at its third miss): [(packed, out)], g4 first."""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    sets = []
-    for name, cfg in (('sort_g4_input.json', G4), ('sort_g5_input.json', G5)):
-        packed = T.pack_streams(T.read_data_file(os.path.join(golden_dir, name), cfg['score']))
-        sets.append((packed, T.track_packed(packed, cfg['iou'], 2, 0)[0]))
-    return sets
+    return H.tracked_fixtures(golden_dir)
 
 
 @pytest.fixture(scope='module')
@@ -83,15 +37,7 @@ def tracked_refs(tracked):
 
 @pytest.mark.parametrize('name', sorted(stitch_cases.CASES))
 def test_case_equals_reference(name):
-    from waymo_2d_tracking_amd.tracking import stitch as S
-    offsets, result, jobs, claim = stitch_cases.CASES[name]()
-    refs = [stitch_ref.stitch(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    got = S.stitch_tracks(packed_for(offsets), [out], jobs)
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert_same(g, ref, out)
+    H.check_case(STAGE, name)
 
 
 def test_all_zero_max_link_reproduces_the_tracked_sequences(tracked):
@@ -116,23 +62,13 @@ def test_settings_on_the_tracked_sequences_equal_the_reference(tracked, tracked_
 
 
 def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tracked, tracked_refs):
-    import torch
-    from waymo_2d_tracking_amd.tracking import stitch as S, utils as T
+    from waymo_2d_tracking_amd.tracking import utils as T
     packed, out = tracked[0]
     other = T.track_packed(packed, G4['iou'], 3, 0)[0]                    # a second result over the same slots: fewer breaks
     outs = [out, other]
     other_refs = [stitch_ref.stitch(packed['stream_frame_offsets'], other, j) for j in JOBS]
-    refs = [tracked_refs[0], other_refs]
     pairs = [(1, 0), (0, 1), (1, 3), (0, 2), (1, 1), (0, 2)]             # (result, job): results interleaved, one job twice
-    jobs = [dict(JOBS[j], result=r) for r, j in pairs]
-    together = S.stitch_tracks(packed, outs, jobs)
-    dev = S.DeviceStitch(packed, outs, jobs)
-    dev.launch()
-    from_dev = dev.results()
-    for (r, j), a, b in zip(pairs, together, from_dev):
-        alone = S.stitch_tracks(packed, [outs[r]], [JOBS[j]])[0]
-        for got in (alone, a, b):
-            assert_same(got, refs[r][j], outs[r])
+    dev, jobs, from_dev = H.check_jobs_over_results(STAGE, packed, outs, [tracked_refs[0], other_refs], JOBS, pairs)
     # the entries of the result a job does not name: no link, no root
     p = dev.p
     pred = dev.out['pred'].cpu().numpy().reshape(len(jobs), -1)
@@ -140,47 +76,20 @@ def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tr
     split, rows = int(p['traj_offsets'][p['n_streams']]), int(p['set_row_offsets'][1])
     assert (pred[0, :split] == -1).all() and (row_root[0, :rows] == -1).all() and (row_root[0, rows:] >= 0).all()
     assert (pred[1, split:] == -1).all() and (row_root[1, rows:] == -1).all()
-    # a second launch on the same buffers gives the same answer (the call initialises everything it reads)
-    dev.launch()
-    for a, b in zip(from_dev, dev.results()):
-        assert all(np.array_equal(a[k], b[k]) for k in ('object_id', 'pred', 'root', 'affinity', 'row_root', 'n_links')) and a['links'] == b['links']
-    # a workspace that is too small: WT_ERR_CAPACITY, nothing launched
-    from waymo_2d_tracking_amd import _lib
-    small = S.DeviceStitch(packed, outs, jobs, workspace_bytes=dev.ws_bytes - 1)
-    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
-        small.launch()
-    torch.cuda.synchronize()
+    H.check_relaunch_and_short_workspace(STAGE, dev, from_dev, packed, outs, jobs, lambda a, b: all(
+        np.array_equal(a[k], b[k]) for k in ('object_id', 'pred', 'root', 'affinity', 'row_root', 'n_links')) and a['links'] == b['links'])
 
 
 def test_unsorted_input_equals_the_sorted_one(tracked, tracked_refs):
-    from waymo_2d_tracking_amd.tracking import stitch as S
-    packed, out = tracked[0]
-    perm = np.random.default_rng(4).permutation(len(out['frame']))
-    shuffled = dict((k, v[perm]) for k, v in out.items())
-    got = S.stitch_tracks(packed, [shuffled], JOBS[1:3])
-    for g, j, ref in zip(got, JOBS[1:3], tracked_refs[0][1:3]):
-        assert_same(g, stitch_ref.stitch(packed['stream_frame_offsets'], shuffled, j), shuffled)
+    def per_row(g, ref, perm):
         # the rows keep the caller's order, and every row gets the id it gets in the sorted input
         assert [int(v) for v in g['object_id']] == [ref['object_id'][i] for i in perm]
+    H.check_shuffled(STAGE, *tracked[0], JOBS[1:3], tracked_refs[0][1:3], per_row)
 
 
 @pytest.mark.parametrize('above', [0, 1], ids=['tables_in_lds', 'tables_in_workspace'])
 def test_trajectory_counts_on_either_side_of_the_lds_limit(above):
-    from waymo_2d_tracking_amd.tracking import stitch as S
-    limit = lds_limit()
-    assert 64 < limit <= 4096
-    offsets, result, jobs, claim = stitch_cases.many_trajectories(limit + above)
-    refs = [stitch_ref.stitch(offsets, result, j) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    p = S._prepare(packed_for(offsets), [out], jobs, 4)
-    assert p['n_traj'].tolist() == [[limit + above]]
-    for g, ref in zip(S.stitch_tracks(packed_for(offsets), [out], jobs), refs):
-        assert_same(g, ref, out)
-    dev = S.DeviceStitch(packed_for(offsets), [out], jobs)
-    dev.launch()
-    for g, ref in zip(dev.results(), refs):
-        assert_same(g, ref, out)
+    H.check_either_side_of_the_lds_limit(STAGE, above)
 
 
 def test_same_local_index_in_two_jobs_does_not_interfere():
@@ -233,10 +142,6 @@ def test_invalid_input_is_refused():
     assert S._host_call(p, o) == 0
 
 
-def gt_box(o, f):
-    return [100.0 * o + 8.0 * f, 50.0 + 4.0 * f, 40.0, 30.0]
-
-
 def test_stitching_removes_the_identity_switch_and_refining_then_fills_the_hole():
     """Object 1 (class 1) is really hidden in slots 4, 5 - no annotation - and comes back under a new id (n = 3).  Object 2 (class 2)
     stays visible, the detector misses it in slots 4, 5, 6 - three false negatives - and it comes back under a new id (n = 4).
@@ -280,32 +185,18 @@ def test_stitching_removes_the_identity_switch_and_refining_then_fills_the_hole(
     assert len(alone['frame']) == len(out['frame'])
 
 
-def _expected_file(path, score_thr, iou_thr, max_age, link, refine=None):
-    """what track.py has to write: the tracker's rows through the reference stitching, the reference refinement and format_tracks"""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    packed = T.pack_streams(T.read_data_file(path, score_thr))
-    out, _ = T.track_packed(packed, iou_thr, max_age, 0)
-    ref = stitch_ref.stitch(packed['stream_frame_offsets'], out, link)
-    rows = with_ids(out, ref)
-    if refine is not None:
-        r = refine_ref.refine(packed['stream_frame_offsets'], rows, refine)
-        rows = {'frame': np.asarray(r['frame'], np.int64), 'category': np.asarray(r['category'], np.int32), 'bbox': np.asarray(r['bbox'], np.float64).reshape(-1, 4),
-                'score': np.asarray(r['score'], np.float64), 'object_id': np.asarray(r['object_id'], np.int64)}
-    return T.format_tracks(packed, rows), ref, len(out['frame'])
-
-
 @pytest.mark.parametrize('fixture,cfg', [('sort_g5_input.json', G5), ('sort_g4_input.json', G4)])
 def test_cli_writes_the_stitched_file(golden_dir, tmp_path, fixture, cfg):
     from waymo_2d_tracking_amd.tracking import track, utils as T
     path = os.path.join(golden_dir, fixture)
     base = ['--input', path, '--max-age=2', '--score-threshold=' + ','.join(map(str, cfg['score']))]
-    runs = [(['--link-gap', '2', '--link-iou', '0.3'], stitch_cases.job(max_link=2, link_iou=0.3), None),
+    runs = [(['--link-gap', '2', '--link-iou', '0.3'], {'stitch': stitch_cases.job(max_link=2, link_iou=0.3)}),
             (['--link-gap=6,6,0,6', '--link-iou=0.1', '--link-motion=linear', '--interpolate-gap=2', '--min-track-len=3'],
-             stitch_cases.job(max_link=[6, 6, 0, 6], link_iou=0.1, motion='linear'), refine_cases.job(max_gap=2, min_len=3))]
-    for k, (flags, link, refine) in enumerate(runs):
-        expected, ref, n_tracked = _expected_file(path, cfg['score'], cfg['iou'], 2, link, refine)
+             {'stitch': stitch_cases.job(max_link=[6, 6, 0, 6], link_iou=0.1, motion='linear'), 'refine': refine_cases.job(max_gap=2, min_len=3)})]
+    for k, (flags, passes) in enumerate(runs):
+        expected, refs, out, _ = H._expected_file(path, cfg['score'], cfg['iou'], 2, passes)
         if 'g4' in fixture and k == 1:
-            assert sum(ref['n_links']) >= 5 and len(expected) != n_tracked              # the flags are live on this input
+            assert sum(refs['stitch']['n_links']) >= 5 and len(expected) != len(out['frame'])      # the flags are live on this input
         for name, extra in (('native%d.json' % k, []), ('python%d.json' % k, ['--python-io'])):
             T.reset_global_ids(0)
             assert track.main(base + flags + ['--output', str(tmp_path / name)] + extra) == 0
@@ -314,21 +205,8 @@ def test_cli_writes_the_stitched_file(golden_dir, tmp_path, fixture, cfg):
 
 
 def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
-    import sys
-    from waymo_2d_tracking_amd.tracking import track, utils as T
-    for fixture, score in (('sort_g5_input.json', '0.95,0.6,1.0,0.9'), ('sort_g4_input.json', '0.3,0.3,1.0,0.2')):
-        path = os.path.join(golden_dir, fixture)
-        flags = ['--input', path, '--max-age=2', '--score-threshold=' + score]
-        T.reset_global_ids(0)
-        unstitched = json.dumps(T.track_all(T.read_data_file(path, [float(v) for v in score.split(',')]), [0.01, 0.01, 1.0, 0.0], 2, 0))
-        written = []
-        for i, extra in enumerate(([], ['--python-io'], ['--link-gap=0', '--link-iou=0.9', '--link-motion=linear'], ['--link-gap=0,0,0,0', '--python-io'])):
-            T.reset_global_ids(0)
-            assert track.main(flags + ['--output', str(tmp_path / ('t%d.json' % i))] + extra) == 0
-            written.append((tmp_path / ('t%d.json' % i)).read_text())
-        assert written[1] == unstitched and written[0] == written[1] == written[2] == written[3]
-    exp = json.load(open(os.path.join(golden_dir, 'sort_g4_expected_a.json')))['tracks']
-    assert [(r['image_id'], r['category_id'], r['object_id']) for r in json.loads(written[0])] == [(r['image_id'], r['category_id'], r['object_id']) for r in exp]
+    from waymo_2d_tracking_amd.tracking import track
+    H.check_cli_default_flags(golden_dir, tmp_path, (['--link-gap=0', '--link-iou=0.9', '--link-motion=linear'], ['--link-gap=0,0,0,0', '--python-io']))
     args = track.build_parser().parse_args([])
     assert args.link_gap == [0] and args.link_iou == [0.3] and args.link_motion == 'hold' and not track.stitches(args)
 
@@ -337,48 +215,23 @@ def test_cli_default_flags_write_what_they_wrote(golden_dir, tmp_path):
 def sweep_set(tmp_path_factory):
     """detections without classes 1 and 2 in three frames, two of them in a row: the tracks of objects scored below the threshold
     next to them break under max_age 1"""
-    from waymo_2d_tracking_amd import synthetic as syn
-    dets, gt_json = syn.make_tracking_json(23, n_segments=1, n_frames=12, n_objects=12, cameras=('FRONT', 'SIDE_LEFT'))
-    frames = sorted(set(int(e['image_id'].split('/')[1]) for e in dets))
-    drop = set(frames[4:6]) | set(frames[8:9])
-    dets = [e for e in dets if not (int(e['image_id'].split('/')[1]) in drop and e['category_id'] != 4)]
-    path = tmp_path_factory.mktemp('stitch_sweep') / 'det.json'
-    path.write_text(json.dumps(dets))
-    return str(path), dets, gt_json
+    return H.sweep_set(tmp_path_factory, 'stitch_sweep', edit=lambda dets: H.without_frames(dets, (4, 5, 8)))
 
 
 def test_sweep_with_link_grids_equals_the_references(sweep_set):
-    from waymo_2d_tracking_amd.tracking import evaluate as E, utils as T
+    from waymo_2d_tracking_amd.tracking import evaluate as E
     path, dets, gt_json = sweep_set
     grid = {'score': [0.3, 0.6], 'iou': [0.01], 'max_age': [1, 2], 'min_hits': [0], 'link_gap': [0, 3], 'link_iou': [0.1, 0.5], 'gap': [0, 2], 'min_len': [1]}
     res = E.sweep(path, E.load_ground_truth(gt_json), grid, identity=True, hota=True)
     assert len(res['settings']) == 32
     assert res['settings'][5] == {'max_age': 1, 'min_hits': 0, 'score': 0.3, 'iou': 0.01, 'link_gap': 3, 'link_iou': 0.1, 'interp_gap': 2, 'min_len': 1}
-    predictions = {}
-    for e in dets:
-        seg, fr, cam = e['image_id'].split('/')
-        predictions.setdefault(seg, {}).setdefault(cam, {}).setdefault(int(fr), []).append(
-            {'bbox': e['bbox'], 'score': e['score'], 'category_id': e['category_id']})
-    packed = T.pack_streams(predictions)
-    cache = {}
-
-    def reference(s):
-        key = tuple(sorted(s.items()))
-        if key not in cache:
-            out, _ = T.track_packed(packed, [s['iou']] * 4, s['max_age'], s['min_hits'], [s['score']] * 4)
-            linked = with_ids(out, stitch_ref.stitch(packed['stream_frame_offsets'], out, stitch_cases.job(max_link=s['link_gap'], link_iou=s['link_iou'])))
-            ref = refine_ref.refine(packed['stream_frame_offsets'], linked, refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len']))
-            rows = json.loads(json.dumps(T.format_tracks(packed, {
-                'frame': np.asarray(ref['frame'], np.int64), 'category': np.asarray(ref['category'], np.int32),
-                'bbox': np.asarray(ref['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(ref['score'], np.float64),
-                'object_id': np.asarray(ref['object_id'], np.int64)})))
-            cache[key] = (mot_ref.evaluate(gt_json, rows)['table'], mot_id_ref.evaluate(gt_json, rows)['table'], hota_ref.evaluate(gt_json, rows))
-        return cache[key]
+    reference = H.sweep_reference(dets, gt_json, lambda s: {'stitch': stitch_cases.job(max_link=s['link_gap'], link_iou=s['link_iou']),
+                                                            'refine': refine_cases.job(max_gap=s['interp_gap'], min_len=s['min_len'])})
     switches = {}
     same = lambda a, b: a == b or (a != a and b != b)
     for k, s in enumerate(res['settings']):
         mot, ident, hota = reference(s)
-        # counts equal, sums and table within the bound of their addition order (the module text of test_gpu_mot_hota.py)
+        # counts equal, sums and table within the bound of their addition order (the module text of mot_support.py)
         assert_hota_equals_reference(res['hota_results'][k], hota)
         for c in E.ALL_CLASSES:
             assert [res['results'][k].table[c][2][f] for f in mot_ref.FIELDS] == [mot[c][2][f] for f in mot_ref.FIELDS], (k, c)

@@ -1,11 +1,10 @@
 """HIP cross-class track suppression (csrc/track_xclass.hip through tracking/xclass.py) against the plain-Python restatement
 tests/xclass_ref.py: keep, by, match, the row mask, the counts and the surviving rows must be EQUAL bit for bit - no float is
 produced, rows are only selected; the operation order of the measures, the one multiplication of the fraction test and the strict
-strength order are part of the definition."""
-import ctypes as C
+strength order are part of the definition.  The comparator and the bodies shared with the other
+post-passes are in tests/track_stage_support.py."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -16,47 +15,22 @@ import refine_cases
 import refine_ref
 import stitch_cases
 import stitch_ref
+import track_stage_support as H
 import xclass_cases
 import xclass_ref
+from track_stage_support import COLUMNS, G4, G5, arrays, packed_for
 
 pytestmark = pytest.mark.gpu
 
+STAGE = H.STAGES['xclass']
+assert_same = STAGE.assert_same
 NC = xclass_cases.N_CLASSES
 EVERY = lambda v: dict(((a, b), v) for a in range(1, NC + 1) for b in range(a + 1, NC + 1))
 JOBS = [xclass_cases.job(EVERY((1, 0.9, 0.0))),                                               # the loosest: every injected copy is the same object
         xclass_cases.job({(2, 4): (3, 0.9, 0.5), (1, 4): (2, 0.45, 1.0), (1, 2): (1, 0.5, 0.25), (1, 1): (2, 0.7, 0.5)}, prio=[0, 1, 0, 2], measure='iou'),
         xclass_cases.job(EVERY((2, 0.7, 0.5)), prio=[3, 2, 1, 0]),
         xclass_cases.job(EVERY((4, 0.99, 1.0)), measure='iou')]                               # the strictest: IoU of a copy is 0.5
-G4 = dict(score=[0.3, 0.3, 1.0, 0.2], iou=[0.01, 0.01, 1.0, 0.0])
-G5 = dict(score=[0.95, 0.6, 1.0, 0.9], iou=[0.01, 0.01, 1.0, 0.0])
-COLUMNS = ('frame', 'category', 'bbox', 'score', 'object_id')
 KEYS = ('keep', 'by', 'match', 'row_keep', 'n_dropped', 'traj_offsets')
-
-
-def packed_for(offsets):
-    """the part of a packed detection set that the pass reads, for hand-made slots"""
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
-
-
-def assert_same(got, ref, out):
-    """got: a dict of tracking/xclass.py; ref: xclass_ref.xclass() of `out`"""
-    for k in KEYS:
-        assert got[k].tolist() == ref[k], k
-    assert [(int(a), int(b), m) for a, b, m in got['dropped']] == ref['dropped']
-    mask = np.asarray(ref['row_keep'], bool)
-    for name in COLUMNS:                                                  # the surviving rows, in the caller's order, with their input bits
-        want = np.asarray(out[name])[mask]
-        assert got[name].dtype == want.dtype and got[name].shape == want.shape and got[name].tobytes() == want.tobytes(), name
-    assert [int(v) for v in got['frame']] == ref['frame'] and [int(v) for v in got['object_id']] == ref['object_id']
 
 
 def with_other_class_copies(packed, out):
@@ -88,11 +62,8 @@ def with_other_class_copies(packed, out):
 @pytest.fixture(scope='module')
 def tracked(golden_dir):
     """The two tracking fixtures tracked with max_age 2, with injected other-class copies: [(packed, out, copies, the tracker's own rows)], g4 first."""
-    from waymo_2d_tracking_amd.tracking import utils as T
     sets = []
-    for name, cfg in (('sort_g4_input.json', G4), ('sort_g5_input.json', G5)):
-        packed = T.pack_streams(T.read_data_file(os.path.join(golden_dir, name), cfg['score']))
-        plain = T.track_packed(packed, cfg['iou'], 2, 0)[0]
+    for packed, plain in H.tracked_fixtures(golden_dir):
         plain = dict((k, plain[k]) for k in COLUMNS)
         out, copies = with_other_class_copies(packed, plain)
         sets.append((packed, out, copies, plain))
@@ -104,10 +75,11 @@ def tracked_refs(tracked):
     return [[xclass_ref.xclass(packed['stream_frame_offsets'], out, j, NC) for j in JOBS] for packed, out, _, _ in tracked]
 
 
-def on_the_device(X, offsets, result, jobs):
+def on_the_device(offsets, result, jobs):
     """a case whose categories the Python layer refuses: prepared with class 1 everywhere, the case's own categories written into
     the device form's column"""
     import torch
+    from waymo_2d_tracking_amd.tracking import xclass as X
     out = arrays(result)
     dev = X.DeviceXClass(packed_for(offsets), [dict(out, category=np.ones_like(out['category']))], jobs)
     assert (np.diff(out['frame']) >= 0).all()                                                # the rows are in slot order: the column is the case's
@@ -119,15 +91,7 @@ def on_the_device(X, offsets, result, jobs):
 
 @pytest.mark.parametrize('name', sorted(xclass_cases.CASES))
 def test_case_equals_reference(name):
-    from waymo_2d_tracking_amd.tracking import xclass as X
-    offsets, result, jobs, claim = xclass_cases.CASES[name]()
-    refs = [xclass_ref.xclass(offsets, result, j, NC) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    got = on_the_device(X, offsets, result, jobs) if name in xclass_cases.DEVICE_ONLY else X.xclass_tracks(packed_for(offsets), [out], jobs)
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert_same(g, ref, out)
+    H.check_case(STAGE, name, run=on_the_device if name in xclass_cases.DEVICE_ONLY else None)
 
 
 def test_diagonal_jobs_are_the_deduplication_on_the_device():
@@ -188,22 +152,11 @@ def test_settings_on_the_tracked_sequences_equal_the_reference(tracked, tracked_
 
 
 def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tracked, tracked_refs):
-    import torch
-    from waymo_2d_tracking_amd.tracking import xclass as X
     packed, out, _, plain = tracked[0]
     outs = [out, plain, plain]                                           # a second result over the same slots, and a third no job names
     plain_refs = [xclass_ref.xclass(packed['stream_frame_offsets'], plain, j, NC) for j in JOBS]
-    refs = [tracked_refs[0], plain_refs]
     pairs = [(1, 0), (0, 1), (1, 3), (0, 2), (1, 1), (0, 0)]             # (result, job): results interleaved
-    jobs = [dict(JOBS[j], result=r) for r, j in pairs]
-    together = X.xclass_tracks(packed, outs, jobs)
-    dev = X.DeviceXClass(packed, outs, jobs)
-    dev.launch()
-    from_dev = dev.results()
-    for (r, j), a, b in zip(pairs, together, from_dev):
-        alone = X.xclass_tracks(packed, [outs[r]], [JOBS[j]])[0]
-        for got in (alone, a, b):
-            assert_same(got, refs[r][j], outs[r])
+    dev, jobs, from_dev = H.check_jobs_over_results(STAGE, packed, outs, [tracked_refs[0], plain_refs], JOBS, pairs)
     # the entries of the results a job does not name are -1
     p = dev.p
     S = p['n_streams']
@@ -215,51 +168,22 @@ def test_jobs_over_results_in_one_call_equal_single_calls_and_dev_equals_host(tr
     assert (grid['keep'][0, split:third] >= 0).all() and (grid['keep'][1, :split] >= 0).all()
     assert (grid['row_keep'][0, :rows] == -1).all() and (grid['row_keep'][0, rows:rows2] >= 0).all() and (grid['row_keep'][1, rows:] == -1).all()
     assert (grid['row_keep'][:, rows2:] == -1).all() and third < p['n_traj_total']
-    # a second launch on the same buffers gives the same answer (the call initialises everything it reads)
-    dev.launch()
-    for a, b in zip(from_dev, dev.results()):
-        assert all(np.array_equal(a[k], b[k]) for k in ('object_id', 'keep', 'by', 'match', 'row_keep', 'n_dropped')) and a['dropped'] == b['dropped']
-    # a workspace one byte too small: WT_ERR_CAPACITY, nothing launched
-    from waymo_2d_tracking_amd import _lib
-    small = X.DeviceXClass(packed, outs, jobs, workspace_bytes=dev.ws_bytes - 1)
-    with pytest.raises(_lib.WaymoTrackError, match='WT_ERR_CAPACITY'):
-        small.launch()
-    torch.cuda.synchronize()
+    small = H.check_relaunch_and_short_workspace(STAGE, dev, from_dev, packed, outs, jobs, lambda a, b: all(
+        np.array_equal(a[k], b[k]) for k in ('object_id', 'keep', 'by', 'match', 'row_keep', 'n_dropped')) and a['dropped'] == b['dropped'])
     assert (small.out['keep'].cpu().numpy() == 0).all()                  # as allocated: no kernel ran
 
 
 def test_shuffled_input_gives_the_same_decision_per_row(tracked, tracked_refs):
-    from waymo_2d_tracking_amd.tracking import xclass as X
-    packed, out, _, _ = tracked[0]
-    perm = np.random.default_rng(4).permutation(len(out['frame']))
-    shuffled = dict((k, v[perm]) for k, v in out.items())
-    got = X.xclass_tracks(packed, [shuffled], JOBS[1:3])
-    for g, j, ref in zip(got, JOBS[1:3], tracked_refs[0][1:3]):
-        assert_same(g, xclass_ref.xclass(packed['stream_frame_offsets'], shuffled, j, NC), shuffled)
+    def per_row(g, ref, perm):
         # every row gets the decision it gets in the unshuffled input, in the caller's order
         assert g['row_keep'].tolist() == [ref['row_keep'][i] for i in perm]
+    H.check_shuffled(STAGE, tracked[0][0], tracked[0][1], JOBS[1:3], tracked_refs[0][1:3], per_row)
 
 
 @pytest.mark.parametrize('above', [0, 1], ids=['tables_in_lds', 'tables_in_workspace'])
 def test_trajectory_counts_on_either_side_of_the_lds_limit(above):
-    from waymo_2d_tracking_amd import _lib
-    from waymo_2d_tracking_amd.tracking import xclass as X
-    n = C.c_int32(0)
-    _lib.lib().wt_xclass_tracks_limits(C.byref(n))
-    limit = n.value
-    assert limit == 1024
-    offsets, result, jobs, claim = xclass_cases.many_trajectories(limit + above)
-    refs = [xclass_ref.xclass(offsets, result, j, NC) for j in jobs]
-    claim(refs)
-    out = arrays(result)
-    p = X._prepare(packed_for(offsets), [out], jobs, NC)
-    assert p['n_traj'].tolist() == [[limit + above]]
-    for g, ref in zip(X.xclass_tracks(packed_for(offsets), [out], jobs), refs):
-        assert_same(g, ref, out)
-    dev = X.DeviceXClass(packed_for(offsets), [out], jobs)
-    dev.launch()
-    for g, ref in zip(dev.results(), refs):
-        assert_same(g, ref, out)
+    assert H.lds_limit('xclass') == 1024
+    H.check_either_side_of_the_lds_limit(STAGE, above)
 
 
 def test_xclass_removes_the_false_positives_of_the_rider_track():
@@ -321,24 +245,6 @@ def cross_class_detections(dets, every=2, factor=0.95):
     return list(dets) + extra
 
 
-def _expected_file(path, score_thr, iou_thr, max_age, link, dup, xjob, refine):
-    """what track.py has to write: the tracker's rows through the reference passes - each where its flags are given - and format_tracks"""
-    from waymo_2d_tracking_amd.tracking import utils as T
-    packed = T.pack_streams(T.read_data_file(path, score_thr))
-    out, _ = T.track_packed(packed, iou_thr, max_age, 0)
-    rows = dict((k, out[k]) for k in COLUMNS)
-    sfo = packed['stream_frame_offsets']
-    if link is not None:
-        rows = dict(rows, object_id=np.asarray(stitch_ref.stitch(sfo, rows, link)['object_id'], dtype=np.asarray(out['object_id']).dtype))
-    if dup is not None:
-        rows = arrays(dedup_ref.dedup(sfo, rows, dup))
-    ref = xclass_ref.xclass(sfo, rows, xjob, NC)
-    rows = arrays(ref)
-    if refine is not None:
-        rows = arrays(refine_ref.refine(sfo, rows, refine))
-    return T.format_tracks(packed, rows), ref, len(out['frame'])
-
-
 @pytest.mark.parametrize('fixture,cfg', [('sort_g5_input.json', G5), ('sort_g4_input.json', G4)])
 def test_cli_writes_the_file_on_both_io_paths(golden_dir, tmp_path, fixture, cfg):
     from waymo_2d_tracking_amd.tracking import track, utils as T
@@ -348,14 +254,16 @@ def test_cli_writes_the_file_on_both_io_paths(golden_dir, tmp_path, fixture, cfg
     with open(path, 'wt') as fp:
         json.dump(cross_class_detections(raw), fp)
     base = ['--input', path, '--max-age=2', '--score-threshold=' + ','.join(map(str, cfg['score']))]
-    runs = [(['--xclass-pairs', '2:4,1:2', '--xclass-frames', '2'], None, None, xclass_cases.job({(2, 4): (2, 0.7, 0.5), (1, 2): (2, 0.7, 0.5)}), None),
+    runs = [(['--xclass-pairs', '2:4,1:2', '--xclass-frames', '2'], {'xclass': xclass_cases.job({(2, 4): (2, 0.7, 0.5), (1, 2): (2, 0.7, 0.5)})}),
             (['--link-gap=4', '--link-iou=0.2', '--dedup-frames=2,2,0,3', '--dedup-iou=0.6', '--xclass-pairs=1:2,2:4', '--xclass-frames=3,2',
               '--xclass-overlap=0.45,0.9', '--xclass-frac=0.25', '--xclass-measure=iou', '--xclass-prio=1,0,0,2', '--interpolate-gap=2', '--min-track-len=3'],
-             stitch_cases.job(max_link=4, link_iou=0.2), dedup_cases.job(min_frames=[2, 2, 0, 3], dup_iou=0.6),
-             xclass_cases.job({(1, 2): (3, 0.45, 0.25), (2, 4): (2, 0.9, 0.25)}, prio=[1, 0, 0, 2], measure='iou'), refine_cases.job(max_gap=2, min_len=3))]
-    for k, (flags, link, dup, xjob, refine) in enumerate(runs):
-        expected, ref, n_tracked = _expected_file(path, cfg['score'], cfg['iou'], 2, link, dup, xjob, refine)
-        print('%s run %d: %d tracked rows, %d tracks dropped' % (fixture, k, n_tracked, sum(ref['n_dropped'])))
+             {'stitch': stitch_cases.job(max_link=4, link_iou=0.2), 'dedup': dedup_cases.job(min_frames=[2, 2, 0, 3], dup_iou=0.6),
+              'xclass': xclass_cases.job({(1, 2): (3, 0.45, 0.25), (2, 4): (2, 0.9, 0.25)}, prio=[1, 0, 0, 2], measure='iou'),
+              'refine': refine_cases.job(max_gap=2, min_len=3)})]
+    for k, (flags, passes) in enumerate(runs):
+        expected, refs, tracker_rows, _ = H._expected_file(path, cfg['score'], cfg['iou'], 2, passes)
+        ref = refs['xclass']
+        print('%s run %d: %d tracked rows, %d tracks dropped' % (fixture, k, len(tracker_rows['frame']), sum(ref['n_dropped'])))
         if 'g4' in fixture:
             assert sum(ref['n_dropped']) >= 1                                                 # the flags are live on this input
         for name, extra in (('native%d.json' % k, []), ('python%d.json' % k, ['--python-io'])):
@@ -366,25 +274,6 @@ def test_cli_writes_the_file_on_both_io_paths(golden_dir, tmp_path, fixture, cfg
 
 
 def test_cli_default_flags_write_what_they_wrote_without_the_module(golden_dir, tmp_path):
-    from waymo_2d_tracking_amd.tracking import track, utils as T
-    module = 'waymo_2d_tracking_amd.tracking.xclass'
-    kept = sys.modules.pop(module, None)                                  # the tests before this one imported it
-    try:
-        for fixture, score in (('sort_g5_input.json', '0.95,0.6,1.0,0.9'), ('sort_g4_input.json', '0.3,0.3,1.0,0.2')):
-            path = os.path.join(golden_dir, fixture)
-            flags = ['--input', path, '--max-age=2', '--score-threshold=' + score]
-            T.reset_global_ids(0)
-            untouched = json.dumps(T.track_all(T.read_data_file(path, [float(v) for v in score.split(',')]), [0.01, 0.01, 1.0, 0.0], 2, 0))
-            written = []
-            for i, extra in enumerate(([], ['--python-io'], ['--xclass-frames=5', '--xclass-overlap=0.1', '--xclass-prio=0,0,0,1'],
-                                       ['--xclass-pairs=2:4', '--xclass-frames=0', '--python-io'])):
-                T.reset_global_ids(0)
-                assert track.main(flags + ['--output', str(tmp_path / ('t%d.json' % i))] + extra) == 0
-                written.append((tmp_path / ('t%d.json' % i)).read_text())
-            assert written[1] == untouched and written[0] == written[1] == written[2] == written[3]
-            assert module not in sys.modules
-        exp = json.load(open(os.path.join(golden_dir, 'sort_g4_expected_a.json')))['tracks']
-        assert [(r['image_id'], r['category_id'], r['object_id']) for r in json.loads(written[0])] == [(r['image_id'], r['category_id'], r['object_id']) for r in exp]
-    finally:
-        if kept is not None:
-            sys.modules[module] = kept
+    H.check_cli_default_flags(golden_dir, tmp_path, (['--xclass-frames=5', '--xclass-overlap=0.1', '--xclass-prio=0,0,0,1'],
+                                                     ['--xclass-pairs=2:4', '--xclass-frames=0', '--python-io']),
+                              module='waymo_2d_tracking_amd.tracking.xclass')

@@ -6,6 +6,7 @@ import pytest
 
 import dedup_cases
 import xclass_cases
+from track_stage_support import arrays, packed_for
 
 INVALID = 1
 
@@ -16,19 +17,6 @@ def _modules():
     from waymo_2d_tracking_amd import _lib
     from waymo_2d_tracking_amd.tracking import xclass
     return _lib, xclass
-
-
-def packed_for(offsets):
-    offsets = np.asarray(offsets, np.int64)
-    n_streams = offsets.size - 1
-    ids = np.concatenate([np.arange(offsets[s + 1] - offsets[s]) * 10 + 5 for s in range(n_streams)] + [np.zeros(0, np.int64)])
-    return {'stream_frame_offsets': offsets, 'frame_ids': ids.astype(np.int64), 'stream_keys': [('seg%d' % s, 'FRONT') for s in range(n_streams)]}
-
-
-def arrays(result):
-    return {'frame': np.asarray(result['frame'], np.int64), 'category': np.asarray(result['category'], np.int32),
-            'bbox': np.asarray(result['bbox'], np.float64).reshape(-1, 4), 'score': np.asarray(result['score'], np.float64),
-            'object_id': np.asarray(result['object_id'], np.int64)}
 
 
 ROWS = [(0, 2, [0, 0, 5, 5], 0.5, 1), (3, 2, [0, 0, 5, 5], 0.5, 2), (4, 4, [0, 0, 5, 5], 0.5, 3), (4, 2, [9, 9, 5, 5], 0.5, 2)]

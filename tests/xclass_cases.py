@@ -7,9 +7,9 @@ import math
 
 import dedup_ref
 import xclass_ref
-from dedup_cases import by_slot, result, track
+from dedup_cases import track
+from track_cases import N_CLASSES, by_slot, result
 
-N_CLASSES = 4
 NAN, INF = float('nan'), float('inf')
 VEHICLE, PEDESTRIAN, CYCLIST = 1, 2, 4
 
