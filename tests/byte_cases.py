@@ -1,5 +1,5 @@
 """Inputs for the tracker's second association with low-score detections, each built to reach one path of
-sort_streams_byte_kernel / tracker_step_byte.  tests/test_byte_cases.py proves on the CPU, from the reference's counters
+sort_streams_kernel<false, true> / tracker_step_byte.  tests/test_byte_cases.py proves on the CPU, from the reference's counters
 (tests/byte_ref.py 'stats'), that every case reaches the path it is named for; tests/test_gpu_track_byte.py runs them on the GPU.
 
 A case is a dict: packed (tracking/utils.pack_streams layout), max_age, min_hits, score / iou (the high thresholds), low_score /

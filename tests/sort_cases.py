@@ -288,9 +288,9 @@ def munkres_lds_bytes(n_small, n_big):
 
 
 def engine_plan(max_frame_dets, n_streams, max_age=MAX_AGE, n_classes=N_CLASSES):
-    """(floats of cost matrix the tracker keeps in LDS, helper waves launched) - mirrors pick_caps, sort_engine.hip lines 470-474 (the
-    few-tracker budget: what 160 KiB leave next to the bitmaps and the helper job, clamped to [8192, 36864]) with lines 462-468 and
-    476 around them, and the helper decision of run_tracking, lines 502-504.  A change there must show up here as a failing
+    """(floats of cost matrix the tracker keeps in LDS, helper waves launched) - mirrors plan_tracking of sort_engine.hip (the
+    few-tracker budget: what 160 KiB leave next to the bitmaps and the helper job, clamped to [8192, 36864], with the capacities
+    above it and the clamp to the full matrix below it) and the helper decision of run_tracking.  A change there must show up here as a failing
     expectation in tests/test_sort_cases.py, not as a silent loss of coverage."""
     cap_n = max(int(max_frame_dets), 1)
     cap = cap_n * (max_age + 2)

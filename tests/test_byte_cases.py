@@ -62,7 +62,7 @@ def test_contested_cases_are_exact_ties():
 
 
 def test_off_lds_case_is_on_the_global_cost_path():
-    """pick_caps of sort_engine.hip restated: more than 256 trackers keep the 8192-float LDS cost budget; the second cost matrix
+    """plan_tracking of sort_engine.hip restated: more than 256 trackers keep the 8192-float LDS cost budget; the second cost matrix
     of the case has n * ld floats with n = 100 rows and ld = 100 | 1."""
     c = BC.off_lds()
     p = c['packed']

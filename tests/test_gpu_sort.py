@@ -299,7 +299,7 @@ def test_mct_c_abi_order_and_errors():
 @pytest.mark.parametrize('n_segments', [1, 14])
 def test_helper_waves_and_plain_kernel_both_equal_the_oracle(oracle, n_segments):
     """Round 4: with at most 256 trackers the persistent SORT kernel runs with three helper waves per tracker (IoU matrix, Munkres steps
-    1 / 6 split over four waves: sort_streams_kernel<true>); beyond that the plain single-wave instantiation runs.  1 segment = 5 streams x
+    1 / 6 split over four waves: sort_streams_kernel<true, false>); beyond that the plain single-wave instantiation runs.  1 segment = 5 streams x
     4 classes = 20 trackers (helpers), 14 segments = 280 trackers (plain): rows, ids, births and boxes identical to the oracle in both."""
     from waymo_2d_tracking_amd import synthetic as syn
     from waymo_2d_tracking_amd.tracking import utils as T

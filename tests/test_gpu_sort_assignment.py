@@ -94,9 +94,9 @@ def _assert_tracks_equal(out, births, ref):
 @pytest.mark.parametrize('n_trivial', [0, sc.N_TRIVIAL], ids=['alone', 'crowded'])
 @pytest.mark.parametrize('name', sorted(sc.CROWDS))
 def test_track_packed_on_crowd_streams_equals_the_oracle(name, n_trivial):
-    """The persistent kernel on crowd configurations (a) .. (d): alone (4 trackers: sort_streams_kernel<true>, helper waves for the IoU
+    """The persistent kernel on crowd configurations (a) .. (d): alone (4 trackers: sort_streams_kernel<true, false>, helper waves for the IoU
     matrix, step 1 and both forms of step 6, the few-tracker LDS budget) and next to 64 one-box streams (260 trackers:
-    sort_streams_kernel<false>, 8192 floats of cost in LDS).  Every output row, the trivial streams' included, and the birth count.
+    sort_streams_kernel<false, false>, 8192 floats of cost in LDS).  Every output row, the trivial streams' included, and the birth count.
     Configuration (b) runs twice: the helper waves' partial results meet in LDS, a missing barrier shows as a run-to-run difference."""
     cfg = sc.CROWDS[name]
     packed, ref = _reference_tracks(name, n_trivial)

@@ -118,7 +118,6 @@ Workspace carve_ws(void* base, int64_t n_dets, int64_t n_frames, int32_t n_strea
 struct ByteExtra {
     int* rem;                            // per tracker: list positions left unmatched by the first association [cap]
     double* low_score; double* low_iou;  // [C]
-    const double *h_low_score, *h_low_iou;   // the caller's host arrays
     size_t bytes;
 };
 
@@ -128,7 +127,6 @@ ByteExtra carve_byte(void* base, int32_t n_streams, int C, int cap) {
     b.rem = cv.take<int>((size_t)n_streams * (size_t)C * cap);
     b.low_score = cv.take<double>((size_t)C);
     b.low_iou = cv.take<double>((size_t)C);
-    b.h_low_score = b.h_low_iou = nullptr;
     b.bytes = cv.off;
     return b;
 }
@@ -204,13 +202,18 @@ struct StreamEmit {       // utils.py:38-58 clip / drop / confidence clip, into 
 // chip has far more CUs than trackers (config 1 at its stated size: 20 trackers)
 // (HELP = false is the plain single-wave code without a trace of the helper branches: inlined into the hot loops they cost the 64-segment
 //  batch 14 %)
-template <bool HELP>
+// BYTE: the same frame loop with a second association (sort_byte_device.h): a detection is valid from low_score[c] on and high from
+// thr_score[c] on; the class's valid detections are compacted into det_idx as the high ones, then the low ones, both in input order.
+// `lower` counts VALID detections of lower classes, so the intermediate slots d0 + lower .. still hold the class's rows: a frame emits
+// at most |H| + |L| of them.  One wave at every tracker count, batch form only (resume is not read).
+template <bool HELP, bool BYTE>
 __global__ __launch_bounds__(HELP ? kHelpWaves * kWave : kWave) void sort_streams_kernel(
     const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
     const double* __restrict__ h, const double* __restrict__ score, const int32_t* __restrict__ category,
     const int64_t* __restrict__ frame_det_offsets, const int64_t* __restrict__ stream_frame_offsets,
     const double* __restrict__ clip_w, const double* __restrict__ clip_h, int C, int max_age, int min_hits,
-    int cap, int capN, int lds_cost_cap, bool have_cost_g, long long n_slots, Workspace ws, State st, int resume) {
+    int cap, int capN, int lds_cost_cap, bool have_cost_g, long long n_slots, Workspace ws, State st, ByteExtra bx, int resume) {
+    static_assert(!(HELP && BYTE), "the second association runs on one wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const unsigned long long lt = lanemask_lt();
@@ -230,11 +233,12 @@ __global__ __launch_bounds__(HELP ? kHelpWaves * kWave : kWave) void sort_stream
     }
     TrackerMem M = tracker_mem(st, ws, tk, cap, capN, have_cost_g);
     int* det_idx = ws.det_idx + tk * capN;
+    int* rem = BYTE ? bx.rem + tk * cap : nullptr;
     TrackerState S = {0, cap, 0, 0};
     bool created = false;
     long long first_key = -1;
     long long frames_before = 0;                 // frames of this stream consumed by earlier chunks
-    if (resume) {                                // streaming form: continue where the previous chunk stopped
+    if (!BYTE && resume) {                       // streaming form: continue where the previous chunk stopped
         S.n_tracks = st.hdr[tk * 4 + 0]; S.n_free = st.hdr[tk * 4 + 1];
         S.frame_count = st.hdr[tk * 4 + 2]; S.next_local = st.hdr[tk * 4 + 3];
         first_key = st.first_key[tk];
@@ -244,46 +248,68 @@ __global__ __launch_bounds__(HELP ? kHelpWaves * kWave : kWave) void sort_stream
         for (int i = lane; i < cap; i += kWave) M.freel[i] = cap - 1 - i;
     }
     wsync();
-    const double thr_iou = ws.thr_iou[c - 1];
+    const double thr_iou = ws.thr_iou[c - 1], low_iou = BYTE ? bx.low_iou[c - 1] : 0.0, thr_high = BYTE ? ws.thr_score[c - 1] : 0.0;
+    const double* thr_valid = BYTE ? bx.low_score : ws.thr_score;
     const double cw = clip_w ? clip_w[s] : 0.0, ch = clip_h ? clip_h[s] : 0.0;
     const long long f0 = stream_frame_offsets[s], f1 = stream_frame_offsets[s + 1];
     for (long long f = f0; f < f1; ++f) {
         const long long d0 = frame_det_offsets[f], d1 = frame_det_offsets[f + 1];
         // select this class's detections (utils.py:79,86 filters; tracker_sort.py:29-37 bucketing) and count the
-        // valid detections of lower class ids: they own the intermediate slots in front of ours
-        int N = 0, lower = 0, first_pos = -1;
-        bool overflow = false;
+        // valid detections of lower class ids: they own the intermediate slots in front of ours.  BYTE: in the same scan the
+        // high detections go straight to det_idx, the low ones wait in `rem` (free between frames, cap >= capN ints)
+        int N = 0, NL = 0, lower = 0, first_pos = -1;
         for (long long base = d0; base < d1; base += kWave) {
             const long long d = base + lane;
-            bool mine = false, low = false;
+            bool mine = false, low = false, before = false;
             if (d < d1) {
                 const int cat = category[d];
-                const bool valid = (cat >= 1 && cat <= C) && !(w[d] < 1) && !(h[d] < 1) && !(score[d] < ws.thr_score[cat - 1]);
+                const bool valid = (cat >= 1 && cat <= C) && !(w[d] < 1) && !(h[d] < 1) && !(score[d] < thr_valid[cat - 1]);
                 mine = valid && cat == c;
-                low = valid && cat < c;
+                before = valid && cat < c;
+                if constexpr (BYTE) {
+                    const bool high = mine && !(score[d] < thr_high);
+                    low = mine && !high;
+                    mine = high;
+                }
             }
-            const unsigned long long mm = __ballot(mine);
+            const unsigned long long mm = __ballot(mine), ml = BYTE ? __ballot(low) : 0ull;
             if (mine) {
                 const int k = N + __popcll(mm & lt);
                 if (k < capN) det_idx[k] = (int)(d - d0);
             }
-            if (mm && first_pos < 0) first_pos = (int)(base - d0) + __builtin_ctzll(mm);
+            if (BYTE && low) {
+                const int k = NL + __popcll(ml & lt);
+                if (k < capN) rem[k] = (int)(d - d0);
+            }
+            if ((mm | ml) && first_pos < 0) first_pos = (int)(base - d0) + __builtin_ctzll(mm | ml);
             N += __popcll(mm);
-            lower += __popcll(__ballot(low));
+            NL += __popcll(ml);
+            lower += __popcll(__ballot(before));
         }
-        if (N > capN) overflow = true;
+        const bool overflow = N + NL > capN;
         if (!created) {
-            if (N == 0) continue;
+            if (N + NL == 0) continue;
             created = true;
             first_key = ((f - f0 + frames_before) << 32) | (long long)first_pos;
         }
         wsync();
+        if constexpr (BYTE) {                    // the low detections behind the high ones
+            if (!overflow)
+                for (int k = lane; k < NL; k += kWave) det_idx[N + k] = rem[k];
+            wsync();
+        }
         StreamDets dets = {x, y, w, h, det_idx, d0};
         StreamEmit emit = {cw, ch, ws.irow, ws.ifr, ws.isc, ws.ij, ws.ibf, ws.ibk, ws.igid, n_slots, d0 + lower, (int)f, (int)tk};
         int nb = 0, nr = 0;
-        int rc = overflow ? WT_ERR_CAPACITY
-                          : tracker_step<HELP>(M, S, L, lds_cost, lds_cost_cap, dets, N, thr_iou, max_age, min_hits, (int)f,
-                                         0ll, emit, &nb, &nr);
+        int rc = WT_ERR_CAPACITY;
+        if constexpr (BYTE) {
+            if (!overflow)
+                rc = tracker_step_byte(M, S, L, lds_cost, lds_cost_cap, dets, N, NL, rem, thr_iou, low_iou, max_age, min_hits, (int)f,
+                                       0ll, emit, &nb, &nr);
+        } else {
+            if (!overflow)
+                rc = tracker_step<HELP>(M, S, L, lds_cost, lds_cost_cap, dets, N, thr_iou, max_age, min_hits, (int)f, 0ll, emit, &nb, &nr);
+        }
         if (rc) {
             if (lane == 0) atomicMax(ws.err, rc);
             break;
@@ -298,94 +324,6 @@ __global__ __launch_bounds__(HELP ? kHelpWaves * kWave : kWave) void sort_stream
     if constexpr (HELP) {                        // send the helper waves home
         if (lane == 0) L.help->cmd = HELP_EXIT;
         __syncthreads();
-    }
-}
-
-// The same wavefront-per-(stream, class) frame loop with a second association (sort_byte_device.h): a detection is valid from
-// low_score[c] on and high from thr_score[c] on; the class's valid detections are compacted into det_idx as the high ones, then
-// the low ones, both in input order.  `lower` counts VALID detections of lower classes, so the intermediate slots d0 + lower ..
-// still hold the class's rows: a frame emits at most |H| + |L| of them.  Plain one-wave form at every tracker count, batch form only.
-__global__ __launch_bounds__(kWave) void sort_streams_byte_kernel(
-    const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-    const double* __restrict__ h, const double* __restrict__ score, const int32_t* __restrict__ category,
-    const int64_t* __restrict__ frame_det_offsets, const int64_t* __restrict__ stream_frame_offsets,
-    const double* __restrict__ clip_w, const double* __restrict__ clip_h, int C, int max_age, int min_hits,
-    int cap, int capN, int lds_cost_cap, bool have_cost_g, long long n_slots, Workspace ws, State st, ByteExtra bx) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lt = lanemask_lt();
-    const size_t tk = blockIdx.x;
-    const int s = (int)(tk / C);
-    const int c = (int)(tk % C) + 1;
-    float* lds_cost = reinterpret_cast<float*>(smem);
-    const size_t mk_off = (((size_t)lds_cost_cap * sizeof(float) + 15) / 16) * 16;
-    MunkresMem L = munkres_mem(smem + mk_off, capN, cap);
-    TrackerMem M = tracker_mem(st, ws, tk, cap, capN, have_cost_g);
-    int* det_idx = ws.det_idx + tk * capN;
-    int* rem = bx.rem + tk * cap;
-    TrackerState S = {0, cap, 0, 0};
-    bool created = false;
-    long long first_key = -1;
-    for (int i = lane; i < cap; i += kWave) M.freel[i] = cap - 1 - i;
-    wsync();
-    const double thr_iou = ws.thr_iou[c - 1], low_iou = bx.low_iou[c - 1], thr_high = ws.thr_score[c - 1];
-    const double cw = clip_w ? clip_w[s] : 0.0, ch = clip_h ? clip_h[s] : 0.0;
-    const long long f0 = stream_frame_offsets[s], f1 = stream_frame_offsets[s + 1];
-    for (long long f = f0; f < f1; ++f) {
-        const long long d0 = frame_det_offsets[f], d1 = frame_det_offsets[f + 1];
-        // one scan: the high detections go straight to det_idx, the low ones wait in `rem` (free between frames, cap >= capN ints)
-        int NH = 0, NL = 0, lower = 0, first_pos = -1;
-        for (long long base = d0; base < d1; base += kWave) {
-            const long long d = base + lane;
-            bool high = false, low = false, before = false;
-            if (d < d1) {
-                const int cat = category[d];
-                const bool valid = (cat >= 1 && cat <= C) && !(w[d] < 1) && !(h[d] < 1) && !(score[d] < bx.low_score[cat - 1]);
-                const bool mine = valid && cat == c;
-                high = mine && !(score[d] < thr_high);
-                low = mine && !high;
-                before = valid && cat < c;
-            }
-            const unsigned long long mh = __ballot(high), ml = __ballot(low);
-            if (high) {
-                const int k = NH + __popcll(mh & lt);
-                if (k < capN) det_idx[k] = (int)(d - d0);
-            }
-            if (low) {
-                const int k = NL + __popcll(ml & lt);
-                if (k < capN) rem[k] = (int)(d - d0);
-            }
-            if ((mh | ml) && first_pos < 0) first_pos = (int)(base - d0) + __builtin_ctzll(mh | ml);
-            NH += __popcll(mh);
-            NL += __popcll(ml);
-            lower += __popcll(__ballot(before));
-        }
-        const bool overflow = NH + NL > capN;
-        if (!created) {
-            if (NH + NL == 0) continue;
-            created = true;
-            first_key = ((f - f0) << 32) | (long long)first_pos;
-        }
-        wsync();
-        if (!overflow)
-            for (int k = lane; k < NL; k += kWave) det_idx[NH + k] = rem[k];
-        wsync();
-        StreamDets dets = {x, y, w, h, det_idx, d0};
-        StreamEmit emit = {cw, ch, ws.irow, ws.ifr, ws.isc, ws.ij, ws.ibf, ws.ibk, ws.igid, n_slots, d0 + lower, (int)f, (int)tk};
-        int nb = 0, nr = 0;
-        int rc = overflow ? WT_ERR_CAPACITY
-                          : tracker_step_byte(M, S, L, lds_cost, lds_cost_cap, dets, NH, NL, rem, thr_iou, low_iou, max_age, min_hits,
-                                              (int)f, 0ll, emit, &nb, &nr);
-        if (rc) {
-            if (lane == 0) atomicMax(ws.err, rc);
-            break;
-        }
-        if (lane == 0) { ws.cnt[f * C + c - 1] = nr; ws.births[f * C + c - 1] = nb; }
-    }
-    if (lane == 0) {
-        st.first_key[tk] = created ? first_key : -1;
-        st.hdr[tk * 4 + 0] = S.n_tracks; st.hdr[tk * 4 + 1] = S.n_free;
-        st.hdr[tk * 4 + 2] = S.frame_count; st.hdr[tk * 4 + 3] = S.next_local;
     }
 }
 
@@ -561,149 +499,17 @@ __global__ void totals_kernel(const long long* totals, const int* err, int64_t* 
     n_births[0] = totals[1];
 }
 
-int pick_caps(int64_t max_frame_dets, const wt_track_params* p, int* cap, int* capN, int* lds_cost, bool* cost_g,
-              size_t* lds_bytes, int64_t n_streams) {
+int check_params(const wt_track_params* p) {
     if (!p || p->n_classes < 1 || !p->iou_threshold || !p->score_threshold || p->max_age < 0) {
         wt::set_error("bad wt_track_params");
         return WT_ERR_INVALID;
     }
-    const int64_t n = max_frame_dets > 0 ? max_frame_dets : 1;
-    const int64_t c = n * ((int64_t)p->max_age + 2);
-    if (c > (1 << 20)) { wt::set_error("per-tracker capacity too large (%lld tracks)", (long long)c); return WT_ERR_CAPACITY; }
-    *capN = (int)n;
-    *cap = (int)c;
-    const int64_t full = (int64_t)(*capN) * ((*cap) | 1);
-    const size_t mk = wtdev::munkres_lds_bytes(*capN, *cap);
-    if (mk > kLdsMunkresMax) { wt::set_error("frame with %lld detections exceeds the LDS budget of the assignment kernel", (long long)n); return WT_ERR_CAPACITY; }
-    int64_t budget = kLdsCostFloats;
-    if (n_streams > 0 && n_streams * (int64_t)p->n_classes <= 256) {           // few trackers: what the CU's 160 KiB leave next to the bitmaps
-        const int64_t room = ((int64_t)160 * 1024 - 512 - (int64_t)mk - (int64_t)wtdev::help_lds_bytes() - 16) / 4;
-        budget = room < kLdsCostFloatsFew ? room : kLdsCostFloatsFew;
-        if (budget < kLdsCostFloats) budget = kLdsCostFloats;
-    }
-    *lds_cost = (int)(full < budget ? full : budget);
-    *cost_g = full > budget;
-    *lds_bytes = wt::align_up((size_t)(*lds_cost) * sizeof(float), 16) + mk;
     return WT_OK;
 }
 
-}  // namespace
-
-namespace {
-// one tracking pass over the given frames; `st` holds the trackers (fresh when !resume)
-int run_tracking(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
-                 const double* score, const int32_t* category, int64_t n_frames, const int64_t* frame_det_offsets,
-                 int32_t n_streams, const int64_t* stream_frame_offsets, const double* clip_w, const double* clip_h,
-                 const wt_track_params* params, int64_t id_base, int64_t* out_frame, int32_t* out_category,
-                 double* out_bbox4, double* out_score, int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
-                 const Workspace& ws, const State& st, int resume, int cap, int capN, int lds_cost, bool cost_g, size_t lds,
-                 hipStream_t stream, const ByteExtra* byte = nullptr) {
-    const int C = params->n_classes;
-    WT_HIP(hipMemcpyAsync(ws.thr_score, params->score_threshold, sizeof(double) * C, hipMemcpyHostToDevice, stream));
-    WT_HIP(hipMemcpyAsync(ws.thr_iou, params->iou_threshold, sizeof(double) * C, hipMemcpyHostToDevice, stream));
-    WT_HIP(hipMemsetAsync(ws.err, 0, sizeof(int) * 4, stream));
-    WT_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(int) * (size_t)n_frames * C, stream));
-    WT_HIP(hipMemsetAsync(ws.births, 0, sizeof(int) * (size_t)n_frames * C, stream));
-    WT_HIP(hipMemsetAsync(ws.ifr, 0xFF, sizeof(int) * ((size_t)n_dets + 1), stream));
-    WT_HIP(hipMemsetAsync(ws.rcnt, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
-    WT_HIP(hipMemsetAsync(ws.rbirths, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
-    const unsigned n_trackers = (unsigned)n_streams * (unsigned)C;
-    // helper waves (three more waves per tracker for the data-parallel phases) when every tracker can have a CU to itself anyway
-    const bool helpers = !byte && n_trackers <= 256 && (lds + 15) / 16 * 16 + wtdev::help_lds_bytes() <= (size_t)160 * 1024 - 256;
-    if (helpers) lds = (lds + 15) / 16 * 16 + wtdev::help_lds_bytes();
-    if (!byte && lds > 48 * 1024)
-        WT_HIP(hipFuncSetAttribute(helpers ? reinterpret_cast<const void*>(sort_streams_kernel<true>) : reinterpret_cast<const void*>(sort_streams_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (byte) {                                  // second association: the plain one-wave form at every tracker count
-        WT_HIP(hipMemcpyAsync(byte->low_score, byte->h_low_score, sizeof(double) * C, hipMemcpyHostToDevice, stream));
-        WT_HIP(hipMemcpyAsync(byte->low_iou, byte->h_low_iou, sizeof(double) * C, hipMemcpyHostToDevice, stream));
-        if (lds > 48 * 1024)
-            WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sort_streams_byte_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(sort_streams_byte_kernel, dim3(n_trackers), dim3(kWave), lds, stream, x, y, w, h, score, category,
-                           frame_det_offsets, stream_frame_offsets, clip_w, clip_h, C, (int)params->max_age,
-                           (int)params->min_hits, cap, capN, lds_cost, cost_g, (long long)n_dets, ws, st, *byte);
-    } else if (helpers)
-        hipLaunchKernelGGL(sort_streams_kernel<true>, dim3(n_trackers), dim3(kHelpWaves * kWave), lds, stream, x, y, w, h, score, category,
-                           frame_det_offsets, stream_frame_offsets, clip_w, clip_h, C, (int)params->max_age,
-                           (int)params->min_hits, cap, capN, lds_cost, cost_g, (long long)n_dets, ws, st, resume);
-    else
-        hipLaunchKernelGGL(sort_streams_kernel<false>, dim3(n_trackers), dim3(kWave), lds, stream, x, y, w, h, score, category,
-                           frame_det_offsets, stream_frame_offsets, clip_w, clip_h, C, (int)params->max_age,
-                           (int)params->min_hits, cap, capN, lds_cost, cost_g, (long long)n_dets, ws, st, resume);
-    WT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rank_classes_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, (int)n_streams, C, ws, st);
-    const long long ne = (long long)n_frames * C;
-    hipLaunchKernelGGL(gather_ranked_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream,
-                       (long long)n_frames, (int)n_streams, C, stream_frame_offsets, ws);
-    hipLaunchKernelGGL(scan2_kernel, dim3(1), dim3(1024), 0, stream, ne, ws.rcnt, ws.rbirths, ws.totals);
-    if (n_dets > 0)
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n_dets + 255) / 256)), dim3(256), 0, stream,
-                           (long long)n_dets, C, (long long)id_base, ws, st, resume, stream_frame_offsets, out_frame,
-                           out_category, out_bbox4, out_score, out_object_id);
-    if (resume) {
-        hipLaunchKernelGGL(resolve_births_kernel, dim3(n_trackers), dim3(kWave), 0, stream, C, cap, ws, st,
-                           stream_frame_offsets);
-        hipLaunchKernelGGL(advance_streams_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, (int)n_streams, C,
-                           (long long)n_frames, ws, st, stream_frame_offsets);
-    }
-    hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(1), 0, stream, (const long long*)ws.totals, ws.err, n_out_dev,
-                       n_births_dev);
-    WT_HIP(hipGetLastError());
-    return WT_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t wt_track_streams_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets,
-                                  const wt_track_params* params) {
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    if (pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams) != WT_OK) return 0;
-    return carve_ws(nullptr, n_dets, n_frames, n_streams, params->n_classes, cap, capN, cost_g).bytes +
-           carve_state(nullptr, n_streams, params->n_classes, cap).bytes + 256;
-}
-
-int wt_track_streams_dev(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
-                         const double* score, const int32_t* category,
-                         int64_t n_frames, const int64_t* frame_det_offsets,
-                         int32_t n_streams, const int64_t* stream_frame_offsets,
-                         const double* clip_w, const double* clip_h, int64_t max_frame_dets,
-                         const wt_track_params* params, int64_t id_base,
-                         int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
-                         int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
-                         void* workspace, size_t workspace_bytes, void* stream_) {
-    WT_TRY(wt::ensure_device());
-    hipStream_t stream = (hipStream_t)stream_;
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
-    const int C = params->n_classes;
-    if (n_streams <= 0 || n_frames <= 0) {
-        WT_HIP(hipMemsetAsync(n_out_dev, 0, sizeof(int64_t), stream));
-        WT_HIP(hipMemsetAsync(n_births_dev, 0, sizeof(int64_t), stream));
-        return WT_OK;
-    }
-    char* base = wt::align_ptr(workspace);
-    Workspace ws = carve_ws(base, n_dets, n_frames, n_streams, C, cap, capN, cost_g);
-    State st = carve_state(base + ws.bytes, n_streams, C, cap);
-    if (!workspace || workspace_bytes < ws.bytes + st.bytes + 256) {
-        wt::set_error("tracking workspace too small: need %zu bytes, have %zu", ws.bytes + st.bytes + 256, workspace_bytes);
-        return WT_ERR_CAPACITY;
-    }
-    return run_tracking(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
-                        clip_w, clip_h, params, id_base, out_frame, out_category, out_bbox4, out_score, out_object_id,
-                        n_out_dev, n_births_dev, ws, st, 0, cap, capN, lds_cost, cost_g, lds, stream);
-}
-
-/* ---- second association with low-score detections (batch form) ---- */
-}  // extern "C"
-
-namespace {
 // low_score[c] <= score_threshold[c], no NaN, low_iou[c] in [0, 1]
 int check_byte_thresholds(const wt_track_params* p, const double* low_score, const double* low_iou) {
-    if (!p || p->n_classes < 1 || !p->iou_threshold || !p->score_threshold || p->max_age < 0) {
-        wt::set_error("bad wt_track_params");
-        return WT_ERR_INVALID;
-    }
+    WT_TRY(check_params(p));
     if (!low_score || !low_iou) { wt::set_error("low_score_threshold / low_iou_threshold is NULL"); return WT_ERR_INVALID; }
     for (int c = 0; c < p->n_classes; ++c) {
         const double lo = low_score[c], hi = p->score_threshold[c], li = low_iou[c];
@@ -722,19 +528,199 @@ int check_byte_thresholds(const wt_track_params* p, const double* low_score, con
     }
     return WT_OK;
 }
+
+// Every size of one call, computed once: the capacities, the LDS split and the caller's memory carved into Workspace / State / ByteExtra.
+// kBatch carves all of them from `workspace` in this order; kChunk keeps State in the caller's `state` block; kState is the entry points
+// that touch the state block alone.  A null block yields offsets only, for the *_workspace / *_bytes queries.
+enum Form { kBatch, kChunk, kState };
+struct Plan {
+    int C, cap, capN;
+    int lds_cost;                        // floats of cost matrix in LDS ...
+    bool cost_g;                         // ... and whether larger matrices need the global one
+    size_t lds;                          // dynamic LDS of the single-wave kernel
+    Workspace ws;
+    State st;
+    ByteExtra bx;                        // all null without a second association
+    const double *low_score, *low_iou;   // the caller's host arrays of the second association, null without one
+    size_t ws_need, st_need;             // what `workspace` / `state` must hold, alignment slack included
+};
+
+int plan_tracking(Plan& pl, int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets, const wt_track_params* p,
+                  const double* low_score, const double* low_iou, Form form, void* workspace, void* state) {
+    WT_TRY(check_params(p));
+    const int64_t n = max_frame_dets > 0 ? max_frame_dets : 1;
+    const int64_t c = n * ((int64_t)p->max_age + 2);
+    if (c > (1 << 20)) { wt::set_error("per-tracker capacity too large (%lld tracks)", (long long)c); return WT_ERR_CAPACITY; }
+    pl.C = p->n_classes;
+    pl.capN = (int)n;
+    pl.cap = (int)c;
+    const int64_t full = (int64_t)pl.capN * (pl.cap | 1);
+    const size_t mk = wtdev::munkres_lds_bytes(pl.capN, pl.cap);
+    if (mk > kLdsMunkresMax) { wt::set_error("frame with %lld detections exceeds the LDS budget of the assignment kernel", (long long)n); return WT_ERR_CAPACITY; }
+    int64_t budget = kLdsCostFloats;
+    if (n_streams > 0 && n_streams * (int64_t)p->n_classes <= 256) {           // few trackers: what the CU's 160 KiB leave next to the bitmaps
+        const int64_t room = ((int64_t)160 * 1024 - 512 - (int64_t)mk - (int64_t)wtdev::help_lds_bytes() - 16) / 4;
+        budget = room < kLdsCostFloatsFew ? room : kLdsCostFloatsFew;
+        if (budget < kLdsCostFloats) budget = kLdsCostFloats;
+    }
+    pl.lds_cost = (int)(full < budget ? full : budget);
+    pl.cost_g = full > budget;
+    pl.lds = wt::align_up((size_t)pl.lds_cost * sizeof(float), 16) + mk;
+    pl.low_score = low_score;
+    pl.low_iou = low_iou;
+    if (n_streams <= 0) workspace = state = nullptr;                    // nothing to carve: every caller refuses or returns before it uses a pointer
+    char* base = workspace ? wt::align_ptr(workspace) : nullptr;
+    auto at = [&](size_t off) { return base ? base + off : nullptr; };
+    pl.ws = form == kState ? Workspace{} : carve_ws(base, n_dets, n_frames, n_streams, pl.C, pl.cap, pl.capN, pl.cost_g);
+    size_t off = pl.ws.bytes;
+    pl.st = carve_state(form == kBatch ? at(off) : (state ? wt::align_ptr(state) : nullptr), n_streams, pl.C, pl.cap);
+    if (form == kBatch) off += pl.st.bytes;
+    pl.bx = ByteExtra{};
+    if (low_score) { pl.bx = carve_byte(at(off), n_streams, pl.C, pl.cap); off += pl.bx.bytes; }
+    pl.ws_need = off + 256;
+    pl.st_need = pl.st.bytes + 256;
+    return WT_OK;
+}
+
+int fits(const char* what, const void* block, size_t have, size_t need) {
+    if (block && have >= need) return WT_OK;
+    wt::set_error("%s too small: need %zu bytes, have %zu", what, need, have);
+    return WT_ERR_CAPACITY;
+}
+
+// what the C entry points receive (device pointers): the detection columns with their two CSR offset arrays, and the output columns
+struct DetsIn {
+    int64_t n_dets;
+    const double *x, *y, *w, *h, *score;
+    const int32_t* category;
+    int64_t n_frames;
+    const int64_t* frame_det_offsets;
+    int32_t n_streams;
+    const int64_t* stream_frame_offsets;
+    const double *clip_w, *clip_h;
+};
+struct RowsOut {
+    int64_t* frame; int32_t* category; double* bbox4; double* score; int64_t* object_id;
+    int64_t *n_out_dev, *n_births_dev;
+};
+
+int no_rows(const RowsOut& out, hipStream_t stream) {
+    WT_HIP(hipMemsetAsync(out.n_out_dev, 0, sizeof(int64_t), stream));
+    WT_HIP(hipMemsetAsync(out.n_births_dev, 0, sizeof(int64_t), stream));
+    return WT_OK;
+}
+
+template <bool HELP, bool BYTE>
+int launch_streams(const DetsIn& in, const wt_track_params* params, const Plan& pl, size_t lds, int resume, hipStream_t stream) {
+    const auto kernel = sort_streams_kernel<HELP, BYTE>;
+    if (lds > 48 * 1024)
+        WT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)in.n_streams * (unsigned)pl.C), dim3(HELP ? kHelpWaves * kWave : kWave), lds, stream,
+                       in.x, in.y, in.w, in.h, in.score, in.category, in.frame_det_offsets, in.stream_frame_offsets, in.clip_w,
+                       in.clip_h, pl.C, (int)params->max_age, (int)params->min_hits, pl.cap, pl.capN, pl.lds_cost, pl.cost_g,
+                       (long long)in.n_dets, pl.ws, pl.st, pl.bx, resume);
+    return WT_OK;
+}
+
+// one tracking pass over the given frames; pl.st holds the trackers (fresh when !resume)
+int run_tracking(const DetsIn& in, const wt_track_params* params, int64_t id_base, const RowsOut& out, const Plan& pl, int resume,
+                 hipStream_t stream) {
+    const Workspace& ws = pl.ws;
+    const State& st = pl.st;
+    const int C = pl.C;
+    const int64_t n_dets = in.n_dets, n_frames = in.n_frames;
+    const int32_t n_streams = in.n_streams;
+    WT_HIP(hipMemcpyAsync(ws.thr_score, params->score_threshold, sizeof(double) * C, hipMemcpyHostToDevice, stream));
+    WT_HIP(hipMemcpyAsync(ws.thr_iou, params->iou_threshold, sizeof(double) * C, hipMemcpyHostToDevice, stream));
+    WT_HIP(hipMemsetAsync(ws.err, 0, sizeof(int) * 4, stream));
+    WT_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(int) * (size_t)n_frames * C, stream));
+    WT_HIP(hipMemsetAsync(ws.births, 0, sizeof(int) * (size_t)n_frames * C, stream));
+    WT_HIP(hipMemsetAsync(ws.ifr, 0xFF, sizeof(int) * ((size_t)n_dets + 1), stream));
+    WT_HIP(hipMemsetAsync(ws.rcnt, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
+    WT_HIP(hipMemsetAsync(ws.rbirths, 0, sizeof(long long) * ((size_t)n_frames * C + 1), stream));
+    if (pl.low_score) {
+        WT_HIP(hipMemcpyAsync(pl.bx.low_score, pl.low_score, sizeof(double) * C, hipMemcpyHostToDevice, stream));
+        WT_HIP(hipMemcpyAsync(pl.bx.low_iou, pl.low_iou, sizeof(double) * C, hipMemcpyHostToDevice, stream));
+    }
+    const unsigned n_trackers = (unsigned)n_streams * (unsigned)C;
+    // helper waves (three more waves per tracker for the data-parallel phases) when every tracker can have a CU to itself anyway;
+    // the second association is the plain one-wave form at every tracker count
+    const size_t lds_help = (pl.lds + 15) / 16 * 16 + wtdev::help_lds_bytes();
+    const bool helpers = !pl.low_score && n_trackers <= 256 && lds_help <= (size_t)160 * 1024 - 256;
+    WT_TRY((pl.low_score ? launch_streams<false, true>(in, params, pl, pl.lds, 0, stream)
+            : helpers    ? launch_streams<true, false>(in, params, pl, lds_help, resume, stream)
+                         : launch_streams<false, false>(in, params, pl, pl.lds, resume, stream)));
+    WT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rank_classes_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, (int)n_streams, C, ws, st);
+    const long long ne = (long long)n_frames * C;
+    hipLaunchKernelGGL(gather_ranked_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream,
+                       (long long)n_frames, (int)n_streams, C, in.stream_frame_offsets, ws);
+    hipLaunchKernelGGL(scan2_kernel, dim3(1), dim3(1024), 0, stream, ne, ws.rcnt, ws.rbirths, ws.totals);
+    if (n_dets > 0)
+        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n_dets + 255) / 256)), dim3(256), 0, stream,
+                           (long long)n_dets, C, (long long)id_base, ws, st, resume, in.stream_frame_offsets, out.frame,
+                           out.category, out.bbox4, out.score, out.object_id);
+    if (resume) {
+        hipLaunchKernelGGL(resolve_births_kernel, dim3(n_trackers), dim3(kWave), 0, stream, C, pl.cap, ws, st,
+                           in.stream_frame_offsets);
+        hipLaunchKernelGGL(advance_streams_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, (int)n_streams, C,
+                           (long long)n_frames, ws, st, in.stream_frame_offsets);
+    }
+    hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(1), 0, stream, (const long long*)ws.totals, ws.err, out.n_out_dev,
+                       out.n_births_dev);
+    WT_HIP(hipGetLastError());
+    return WT_OK;
+}
+
+// the batch form on device pointers: wt_track_streams_dev (low_score == nullptr) or wt_track_streams_byte_dev (thresholds checked)
+int track_streams_dev(const DetsIn& in, int64_t max_frame_dets, const wt_track_params* params, const double* low_score,
+                      const double* low_iou, int64_t id_base, const RowsOut& out, void* workspace, size_t workspace_bytes,
+                      hipStream_t stream) {
+    WT_TRY(wt::ensure_device());
+    Plan pl;
+    WT_TRY(plan_tracking(pl, in.n_dets, in.n_frames, in.n_streams, max_frame_dets, params, low_score, low_iou, kBatch, workspace, nullptr));
+    if (in.n_streams <= 0 || in.n_frames <= 0) return no_rows(out, stream);
+    WT_TRY(fits("tracking workspace", workspace, workspace_bytes, pl.ws_need));
+    return run_tracking(in, params, id_base, out, pl, 0, stream);
+}
+
+// 0 when the parameters are refused
+size_t streams_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets, const wt_track_params* params,
+                         const double* low_score, const double* low_iou, Form form) {
+    Plan pl;
+    return plan_tracking(pl, n_dets, n_frames, n_streams, max_frame_dets, params, low_score, low_iou, form, nullptr, nullptr) == WT_OK ? pl.ws_need : 0;
+}
+
 }  // namespace
 
 extern "C" {
 
+size_t wt_track_streams_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets,
+                                  const wt_track_params* params) {
+    return streams_workspace(n_dets, n_frames, n_streams, max_frame_dets, params, nullptr, nullptr, kBatch);
+}
+
+int wt_track_streams_dev(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
+                         const double* score, const int32_t* category,
+                         int64_t n_frames, const int64_t* frame_det_offsets,
+                         int32_t n_streams, const int64_t* stream_frame_offsets,
+                         const double* clip_w, const double* clip_h, int64_t max_frame_dets,
+                         const wt_track_params* params, int64_t id_base,
+                         int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
+                         int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
+                         void* workspace, size_t workspace_bytes, void* stream_) {
+    return track_streams_dev({n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets, clip_w, clip_h},
+                             max_frame_dets, params, nullptr, nullptr, id_base,
+                             {out_frame, out_category, out_bbox4, out_score, out_object_id, n_out_dev, n_births_dev},
+                             workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+/* ---- second association with low-score detections (batch form) ---- */
 size_t wt_track_streams_byte_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets,
                                        const wt_track_params* params, const double* low_score_threshold,
                                        const double* low_iou_threshold) {
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
     if (check_byte_thresholds(params, low_score_threshold, low_iou_threshold) != WT_OK) return 0;
-    if (pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams) != WT_OK) return 0;
-    return carve_ws(nullptr, n_dets, n_frames, n_streams, params->n_classes, cap, capN, cost_g).bytes +
-           carve_state(nullptr, n_streams, params->n_classes, cap).bytes +
-           carve_byte(nullptr, n_streams, params->n_classes, cap).bytes + 256;
+    return streams_workspace(n_dets, n_frames, n_streams, max_frame_dets, params, low_score_threshold, low_iou_threshold, kBatch);
 }
 
 int wt_track_streams_byte_dev(int64_t n_dets, const double* x, const double* y, const double* w, const double* h,
@@ -747,63 +733,37 @@ int wt_track_streams_byte_dev(int64_t n_dets, const double* x, const double* y, 
                               int64_t* out_frame, int32_t* out_category, double* out_bbox4, double* out_score,
                               int64_t* out_object_id, int64_t* n_out_dev, int64_t* n_births_dev,
                               void* workspace, size_t workspace_bytes, void* stream_) {
-    WT_TRY(check_byte_thresholds(params, low_score_threshold, low_iou_threshold));
-    WT_TRY(wt::ensure_device());
-    hipStream_t stream = (hipStream_t)stream_;
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
-    const int C = params->n_classes;
-    if (n_streams <= 0 || n_frames <= 0) {
-        WT_HIP(hipMemsetAsync(n_out_dev, 0, sizeof(int64_t), stream));
-        WT_HIP(hipMemsetAsync(n_births_dev, 0, sizeof(int64_t), stream));
-        return WT_OK;
-    }
-    char* base = wt::align_ptr(workspace);
-    Workspace ws = carve_ws(base, n_dets, n_frames, n_streams, C, cap, capN, cost_g);
-    State st = carve_state(base + ws.bytes, n_streams, C, cap);
-    ByteExtra bx = carve_byte(base + ws.bytes + st.bytes, n_streams, C, cap);
-    if (!workspace || workspace_bytes < ws.bytes + st.bytes + bx.bytes + 256) {
-        wt::set_error("tracking workspace too small: need %zu bytes, have %zu", ws.bytes + st.bytes + bx.bytes + 256, workspace_bytes);
-        return WT_ERR_CAPACITY;
-    }
-    bx.h_low_score = low_score_threshold;
-    bx.h_low_iou = low_iou_threshold;
-    return run_tracking(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
-                        clip_w, clip_h, params, id_base, out_frame, out_category, out_bbox4, out_score, out_object_id,
-                        n_out_dev, n_births_dev, ws, st, 0, cap, capN, lds_cost, cost_g, lds, stream, &bx);
+    WT_TRY(check_byte_thresholds(params, low_score_threshold, low_iou_threshold));      // before any device call
+    return track_streams_dev({n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets, clip_w, clip_h},
+                             max_frame_dets, params, low_score_threshold, low_iou_threshold, id_base,
+                             {out_frame, out_category, out_bbox4, out_score, out_object_id, n_out_dev, n_births_dev},
+                             workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 /* ---- streaming form: the trackers persist in `state` between chunks of frames ---- */
 size_t wt_track_state_bytes(int32_t n_streams, int64_t max_frame_dets, const wt_track_params* params) {
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    if (n_streams <= 0 || pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams) != WT_OK) return 0;
-    return carve_state(nullptr, n_streams, params->n_classes, cap).bytes + 256;
+    Plan pl;
+    if (n_streams <= 0 || plan_tracking(pl, 0, 0, n_streams, max_frame_dets, params, nullptr, nullptr, kState, nullptr, nullptr) != WT_OK) return 0;
+    return pl.st_need;
 }
 
 int wt_track_state_init_dev(void* state, size_t state_bytes, int32_t n_streams, int64_t max_frame_dets,
                             const wt_track_params* params, void* stream_) {
     WT_TRY(wt::ensure_device());
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
+    Plan pl;
+    WT_TRY(plan_tracking(pl, 0, 0, n_streams, max_frame_dets, params, nullptr, nullptr, kState, nullptr, state));
     if (n_streams <= 0) { wt::set_error("n_streams must be positive"); return WT_ERR_INVALID; }
-    const int C = params->n_classes;
-    State st = carve_state(wt::align_ptr(state), n_streams, C, cap);
-    if (!state || state_bytes < st.bytes + 256) {
-        wt::set_error("tracker state too small: need %zu bytes, have %zu", st.bytes + 256, state_bytes);
-        return WT_ERR_CAPACITY;
-    }
-    const long long items = (long long)n_streams * C * cap;
+    WT_TRY(fits("tracker state", state, state_bytes, pl.st_need));
+    const long long items = (long long)n_streams * pl.C * pl.cap;
     hipLaunchKernelGGL(state_init_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
-                       (int)n_streams, C, cap, st);
+                       (int)n_streams, pl.C, pl.cap, pl.st);
     WT_HIP(hipGetLastError());
     return WT_OK;
 }
 
 size_t wt_track_chunk_workspace(int64_t n_dets, int64_t n_frames, int32_t n_streams, int64_t max_frame_dets,
                                 const wt_track_params* params) {
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    if (pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams) != WT_OK) return 0;
-    return carve_ws(nullptr, n_dets, n_frames, n_streams, params->n_classes, cap, capN, cost_g).bytes + 256;
+    return streams_workspace(n_dets, n_frames, n_streams, max_frame_dets, params, nullptr, nullptr, kChunk);
 }
 
 int wt_track_chunk_dev(void* state, size_t state_bytes,
@@ -818,28 +778,15 @@ int wt_track_chunk_dev(void* state, size_t state_bytes,
                        void* workspace, size_t workspace_bytes, void* stream_) {
     WT_TRY(wt::ensure_device());
     hipStream_t stream = (hipStream_t)stream_;
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
-    const int C = params->n_classes;
+    const RowsOut out = {out_frame, out_category, out_bbox4, out_score, out_local_id, n_out_dev, n_births_dev};
+    Plan pl;
+    WT_TRY(plan_tracking(pl, n_dets, n_frames, n_streams, max_frame_dets, params, nullptr, nullptr, kChunk, workspace, state));
     if (n_streams <= 0) { wt::set_error("n_streams must be positive"); return WT_ERR_INVALID; }
-    if (n_frames <= 0) {
-        WT_HIP(hipMemsetAsync(n_out_dev, 0, sizeof(int64_t), stream));
-        WT_HIP(hipMemsetAsync(n_births_dev, 0, sizeof(int64_t), stream));
-        return WT_OK;
-    }
-    State st = carve_state(wt::align_ptr(state), n_streams, C, cap);
-    if (!state || state_bytes < st.bytes + 256) {
-        wt::set_error("tracker state too small: need %zu bytes, have %zu", st.bytes + 256, state_bytes);
-        return WT_ERR_CAPACITY;
-    }
-    Workspace ws = carve_ws(wt::align_ptr(workspace), n_dets, n_frames, n_streams, C, cap, capN, cost_g);
-    if (!workspace || workspace_bytes < ws.bytes + 256) {
-        wt::set_error("tracking workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
-        return WT_ERR_CAPACITY;
-    }
-    return run_tracking(n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets,
-                        clip_w, clip_h, params, 0, out_frame, out_category, out_bbox4, out_score, out_local_id,
-                        n_out_dev, n_births_dev, ws, st, 1, cap, capN, lds_cost, cost_g, lds, stream);
+    if (n_frames <= 0) return no_rows(out, stream);
+    WT_TRY(fits("tracker state", state, state_bytes, pl.st_need));
+    WT_TRY(fits("tracking workspace", workspace, workspace_bytes, pl.ws_need));
+    return run_tracking({n_dets, x, y, w, h, score, category, n_frames, frame_det_offsets, n_streams, stream_frame_offsets, clip_w, clip_h},
+                        params, 0, out, pl, 1, stream);
 }
 
 int wt_track_global_ids_dev(const void* state, size_t state_bytes, int32_t n_streams, int64_t max_frame_dets,
@@ -848,12 +795,11 @@ int wt_track_global_ids_dev(const void* state, size_t state_bytes, int32_t n_str
                             void* stream_) {
     WT_TRY(wt::ensure_device());
     hipStream_t stream = (hipStream_t)stream_;
-    int cap, capN, lds_cost; bool cost_g; size_t lds;
-    WT_TRY(pick_caps(max_frame_dets, params, &cap, &capN, &lds_cost, &cost_g, &lds, n_streams));
+    Plan pl;
+    WT_TRY(plan_tracking(pl, 0, 0, n_streams, max_frame_dets, params, nullptr, nullptr, kState, nullptr, const_cast<void*>(state)));
     if (n_streams <= 0 || !stream_birth_prefix) { wt::set_error("bad arguments"); return WT_ERR_INVALID; }
-    State st = carve_state(wt::align_ptr(const_cast<void*>(state)), n_streams, params->n_classes, cap);
-    if (!state || state_bytes < st.bytes + 256) { wt::set_error("tracker state too small"); return WT_ERR_CAPACITY; }
-    hipLaunchKernelGGL(stream_prefix_kernel, dim3(1), dim3(1024), 0, stream, (int)n_streams, st,
+    if (!state || state_bytes < pl.st_need) { wt::set_error("tracker state too small"); return WT_ERR_CAPACITY; }
+    hipLaunchKernelGGL(stream_prefix_kernel, dim3(1), dim3(1024), 0, stream, (int)n_streams, pl.st,
                        (long long*)stream_birth_prefix);
     if (n_rows > 0)
         hipLaunchKernelGGL(global_ids_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, stream,
@@ -904,22 +850,16 @@ static int track_streams_host(int64_t n_dets, const double* x, const double* y, 
     WT_TRY(dch.upload(clip_h ? clip_h : zeros.data(), 8 * (size_t)n_streams));
     WT_TRY(of.alloc(8 * (nd + 1))); WT_TRY(oc.alloc(4 * (nd + 1))); WT_TRY(ob.alloc(32 * (nd + 1)));
     WT_TRY(os.alloc(8 * (nd + 1))); WT_TRY(oi.alloc(8 * (nd + 1))); WT_TRY(dn.alloc(16));
-    const size_t wsb = low_score ? wt_track_streams_byte_workspace(n_dets, n_frames, n_streams, max_frame, params, low_score, low_iou)
-                                 : wt_track_streams_workspace(n_dets, n_frames, n_streams, max_frame, params);
+    const size_t wsb = streams_workspace(n_dets, n_frames, n_streams, max_frame, params, low_score, low_iou, kBatch);
     if (!wsb) return WT_ERR_CAPACITY;
     WT_TRY(dws.alloc(wsb));
-    if (low_score)
-        WT_TRY(wt_track_streams_byte_dev(n_dets, dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>(),
-                                         ds.as<double>(), dc.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams,
-                                         dso.as<int64_t>(), dcw.as<double>(), dch.as<double>(), max_frame, params, low_score, low_iou,
-                                         id_base, of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(),
-                                         oi.as<int64_t>(), dn.as<int64_t>(), dn.as<int64_t>() + 1, dws.p, wsb, nullptr));
-    else
-        WT_TRY(wt_track_streams_dev(n_dets, dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>(),
-                                    ds.as<double>(), dc.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams,
-                                    dso.as<int64_t>(), dcw.as<double>(), dch.as<double>(), max_frame, params, id_base,
-                                    of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(), oi.as<int64_t>(),
-                                    dn.as<int64_t>(), dn.as<int64_t>() + 1, dws.p, wsb, nullptr));
+    WT_TRY(track_streams_dev({n_dets, dx.as<double>(), dy.as<double>(), dw.as<double>(), dh.as<double>(), ds.as<double>(),
+                              dc.as<int32_t>(), n_frames, dfo.as<int64_t>(), n_streams, dso.as<int64_t>(), dcw.as<double>(),
+                              dch.as<double>()},
+                             max_frame, params, low_score, low_iou, id_base,
+                             {of.as<int64_t>(), oc.as<int32_t>(), ob.as<double>(), os.as<double>(), oi.as<int64_t>(),
+                              dn.as<int64_t>(), dn.as<int64_t>() + 1},
+                             dws.p, wsb, nullptr));
     WT_HIP(hipDeviceSynchronize());
     int64_t res[2] = {0, 0};
     WT_HIP(hipMemcpy(res, dn.p, 16, hipMemcpyDeviceToHost));
