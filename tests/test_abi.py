@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library builds for gfx950, loads, and exports every symbol
 the headers under include/ declare.  No compute call is made (no GPU here)."""
 import ctypes
+import glob
 import os
 import re
 
@@ -126,3 +127,50 @@ def test_environment_switches_are_the_listed_ones():
             if f.endswith(('.py', '.hip', '.h', '.cpp')):
                 found.update(a or b for a, b in pat.findall(open(os.path.join(d, f), errors='replace').read()))
     assert sorted(found) == ENV_SWITCHES
+
+
+def _sources(top, suffixes=('',)):
+    for d, _, files in os.walk(os.path.join(ROOT, top)):
+        for f in sorted(files):
+            if f.endswith(suffixes):
+                yield os.path.relpath(os.path.join(d, f), ROOT), open(os.path.join(d, f), errors='replace').read()
+
+
+# Every identifier a preprocessor conditional under csrc/ tests (include guards aside).  The rule above holds for these too: a compile-time
+# switch whose variant lost is deleted together with its code; an experiment patches a COPY of the source (tools/split_planes_ablation_build.py).
+CPP_SWITCHES = ['FB_TIMING', 'WD_DEBUG', 'WT_PHASE_TIMING', '__HIPCC__', '__cplusplus']
+
+
+def test_preprocessor_switches_are_the_listed_ones():
+    found = set()
+    for _, txt in _sources('waymo_2d_tracking_amd/csrc', ('.hip', '.h', '.cpp')):
+        # an include guard defines its name to nothing; "#ifndef X / #define X 7" is an overridable constant, i.e. a switch
+        guards = set(re.findall(r'^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[ \t]*\n[ \t]*#[ \t]*define[ \t]+\1[ \t]*$', txt, flags=re.M))
+        for cond in re.findall(r'^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$', txt, flags=re.M):
+            found.update(set(re.findall(r'[A-Za-z_]\w*', re.split(r'//|/\*', cond)[0])) - {'defined'} - guards)
+    assert sorted(found) == CPP_SWITCHES
+    # a project switch lives as long as the build or a tool compiles with it
+    users = open(os.path.join(ROOT, 'waymo_2d_tracking_amd', 'build.py')).read() + ''.join(t for _, t in _sources('tools'))
+    orphans = [s for s in CPP_SWITCHES if not s.startswith('__') and not re.search(r'(?:\b|-D)%s\b' % s, users)]
+    assert not orphans, orphans
+
+
+def test_tools_and_documents_name_only_what_the_tree_has():
+    """Every tools/<path> written under tools/ or in the documents exists (a program counts when its .hip source does), and every wd_ / wt_ entry
+    point a tool calls on the library is declared in include/*.h or csrc/debug/waymodet_debug.h."""
+    declared = set()
+    for _, txt in list(_sources('include', '.h')) + list(_sources('waymo_2d_tracking_amd/csrc/debug', '.h')):
+        declared.update(re.findall(r'\b(w[td]_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', '', txt, flags=re.S)))
+    assert len(declared) >= 100
+    texts = dict(_sources('tools'))
+    for doc in ('DESIGN.md', 'README.md', 'INTEGRATION.md'):
+        texts[doc] = open(os.path.join(ROOT, doc)).read()
+    missing = []
+    for rel, txt in sorted(texts.items()):
+        for path in sorted(set(re.findall(r'\btools/[\w./*-]*[\w*]', txt))):
+            if not glob.glob(os.path.join(ROOT, path)) and not os.path.exists(os.path.join(ROOT, path + '.hip')):
+                missing.append((rel, path))
+        if rel.startswith('tools'):
+            called = re.findall(r'\.(w[td]_[a-z0-9_]+)\s*\(|attr\(.*?,\s*[\'"](w[td]_[a-z0-9_]+)[\'"]', txt)
+            missing += [(rel, name) for name in sorted({a or b for a, b in called} - declared)]
+    assert not missing, missing

@@ -14,6 +14,11 @@ int wd_debug_hold(int n_wg, int lds_bytes, long long cycles, int* sink, void* st
 int wd_debug_mfma_burn(int workgroups, int kind, int iters, unsigned* sink, void* stream);
 /* per-workgroup s_memtime stamps of the following split-operand launches (8 int64 per workgroup; NULL = off); csrc/det_gemm_split.hip under -DWD_DEBUG */
 int wd_gemm_split_debug_stamps(long long* buf);
+/* Instrumented builds of the product library (WD_HIPCC_FLAGS, not WD_DEBUG_BUILD): cycle counters read back by the timing tools. */
+/* -DFB_TIMING (csrc/det_deform_bwd.hip): cycles per phase of deform_dxoff_kernel, summed over wave 0 of every workgroup */
+int wd_deform_fb_ticks(unsigned long long* out8, int reset);
+/* -DWT_PHASE_TIMING (csrc/sort_engine.hip): cycles per tracker_step phase, summed over all waves */
+int wt_debug_phase_cycles(unsigned long long* out12, int reset);
 #ifdef __cplusplus
 }
 #endif

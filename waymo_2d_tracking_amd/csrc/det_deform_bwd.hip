@@ -163,7 +163,7 @@ __global__ __launch_bounds__(192) void deform_dw_kernel(const float* __restrict_
     const int g = blockIdx.x % G, slice = blockIdx.x / G;
     const int H = geo.H, W = geo.W, Ho = geo.Ho, Wo = geo.Wo;
     const int tiles_x = (Wo + 7) >> 3, tiles_y = (Ho + 7) >> 3, ntiles = batch * tiles_y * tiles_x;
-    f32x4 acc[3][MT][MT];   // experiments: -DFB_NO_EPILOGUE (no atomics), -DFB_NO_STAGE (stage the first tile only)
+    f32x4 acc[3][MT][MT];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -180,9 +180,6 @@ __global__ __launch_bounds__(192) void deform_dw_kernel(const float* __restrict_
         __syncthreads();                                   // the previous tile's readers are done
         if (tid < 4) farflag[tid] = 0;
         __syncthreads();
-#ifdef FB_NO_STAGE
-        if (tile == slice)
-#endif
         fb_stage<CG, 192>(x, offset, tn, ty, tx, geo, C, g * CG, xs, tab, farpos, farflag, tid);
         // A fragments: dY[pixel 4 s + j][o = MT n + mt]  (K = pixels: k-step s covers 4 consecutive pixels of a tile row)
         vec a[16];
@@ -232,9 +229,6 @@ __global__ __launch_bounds__(192) void deform_dw_kernel(const float* __restrict_
             }
         }
     }
-#ifdef FB_NO_EPILOGUE
-    if (acc[0][0][0][0] != 123.456f) return;
-#endif
     // partial sums of this workgroup, in register order (256-byte stores): part[slice][g][wave][t][mt][nt][r][lane]
     float* __restrict__ pw = part + ((size_t)blockIdx.x * 3 + wave) * (3 * MT * MT * 4 * 64) + lane;
 #pragma unroll
@@ -449,24 +443,15 @@ __device__ unsigned long long fb_ticks[8];
 #else
 #define FB_T(k) do { } while (0)
 #endif
-#ifndef FB_GU
-#define FB_GU 4
-#endif
 // Workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() carries a fence that would also wait for the global float
 // atomics of the gather (fire-and-forget adds into dX; nothing in the kernel reads them back) - a memory round trip per phase.
-#ifdef FB_FULL_BARRIER
-#define FB_BARRIER() __syncthreads()
-#else
 #define FB_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
-#endif
-#ifndef FB_WAVES
-#define FB_WAVES __attribute__((amdgpu_waves_per_eu(3, 3)))
-#endif
 template <int CG> constexpr size_t dxoff_smem_bytes() { return (size_t)(fb::NPIX + 1) * (CG + fb::XPAD) * 4 + tt::NROW * 16 * 4 + tt::LDS_BYTES; }
 
 template <int CG>
-__global__ __launch_bounds__(384) FB_WAVES void deform_dxoff_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                                    const float* __restrict__ yact, const float* __restrict__ scale, const float* __restrict__ wpk,
+__global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(3, 3))) void deform_dxoff_kernel(
+                                                           const float* __restrict__ x, const float* __restrict__ dy,
+                                                           const float* __restrict__ yact, const float* __restrict__ scale, const float* __restrict__ wpk,
                                                            const unsigned char* __restrict__ tbl, int batch, Geo geo, int C, int items_total,
                                                            float* __restrict__ dx, float* __restrict__ doff) {
     constexpr int MT = CG / 16, KS = CG / 4, KQ = KS / 4;       // k-steps of 4 output channels; float4s per operand fragment
@@ -619,7 +604,6 @@ __global__ __launch_bounds__(384) FB_WAVES void deform_dxoff_kernel(const float*
 #pragma unroll
                 for (int p2 = 0; p2 < 2; ++p2) {
                     const int row = row0 + 64 * t + 16 * p2;
-#ifndef FB_NO_DOFF
                     // the unit's LDS requests first (they land under the MFMA chain), then the next unit's table entry
                     const uint4 e = en;
                     const f32x4 v0 = *reinterpret_cast<const f32x4*>(cb + (e.x & 0xFFFFu));
@@ -628,14 +612,12 @@ __global__ __launch_bounds__(384) FB_WAVES void deform_dxoff_kernel(const float*
                     const f32x4 v3 = *reinterpret_cast<const f32x4*>(cb + (e.y >> 16));
                     if (t * 2 + p2 < 5) en = tab[row0 + 64 * ((t * 2 + p2 + 1) >> 1) + 16 * ((t * 2 + p2 + 1) & 1)];
                     asm volatile("" ::: "memory");
-#endif
                     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int u = 0; u < KQ; ++u)
 #pragma unroll
                         for (int v = 0; v < 4; ++v) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[u][v], bq[p2][u][v], acc, 0, 0, 0);
                     // acc[r] = dcol[pixel][tap][ci = mt 16 + 4 j + r]
-#ifndef FB_NO_DOFF
                     const float lh = __uint_as_float(e.z), lw = __uint_as_float(e.w), uh = 1.f - lh, uw = 1.f - lw;
                     // d val / d h = (v2 - v0)(1 - lw) + (v3 - v1) lw ;  d val / d w = (v1 - v0)(1 - lh) + (v3 - v2) lh, summed over the channels with
                     // dcol as the weight: four dot products s_q = <dcol, v_q> (16 FMAs; VALU time adds to the MFMA time on this machine), then
@@ -648,7 +630,6 @@ __global__ __launch_bounds__(384) FB_WAVES void deform_dxoff_kernel(const float*
                     od[t][p2][1] += (s1 - s0) * uh + (s3 - s2) * lh;
                     asm volatile("" : "+v"(od[t][p2][0]), "+v"(od[t][p2][1]));     // or LLVM sinks this arithmetic (and the 20 registers of every unit
                                                                                   // it needs) below the gather
-#endif
                     *reinterpret_cast<f32x4*>(dc + row * 16 + ((j ^ ((row >> 1) & 3)) << 2)) = acc;
                     FB_FENCE();
                 }
@@ -658,7 +639,6 @@ __global__ __launch_bounds__(384) FB_WAVES void deform_dxoff_kernel(const float*
             FB_T(3);
             if (mt + 1 == mt_end && more) load_item(ntile, ng);    // in flight during the gather; bq is dead after the last MFMA phase
             // gather: patch pixel pp sums its list; 4 lanes x 4 channels per patch pixel, longest lists first
-#ifndef FB_NO_GATHER       // experiments (wrong results): -DFB_NO_GATHER, -DFB_NO_DOFF, -DFB_NO_DXATOMIC
             {
                 const int c = tid & 3;
 #pragma unroll 1
@@ -692,16 +672,11 @@ __global__ __launch_bounds__(384) FB_WAVES void deform_dxoff_kernel(const float*
                             const int r = pp / fb::PS;
                             const int iy = geo.S * 8 * ty - geo.org + r, ix = geo.S * 8 * tx - geo.org + (pp - r * fb::PS);
                             float* d = dx + ((size_t)(tn * H + iy) * W + ix) * C + g * CG + mt * 16 + 4 * c;
-#ifdef FB_NO_DXATOMIC
-                            *reinterpret_cast<f32x4*>(d) = a;
-#else
                             atomicAdd(d + 0, a[0]); atomicAdd(d + 1, a[1]); atomicAdd(d + 2, a[2]); atomicAdd(d + 3, a[3]);
-#endif
                         }
                     }
                 }
             }
-#endif
             FB_T(4);
             if (mt + 1 < mt_end) FB_BARRIER();
             FB_T(5);

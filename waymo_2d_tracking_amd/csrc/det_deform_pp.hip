@@ -40,9 +40,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
-#ifndef PP_SPLIT32
-#define PP_SPLIT32 0
-#endif
 namespace pp {
 constexpr int PS = 14;                 // patch side: 8 + 2 (3x3 footprint) + 2 * 2 (halo for the learned offsets)
 constexpr int NPIX = PS * PS;          // 196 (+ pixel 196 = zeros)
@@ -52,21 +49,14 @@ constexpr int PATCH_B = PATCH_F * 4;
 constexpr int NE = 64 * 9;             // (pixel, tap) entries per tile
 constexpr int TAB_B = NE * 16;         // bytes per table buffer
 constexpr unsigned FAR_Y = 0xFFFFFFFFu;    // entry.y of a sample whose corners are fetched from global memory
-#ifndef PP_RES_TAPS
-#define PP_RES_TAPS 3                  // taps whose weights stay in registers for the whole kernel; the others stream from LDS per tile
-#endif
-constexpr int RW = PP_RES_TAPS;
+constexpr int RW = 3;                  // taps whose weights stay in registers for the whole kernel; the others stream from LDS per tile
 template <int CG> constexpr int tap_floats() { return (CG == 32 ? 4 : 2) * 64 * 4; }     // weights of one tap of an item
 constexpr int NT = 2;                  // teams (4 waves, one tile each) per workgroup
 template <int CG> constexpr size_t smem_bytes() { return (size_t)(9 - RW) * tap_floats<CG>() * 4 + 2 * NT * (size_t)PATCH_B + 2 * NT * (size_t)TAB_B; }
 }  // namespace pp
 
 // Workgroup barrier without the fence of __syncthreads() (the fence would make every wave wait for its outstanding LDS reads)
-#ifdef PP_NO_BARRIER      // experiments: upper bound of what the barrier costs (results are wrong)
-#define PP_BARRIER() do { asm volatile("" ::: "memory"); } while (0)
-#else
 #define PP_BARRIER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
-#endif
 // slot boundary: the "memory" clobber keeps LLVM's IR passes from sinking the LDS loads to their uses behind the MFMA burst, the
 // sched_barrier keeps the machine scheduler from moving anything across
 #define PP_SLOT() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -415,9 +405,6 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
         ad1 = ((ent.x >> 16) ^ kx) + base;
         ad2 = ((ent.y & 0xFFFFu) ^ kx) + base;
         ad3 = ((ent.y >> 16) ^ kx) + base;
-#ifdef PP_LIN_CORNER
-        ad0 = base + lane * 32; ad1 = ad0 + 2048; ad2 = ad0 + 4096; ad3 = ad0 + 6144;      // experiments: lane-linear corner reads
-#endif
     };
     auto lds_corners = [&]() {
         cv[0] = *(lds4)(uintptr_t)ad0; cv[1] = *(lds4)(uintptr_t)(ad0 ^ QX);
@@ -429,7 +416,6 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
     // corner outside the image gets weight 0) and the weights of tap k -> bb
     auto issue_reads = [&](auto FARC, int k, f32x4 (&bb)[NQ], bool want_w, int tn) {
         constexpr bool FAR = decltype(FARC)::value;
-#ifndef PP_NO_FAR
         if (FAR && __builtin_expect(__ballot(far_nxt) != 0, 0)) {
             if (far_nxt) {
                 const int ih = (int)(ent.x & 0xFFFFu) - 32768, iw = (int)(ent.x >> 16) - 32768;
@@ -450,9 +436,7 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
             } else {
                 lds_corners();
             }
-        } else
-#endif
-        {
+        } else {
             lds_corners();
         }
         if (want_w) {
@@ -461,10 +445,6 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
         }
     };
     auto blend = [&]() {
-#ifdef PP_NO_BLEND
-        a[0] = cv[0].x; a[1] = cv[1].y; a[2] = cv[2].x; a[3] = cv[3].y; a[4] = cv[4].x; a[5] = cv[5].x; a[6] = cv[6].x; a[7] = cv[7].x + w00 + w01 + w10 + w11;
-        return;
-#endif
         // two channels per instruction (v_pk_fma_f32 with a broadcast weight), four independent chains advanced together
         const f32x2 W00 = {w00, w00}, W01 = {w01, w01}, W10 = {w10, w10}, W11 = {w11, w11};
         f32x2 r0 = W00 * cv[0].xy, r1 = W00 * cv[0].zw, r2 = W00 * cv[1].xy, r3 = W00 * cv[1].zw;
@@ -474,10 +454,6 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
         a[0] = r0.x; a[1] = r0.y; a[2] = r1.x; a[3] = r1.y; a[4] = r2.x; a[5] = r2.y; a[6] = r3.x; a[7] = r3.y;
     };
     auto mfma_tap = [&](const f32x4 (&bb)[NQ]) {
-#ifdef PP_NO_MFMA
-        acc[0][0] += a[0] * bb[0].x + a[7] * bb[NQ - 1].w; acc[1][1] += a[3] * bb[1].y + a[5] * bb[0].z; acc[2][0] += a[1]; acc[3][0] += a[2];
-        return;
-#endif
 #define PP_MM(ch, t, wa, av) acc[2 * (ch) + (t)] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa, av, acc[2 * (ch) + (t)], 0, 0, 0);
         if constexpr (CG == 32) {
             // k-step kk: channels 8 kq + kk of the lane's pixel; output tiles 0 / 1 = channels 0-15 / 16-31 of the group
@@ -522,21 +498,15 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
         // side jobs: the compiler waits for ALL vector-memory operations right before the next tap's corner requests (the corner
         // registers may be the target of global loads), so stores and DMA requests are issued right behind this tap's and have a
         // whole tap to complete
-#ifndef PP_NO_SIDE
-#ifndef PP_NO_EPI
         if (k == 0 && it > 0) epilogue();
-#endif
         if (k == 1) {                                             // next tile of this team: patch + table on their way for 6 taps
             have_next = it + 1 < n_items;
             if (have_next) {
                 nxt = tile_xy(it + 1);
-#ifndef PP_NO_DMA
                 issue_patch(nxt, base_nxt);
                 issue_table(nxt, tab_nxt);
-#endif
             }
         }
-#endif
         if (k == 7) {
             // the tile's only barrier.  Before it: every read of THIS tile's patch and table has been issued (tap 8's corners just
             // above, entry 8 in G(6)), so the DMA of tap 1 of the next tile may overwrite them; own DMA pieces (and zero-fill
@@ -562,7 +532,7 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
     // 16 channels per group: does any tile of this workgroup hold a far sample?  (one word per tile behind the table, written by the
     // pre-pass; every wave reads them itself: no barrier)
     bool wg_far = true;
-    if constexpr ((CG == 16 || PP_SPLIT32) && NT == 2) {
+    if constexpr (CG == 16 && NT == 2) {
         const unsigned* tflag = reinterpret_cast<const unsigned*>(table + (size_t)ntiles * pp::NE);
         wg_far = false;
         for (int t = t0 + lane; t < t1; t += 64) {
@@ -590,7 +560,7 @@ __global__ __launch_bounds__(256 * pp::NT, pp::NT) __attribute__((amdgpu_waves_p
     // epilogue stores) before every corner read, even when no lane takes it.  16 channels per group: a second copy of the loop without
     // the far path runs when none of the workgroup's tiles needs it (+8 % at offsets below 1 px).  32 channels per group: the shared
     // register allocation of two copies spills inside the far-capable one (2 px: +9 % time) - one loop there.
-    if constexpr ((CG == 16 || PP_SPLIT32) && NT == 2) {
+    if constexpr (CG == 16 && NT == 2) {
         if (wg_far) items(std::true_type{});
         else items(std::false_type{});
     } else {

@@ -246,7 +246,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v2_kernel(const float* __restr
         read_half(0, 0);
         if (nslab > 1) sstore(1);
         int s = 0;
-#ifndef WD_GEMM_NO_INTERLEAVE
         // steady state (branch-free body): the loads / LDS reads / LDS writes are interleaved with the MFMAs of the same half by
         // sched_group_barrier (one memory instruction per 4 MFMAs): issued in the matrix pipe's shadow instead of in front of it
         for (; s + 2 < nslab; ++s) {
@@ -283,8 +282,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v2_kernel(const float* __restr
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
-        for (; s < nslab; ++s) {                                // tail (and the whole loop with WD_GEMM_NO_INTERLEAVE)
+        for (; s < nslab; ++s) {                                // tail
             const int buf = s & 1;
             if (s + 2 < nslab) gload(s + 2);
             read_half(buf, 1);

@@ -283,10 +283,6 @@ __global__ __launch_bounds__(1024) void roi_bucket_order_kernel(Levels lv, int n
             cell = cell > 7 ? 7 : cell;
             // serpentine: odd bands run right to left, so consecutive ROIs stay neighbours at the band ends
             key[j] = ((li & 3) << 9) | (band << 3) | ((band & 1) ? 7 - cell : cell);
-#ifdef ROI_KEY_LPT      // experiment: largest footprint first
-            { const float fp = ((x2 - x1) * sc + 2.f) * ((y2 - y1) * sc + 2.f);
-              int k2 = (int)fp; k2 = k2 > NB - 1 ? NB - 1 : (k2 < 0 ? 0 : k2); key[j] = NB - 1 - k2; }
-#endif
             rank[j] = atomicAdd(&hist[key[j]], 1);
         }
     }
@@ -329,40 +325,26 @@ __device__ __forceinline__ void roi_fma4(float4& a, float w, const float4& v) {
     a.x += w * v.x; a.y += w * v.y; a.z += w * v.z; a.w += w * v.w;
 }
 
-#ifndef ROI_NW
-#define ROI_NW 7                  // waves per workgroup: one per bin row (4: waves take rows w and w + 4, measured slower on scattered ROIs)
-#endif
-#ifndef ROI_QB
-#define ROI_QB 8                  // footprint columns per block: 2 QB loads of 1 KiB in flight per wave
-#endif
-#ifndef ROI_MINW
-#define ROI_MINW 2
-#endif
-__global__ __launch_bounds__(64 * ROI_NW, ROI_MINW) void roi_pool_wg_kernel(Levels lv, int n_levels, int C, int batch,
+constexpr int kRoiNW = 7;         // waves per workgroup: one per bin row (4: waves take rows w and w + 4, measured slower on scattered ROIs)
+constexpr int kRoiQB = 8;         // footprint columns per block: 2 QB loads of 1 KiB in flight per wave
+constexpr int kRoiMinW = 2;       // second __launch_bounds__ argument (minimum waves per SIMD)
+__global__ __launch_bounds__(64 * kRoiNW, kRoiMinW) void roi_pool_wg_kernel(Levels lv, int n_levels, int C, int batch,
                                                           const float* __restrict__ rois, int n_rois,
                                                           int min_level, int canonical_level, float canonical_size,
                                                           float* __restrict__ out, const int* __restrict__ order) {
-    constexpr int QB = ROI_QB, NW = ROI_NW, NT = 64 * NW;
+    constexpr int QB = kRoiQB, NW = kRoiNW, NT = 64 * NW;
     __shared__ float wy[7][kMaxFoot];
     __shared__ float wx[8][kMaxFoot];                // row 7 stays zero: the sliding window may look one bin past the last
     __shared__ int lohi_y[7][2];
     __shared__ int col_pa[kMaxFoot];
     __shared__ int any_wide;
-    __shared__ __attribute__((aligned(16))) float done_lds[ROI_NW * 7 * 64 * 4];     // per wave: the 7 finished bin sums of the current bin row
-#ifdef ROI_LDS_PAD
-    __shared__ int lds_pad[ROI_LDS_PAD / 4];         // experiments: fewer resident workgroups per CU
-    if (n_rois < 0) lds_pad[threadIdx.x] = n_rois;
-#endif
+    __shared__ __attribute__((aligned(16))) float done_lds[kRoiNW * 7 * 64 * 4];     // per wave: the 7 finished bin sums of the current bin row
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // with an order list: XCD x (blockIdx % 8) takes the x-th contiguous eighth of it
     const int per_xcd = ((int)gridDim.x + 7) >> 3;
-#ifdef ROI_KEY_LPT
-    const int slot = (int)blockIdx.x; (void)per_xcd;
-#else
     const int slot = order ? ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-#endif
     if (slot >= n_rois) return;
     const int r = order ? order[slot] : slot;
     const float* roi = rois + 5 * (size_t)r;
@@ -615,7 +597,7 @@ extern "C" int wd_roi_pool_fpn_f32(const float* const* feats, const int32_t* hei
                 hipLaunchKernelGGL(roi_bucket_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, lv, n_levels, rois, n_rois,
                                    min_level, canonical_level, canonical_size, order);
             }
-            hipLaunchKernelGGL(roi_pool_wg_kernel, dim3((unsigned)(order ? (n_rois + 7) / 8 * 8 : n_rois)), dim3(64 * ROI_NW), 0,
+            hipLaunchKernelGGL(roi_pool_wg_kernel, dim3((unsigned)(order ? (n_rois + 7) / 8 * 8 : n_rois)), dim3(64 * kRoiNW), 0,
                                (hipStream_t)stream, lv, n_levels, channels, batch, rois, n_rois, min_level, canonical_level,
                                canonical_size, out, (const int*)order);
         } else {

@@ -24,10 +24,7 @@
 
 namespace jd {
 
-#ifndef JD_SUB_BITS
-#define JD_SUB_BITS 1024
-#endif
-constexpr int SUB_BITS = JD_SUB_BITS;              // bits per subsequence (1024 = 128 bytes = 32 words)
+constexpr int SUB_BITS = 1024;                     // bits per subsequence (1024 = 128 bytes = 32 words)
 constexpr int SUB_BYTES = SUB_BITS / 8;
 constexpr int SUB_WORDS = SUB_BITS / 32;
 constexpr int MAX_BPM = 10;                        // blocks per MCU (T.81 B.2.3)

@@ -33,14 +33,6 @@ __device__ __forceinline__ bool finite_d(double v) { return (v == v) && (v - v =
 // (~100 cycles each; Munkres step 6 calls this ~26 times per frame).  The inputs are never NaN (the callers' per-lane minima start from +inf
 // and skip NaN entries with `v < mn`), so the order of the comparisons does not matter.
 __device__ __forceinline__ float wave_min_f(float v) {
-#ifdef WT_WAVE_MIN_BPERMUTE
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float u = __shfl_xor(v, o, kWave);
-        v = (u < v) ? u : v;
-    }
-    return v;
-#else
     auto step = [](float x, auto CTRL, auto ROWMASK) {
         const int moved = __builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), decltype(CTRL)::value, decltype(ROWMASK)::value, 0xF, false);
         const float u = __int_as_float(moved);
@@ -55,7 +47,6 @@ __device__ __forceinline__ float wave_min_f(float v) {
     v = step(v, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xA>{});     // row_bcast:15 into rows 1 and 3
     v = step(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xC>{});     // row_bcast:31 into rows 2 and 3: lane 63 holds the total
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-#endif
 }
 
 // ---- sort.py:33-47 iou(float32 detection, float64 track) under NumPy-1.x scalar promotion -----------------
