@@ -138,7 +138,17 @@ int wd_nms_segmented_f32(const float* boxes, const int32_t* idxs, const int32_t*
  * RPN.predict_proposals (detectron2 proposal_utils.find_top_rpn_proposals, called from detectron2_det/__init__.py:74 via the
  * model forward): per FPN level the k best objectness logits (torch.topk(sorted=True); ties: lower anchor index first) and
  * apply_deltas + clip of exactly those anchors.  Level l's rows start at sum_{m<l} min(k, n_m).  group = level, or -1 for an
- * empty box (dropped by find_top_rpn_proposals); valid = 0 for an empty box.  Device pointers in host arrays. */
+ * empty box (dropped by find_top_rpn_proposals); valid = 0 for an empty box.  Device pointers in host arrays.
+ * Order of the selection, and of both candidate sorts below: torch.sort(descending=True, stable=True) of the float32 scores,
+ * i.e. every NaN first, whatever its sign or payload (the score written for such a row is a NaN), then descending by value
+ * with -0.0 equal to +0.0; equal scores and NaNs among themselves in index order.
+ * k and the level sizes: 1 <= k <= 8192, 1 <= n_levels <= 8, no empty level.  A level longer than one 8192-key chunk is reduced
+ * in stages, c chunks leaving (c - 1) * k + min(last chunk, k) keys; the whole plan is made on the host before anything is
+ * launched and a call is served when the plan ends within 24 stages.  That holds for every k <= 4096 at any level size, and for
+ * every k <= 8192 when no level exceeds 8192 keys (one stage); 4096 < k <= 8192 with a longer level is served when the plan
+ * happens to end in time (k = 5000, n = 460800: 10 stages) and is otherwise refused with WT_ERR_INVALID (k = 8000, n = 16384:
+ * 43 stages; k = 8192, n = 8193: never ends).  Every refusal happens before the first launch: outputs and workspace are
+ * untouched and wt_last_error names k. */
 size_t wd_rpn_topk_workspace(const int* n_per_level, int n_levels, int k);
 int wd_rpn_topk_decode_f32(const float* const* logits, const float* const* deltas, const float* const* anchors,
                            const int* n_per_level, int n_levels, int k, float img_h, float img_w, float scale_clamp,
@@ -162,7 +172,8 @@ int wd_gather_kept_f32(const uint8_t* keep, const uint8_t* valid, const float* b
                        void* stream);
 /* Detectron2Det.predict (detectron2_det/__init__.py:119-131) + COCODetection.load_prediction (detnet/data/coco.py:229-252) on the
  * device: pixel boxes of the (possibly h-flipped) in_w x in_h network input -> integer [x, y, w, h] of the out_w x out_h image,
- * 5-decimal score (xywhs: 5 rows of n doubles) and category id = class + 1 (0 for slots >= *count). */
+ * 5-decimal score (xywhs: 5 rows of n doubles) and category id = class + 1 (0 for slots >= *count).  n = 0 is served (nothing
+ * to write: the pointers may be NULL, as those of empty tensors are). */
 int wd_detections_to_wire(const float* boxes, const float* scores, const int64_t* classes, const int32_t* count, int n, int in_w,
                           int in_h, int hflip, int out_w, int out_h, double* xywhs, int32_t* category, void* stream);
 

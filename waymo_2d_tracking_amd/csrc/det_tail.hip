@@ -15,8 +15,9 @@
 //   wire format (Detectron2Det.predict + COCODetection.load_prediction): wire_kernel x1
 //
 // Keys are 64-bit: (order-preserving bits of the float score) << 32 | ~position, so that a descending sort yields
-// score-descending, position-ascending order = a stable descending sort.  Built with -ffp-contract=off: the float
-// arithmetic is the torch sequence operation by operation.
+// score-descending, position-ascending order = a stable descending sort.  Every NaN has the one key value above +inf and
+// -0.0 shares the key of +0.0, as torch's sort compares them.  Built with -ffp-contract=off: the float arithmetic is the
+// torch sequence operation by operation.
 #include "common.h"
 #include <cstdlib>
 #include <cstring>
@@ -37,7 +38,10 @@ __device__ __forceinline__ float from_orderable(unsigned int k) {
 }
 __device__ __forceinline__ unsigned long long make_key(float score, unsigned int pos) {
     if (score == 0.f) score = 0.f;                         // -0.0 and +0.0 compare equal in torch's sort: one key for both
-    return ((unsigned long long)orderable(score) << 32) | (unsigned long long)(0xffffffffu - pos);
+    // torch's descending sort puts every NaN first, whatever its sign or payload, in index order: one key above +inf
+    // (from_orderable gives a NaN back for it)
+    const unsigned int hi = (score != score) ? 0xffffffffu : orderable(score);
+    return ((unsigned long long)hi << 32) | (unsigned long long)(0xffffffffu - pos);
 }
 
 // Descending bitonic sort of s[0..p) (p a power of two, >= 2), all kThreads threads of the workgroup.
@@ -64,6 +68,7 @@ __device__ __forceinline__ int pow2_at_least(int n) {
 }
 
 constexpr int kMaxLevels = 8;
+constexpr int kMaxStages = 24;        // launches one call may plan (include/waymodet.h states what that serves)
 
 struct TopkStage {
     int n_levels, k;
@@ -291,10 +296,14 @@ int wd_rpn_topk_decode_f32(const float* const* logits, const float* const* delta
         cur_n[l] = n_per_level[l];
         cur_off[l] = 0;
     }
-    bool first = true;
-    int which = 0;
-    for (int stage = 0; stage < 8; ++stage) {
-        TopkStage st;
+    // Plan every stage before the first launch: a level of c chunks leaves (c - 1) * k + min(last chunk, k) keys, which does
+    // not shrink fast enough (or at all) when k is near the chunk size.  What the plan cannot finish is refused here, with
+    // nothing queued.  The key buffers stay valid throughout: a stage writes chunks * k keys per level and chunks only shrink.
+    TopkStage plan[kMaxStages];
+    int n_stages = 0;
+    bool done = false;
+    while (!done && n_stages < kMaxStages) {
+        TopkStage& st = plan[n_stages++];
         memset(&st, 0, sizeof(st));
         st.n_levels = n_levels;
         st.k = k;
@@ -313,26 +322,38 @@ int wd_rpn_topk_decode_f32(const float* const* logits, const float* const* delta
             st.anchors[l] = anchors[l];
         }
         st.chunk_begin[n_levels] = chunks_total;
-        int next_n[kMaxLevels];
+        bool shrinks = true;
         for (int l = 0; l < n_levels; ++l) {
             const int chunks = (cur_n[l] + kChunk - 1) / kChunk;
             const int last = cur_n[l] - (chunks - 1) * kChunk;
-            next_n[l] = (chunks - 1) * k + (last < k ? last : k);
+            const int next_n = (chunks - 1) * k + (last < k ? last : k);
+            if (chunks > 1 && next_n >= cur_n[l]) shrinks = false;
             st.out_off[l] = final ? row : out_off;
             out_off += (long long)chunks * k;
-            row += next_n[l];
+            row += next_n;
+            cur_n[l] = next_n;
+            cur_off[l] = st.out_off[l];
         }
-        hipLaunchKernelGGL(rpn_topk_stage_kernel, dim3((unsigned)chunks_total), dim3(kThreads), (size_t)kChunk * 8, stream, st,
-                           first ? 1 : 0, final ? 1 : 0, (const unsigned long long*)buf[which], buf[which ^ 1], img_h, img_w,
-                           scale_clamp, (float4*)out_boxes, out_scores, out_group, out_valid);
-        WT_HIP(hipGetLastError());
-        if (final) return WT_OK;
-        for (int l = 0; l < n_levels; ++l) { cur_n[l] = next_n[l]; cur_off[l] = st.out_off[l]; }
-        which ^= 1;
-        first = false;
+        done = final;
+        if (!shrinks) break;
     }
-    wt::set_error("wd_rpn_topk_decode_f32: selection did not converge");
-    return WT_ERR_INVALID;
+    if (!done) {
+        int longest = 0;
+        for (int l = 0; l < n_levels; ++l) longest = n_per_level[l] > longest ? n_per_level[l] : longest;
+        wt::set_error("wd_rpn_topk_decode_f32: k=%d cannot be selected from a level of %d keys within %d stages (k <= %d always can; "
+                      "any k <= %d when no level exceeds %d)", k, longest, kMaxStages, kChunk / 2, kChunk, kChunk);
+        return WT_ERR_INVALID;
+    }
+    int which = 0;
+    for (int stage = 0; stage < n_stages; ++stage) {
+        const TopkStage& st = plan[stage];
+        hipLaunchKernelGGL(rpn_topk_stage_kernel, dim3((unsigned)st.chunk_begin[n_levels]), dim3(kThreads), (size_t)kChunk * 8, stream,
+                           st, stage == 0 ? 1 : 0, stage == n_stages - 1 ? 1 : 0, (const unsigned long long*)buf[which], buf[which ^ 1],
+                           img_h, img_w, scale_clamp, (float4*)out_boxes, out_scores, out_group, out_valid);
+        WT_HIP(hipGetLastError());
+        which ^= 1;
+    }
+    return WT_OK;
 }
 
 // Stable descending sort of RPN candidates (n <= 8192) and gather into sorted order.
@@ -389,7 +410,7 @@ int wd_gather_kept_f32(const uint8_t* keep, const uint8_t* valid, const float* b
 int wd_detections_to_wire(const float* boxes, const float* scores, const int64_t* classes, const int32_t* count, int n, int in_w,
                           int in_h, int hflip, int out_w, int out_h, double* xywhs, int32_t* category, void* stream) {
     WT_TRY(wt::ensure_device());
-    if (n < 0 || in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1 || !xywhs || !category || (n > 0 && (!boxes || !scores || !classes))) {
+    if (n < 0 || in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1 || (n > 0 && (!xywhs || !category || !boxes || !scores || !classes))) {
         wt::set_error("wd_detections_to_wire: bad argument");
         return WT_ERR_INVALID;
     }
