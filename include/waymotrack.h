@@ -337,6 +337,27 @@ int wt_fuse_groups_dev(const double* dets5, const int64_t* group_offsets, const 
 int wt_fuse_groups_host(const double* dets5, const int64_t* group_offsets, const double* group_wsum, int64_t n_groups, int method,
                         double iou_thresh, double* out5, int32_t* out_members, int32_t* row_cluster, int64_t* out_counts);
 
+/* Weighted boxes fusion / NMW of K test-time views of the same frames, slot to slot: the device form of exporting each view,
+ * detnet/ensemble_b.py over the K files and reading the result back as tracker slots, between the pipeline's two score filters.
+ * xywhs, category, weights, the outputs and the calling conventions are those of wt_ensemble_slots_dev; method is 0
+ * (weighted_fusion) or 1 (nmw), the codes of wt_fuse_groups_*.  One (frame, category) group:
+ *   rows view by view in slot order, kept when the category is in 1..n_categories, w > 0, h > 0 and score * weight >= min_score;
+ *   a kept row's score is score * weight; wsum of the frame = the weights, added in view order, of the views that kept a row of
+ *   ANY category in it; the group is merged as wt_fuse_groups_dev merges it; a cluster is kept if conf > min_score and leaves as
+ *   [x1, y1, x2 - x1, y2 - y1] float64 (not truncated) with score = numpy round(conf, 5).
+ * With min_score = -inf this is detnet/ensemble_b.py itself (whose CPython round differs from numpy's at decimal half-way points).
+ *   out_xywhs (5, n_frames * K * slots), out_category, out_counts: per frame the groups in ascending category order, inside a
+ *   group the clusters by descending conf (ties: creation order), then empty slots (category 0, zero rows).
+ * Group state lives in LDS while K * slots <= wt_fuse_groups_lds_rows(), else in the workspace.  Stream-ordered, no host
+ * synchronisation, no allocation: capturable in a hipGraph.  1 <= K <= 16.  Bad shapes, null pointers or a bad method are
+ * WT_ERR_INVALID, a workspace below wt_fuse_slots_workspace bytes WT_ERR_CAPACITY, both before any launch; the sizer returns 0
+ * for a bad shape. */
+size_t wt_fuse_slots_workspace(int64_t n_frames, int64_t slots, int k_views, int n_categories, int method);
+int wt_fuse_slots_dev(const double* xywhs, const int32_t* category, int64_t n_frames, int64_t slots, int k_views,
+                      const double* weights, int n_categories, int method, double iou_thresh, double min_score,
+                      double* out_xywhs, int32_t* out_category, int64_t* out_counts,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * MOT evaluation (CLEAR-MOT per class and Waymo difficulty level; the definition is in DESIGN.md, "Tracking metric")
  * ================================================================================================= */

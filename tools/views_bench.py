@@ -1,10 +1,11 @@
 """Multi-view detect -> ensemble -> SORT pipeline against its single views, in one invocation; prints one JSON line.
 
-    python tools/views_bench.py [--steps 12] [--warmup 3] [--height 1280 --width 1920]
+    python tools/views_bench.py [--steps 12] [--warmup 3] [--height 1280 --width 1920] [--method soft_nms] [--views-only]
 
 Each configuration is DetectTrackPipeline at the bench's settings (5 cameras x 2 frames per step, 2 frames in flight, deferred
-tracking, captured graphs): views=('orig', 'x1.5,hflip') merged by soft-NMS (cut 0.9, min_score 0.01), then each view alone
-(tta='' and tta='x1.5,hflip').  Reported per configuration: frames/s over the timed steps and the peak device memory
+tracking, captured graphs): views=('orig', 'x1.5,hflip') merged by --method (default soft-NMS; cut 0.9, min_score 0.01;
+weighted_fusion_b / nmw are the rules of detnet.ensemble_b), then each view alone (tta='' and tta='x1.5,hflip'; --views-only skips
+them, to time several merge rules in one session).  Reported per configuration: frames/s over the timed steps and the peak device memory
 (torch.cuda.max_memory_reserved: graph pools included).  For the two-view run also the merge (wt_ensemble_slots_dev, both
 launches) per chunk from HIP events around it on the track stream, and the ratio of its rate to the serial-composition
 estimate 1 / (1 / r_orig + 1 / r_x1.5hflip)."""
@@ -58,10 +59,18 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--height', type=int, default=1280)
     ap.add_argument('--width', type=int, default=1920)
+    ap.add_argument('--method', default=VIEW_ENS['method'], choices=('weighted_fusion', 'nms', 'soft_nms', 'weighted_fusion_b', 'nmw'),
+                    help='merge rule of the two-view run (the other settings stay: iou 0.5, cut 0.9, min_score 0.01)')
+    ap.add_argument('--views-only', action='store_true', help='skip the two single-view runs and the figures derived from them')
     args = ap.parse_args(argv)
     res = dict(workload='DetectTrackPipeline %dx%d, 5 cameras x 2 frames per step, 2 lanes, deferred tracking' % (args.width, args.height),
-               steps=args.steps, warmup=args.warmup)
-    res['views'] = measure(args, views=VIEWS, view_ensemble=VIEW_ENS)
+               steps=args.steps, warmup=args.warmup, method=args.method)
+    res['views'] = measure(args, views=VIEWS, view_ensemble=dict(VIEW_ENS, method=args.method))
+    if args.views_only:
+        v = res['views']
+        res['merge_share_of_chunk_time'] = v['merge_us_per_chunk'] * 1e-3 / (v['ms_per_frame'] * 10)
+        print(json.dumps(res))
+        return
     res['orig'] = measure(args, tta='')
     res['x1.5,hflip'] = measure(args, tta='x1.5,hflip')
     r0, r1 = res['orig']['frames_per_s'], res['x1.5,hflip']['frames_per_s']

@@ -230,9 +230,206 @@ int launch_fuse(const double* dets5, const int64_t* group_offsets, const double*
     return WT_OK;
 }
 
+// ---- fusion of K views' wire slots (the device form of: --export per view -> detnet.ensemble_b -> JSON, between the pipeline's
+// two score filters) ----------------------------------------------------------------------------------------------------------
+// The slot layout and the two passes are those of wt_ensemble_slots_dev (ensemble.hip).  Pass 1, one wavefront per (frame,
+// category) group: scan all K * S slots of the frame view by view in slot order; a row is kept when its category is in 1..C,
+// w > 0, h > 0 and score * weight >= min_score; the kept rows of the group's own category are gathered, and every view with a kept
+// row of ANY category adds its weight to wsum, in view order (ensemble_b.merge_inputs) - so each group's wave derives the frame's
+// wsum on its own.  fuse_group merges; clusters with conf > min_score leave as [x, y, w, h, round5(conf)], boxes not truncated.
+// Pass 2, one wavefront per frame: the frame's groups in ascending category order into its K * S output slots.
+constexpr int kMaxViews = 16;
+constexpr int64_t kMaxSlots = 1 << 20;            // K * S <= kMaxGroupRows
+
+// round(np.float64(s), 5) = numpy around: multiply, rint (half to even), divide (not CPython's correctly rounded round)
+__device__ __forceinline__ double round5_numpy(double s) { return rint(s * 1e5) / 1e5; }
+
+struct FuseSlotsWs {
+    double* rows;      // per group K*S rows of 5: gathered input [score, x, y, w, h], later the final wire rows [x, y, w, h, score]
+    double* merged;    // per group K*S rows of 5: fuse_group's output [conf, x, y, w, h]
+    int32_t* count;    // per group: final row count
+    char* scratch;     // per group `scratch_stride` bytes of group state (global path only)
+    size_t scratch_stride;
+};
+
+bool fuse_slots_use_lds(int64_t ks) { return (size_t)ks <= lds_capacity_rows(); }
+
+FuseSlotsWs fuse_slots_ws_layout(char* base, int64_t n_groups, size_t ks, bool lds, size_t* total) {
+    FuseSlotsWs w;
+    size_t off = 0;
+    const size_t rows_b = wt::align_up((size_t)n_groups * ks * 5 * sizeof(double));
+    w.rows = reinterpret_cast<double*>(base + off); off += rows_b;
+    w.merged = reinterpret_cast<double*>(base + off); off += rows_b;
+    w.count = reinterpret_cast<int32_t*>(base + off); off += wt::align_up((size_t)n_groups * sizeof(int32_t));
+    w.scratch_stride = lds ? 0 : wt::align_up(group_mem_bytes(ks));
+    w.scratch = base + off; off += (size_t)n_groups * w.scratch_stride;
+    *total = off > 0 ? off : 256;
+    return w;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kWave) void fuse_slots_kernel(
+    const double* __restrict__ xywhs, const int32_t* __restrict__ category, int64_t n_frames, int S, int K,
+    const double* __restrict__ weights, int C, int method, double thr, double min_score, FuseSlotsWs ws) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int64_t n_merged;
+    const int lane = threadIdx.x;
+    const int64_t N = n_frames * S;
+    const size_t ks = (size_t)K * S;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int64_t g = blockIdx.x; g < n_frames * C; g += gridDim.x) {
+        const int64_t f = g / C;
+        const int c = (int)(g - f * C) + 1;
+        double* rows = ws.rows + (size_t)g * ks * 5;
+        double* merged = ws.merged + (size_t)g * ks * 5;
+        // 1. scan the frame: gather this category's kept rows, add up the weights of the views that kept any row
+        int n = 0;
+        double wsum = 0.;
+        for (int k = 0; k < K; ++k) {
+            const double wk = weights[k];
+            bool any = false;
+            for (int base = 0; base < S; base += kWave) {
+                const int s = base + lane;
+                bool kept = false, own = false;
+                double x = 0., y = 0., w = 0., h = 0., sc = 0.;
+                if (s < S) {
+                    const int cat = category[(int64_t)k * N + f * S + s];
+                    if (cat >= 1 && cat <= C) {
+                        const double* p = xywhs + (int64_t)k * 5 * N + f * S + s;
+                        w = p[2 * N]; h = p[3 * N];
+                        sc = p[4 * N] * wk;
+                        kept = (w > 0.) && (h > 0.) && (sc >= min_score);
+                        own = kept && cat == c;
+                        if (own) { x = p[0]; y = p[N]; }
+                    }
+                }
+                any = any || __ballot(kept) != 0ull;
+                const unsigned long long mask = __ballot(own);
+                if (own) {
+                    double* r = rows + 5 * (size_t)(n + __popcll(mask & below));
+                    r[0] = sc; r[1] = x; r[2] = y; r[3] = w; r[4] = h;
+                }
+                n += __popcll(mask);
+            }
+            wsum = wsum + (any ? wk : 0.);
+        }
+        __syncthreads();
+        // 2. merge (fuse_group, rows [score, x_left, y_top, w, h])
+        if (n > 0) {
+            const FuseMem m = carve(kLds ? smem : ws.scratch + (size_t)g * ws.scratch_stride, ks);
+            fuse_group(rows, n, wsum, method == 1, thr, m, ks, merged, nullptr, nullptr, &n_merged);
+        } else if (lane == 0) {
+            n_merged = 0;
+        }
+        __syncthreads();
+        // 3. conf > min_score, float boxes, numpy's round(conf, 5); wire order [x, y, w, h, score]
+        const int nm = (int)n_merged;
+        int nk = 0;
+        for (int base = 0; base < nm; base += kWave) {
+            const int r = base + lane;
+            bool keep = false;
+            double v[5] = {0., 0., 0., 0., 0.};
+            if (r < nm) {
+                for (int q = 0; q < 5; ++q) v[q] = merged[5 * (size_t)r + q];
+                keep = v[0] > min_score;
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (keep) {
+                double* o = rows + 5 * (size_t)(nk + __popcll(mask & below));
+                o[0] = v[1]; o[1] = v[2]; o[2] = v[3]; o[3] = v[4];
+                o[4] = round5_numpy(v[0]);
+            }
+            nk += __popcll(mask);
+        }
+        if (lane == 0) ws.count[g] = nk;
+        __syncthreads();
+    }
+}
+
+// pass 2: frame f's groups in ascending category order -> output slots [f * K * S, (f + 1) * K * S); the rest empty
+__global__ __launch_bounds__(kWave) void fuse_slots_compact_kernel(int64_t n_frames, int S, int K, int C, FuseSlotsWs ws,
+                                                                  double* __restrict__ out_xywhs,
+                                                                  int32_t* __restrict__ out_category,
+                                                                  int64_t* __restrict__ out_counts) {
+    const int lane = threadIdx.x;
+    const int64_t ks = (int64_t)K * S;
+    const int64_t NO = n_frames * ks;
+    for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
+        int64_t o = f * ks;
+        for (int c = 0; c < C; ++c) {
+            const int64_t g = f * C + c;
+            const int cnt = ws.count[g];
+            const double* rows = ws.rows + (size_t)g * ks * 5;
+            for (int j = lane; j < cnt; j += kWave) {
+                for (int q = 0; q < 5; ++q) out_xywhs[q * NO + o + j] = rows[5 * (size_t)j + q];
+                out_category[o + j] = c + 1;
+            }
+            o += cnt;
+        }
+        for (int64_t j = o + lane; j < (f + 1) * ks; j += kWave) {
+            for (int q = 0; q < 5; ++q) out_xywhs[q * NO + j] = 0.;
+            out_category[j] = 0;
+        }
+        if (lane == 0) out_counts[f] = o - f * ks;
+    }
+}
+
+bool fuse_slots_shape_ok(int64_t n_frames, int64_t slots, int k_views, int n_categories, int method) {
+    return n_frames >= 0 && slots >= 0 && slots <= kMaxSlots && k_views >= 1 && k_views <= kMaxViews && n_categories >= 1 &&
+           (method == 0 || method == 1) && n_frames <= ((int64_t)1 << 40) / n_categories;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t wt_fuse_slots_workspace(int64_t n_frames, int64_t slots, int k_views, int n_categories, int method) {
+    if (!fuse_slots_shape_ok(n_frames, slots, k_views, n_categories, method)) return 0;
+    const int64_t ks = (int64_t)k_views * slots;
+    size_t total = 0;
+    fuse_slots_ws_layout(nullptr, n_frames * n_categories, (size_t)(ks > 0 ? ks : 1), fuse_slots_use_lds(ks), &total);
+    return total;
+}
+
+int wt_fuse_slots_dev(const double* xywhs, const int32_t* category, int64_t n_frames, int64_t slots, int k_views,
+                      const double* weights, int n_categories, int method, double iou_thresh, double min_score,
+                      double* out_xywhs, int32_t* out_category, int64_t* out_counts, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    WT_TRY(wt::ensure_device());
+    if (method != 0 && method != 1) { wt::set_error("method must be 0 (weighted_fusion) or 1 (nmw), got %d", method); return WT_ERR_INVALID; }
+    if (k_views < 1 || k_views > kMaxViews) { wt::set_error("k_views must be in 1..%d", kMaxViews); return WT_ERR_INVALID; }
+    if (!fuse_slots_shape_ok(n_frames, slots, k_views, n_categories, method)) {
+        wt::set_error("bad slot shape: n_frames %lld, slots %lld, n_categories %d", (long long)n_frames, (long long)slots, n_categories);
+        return WT_ERR_INVALID;
+    }
+    if (n_frames == 0 || slots == 0) return WT_OK;
+    if (!xywhs || !category || !weights || !out_xywhs || !out_category || !out_counts || !workspace) {
+        wt::set_error("null pointer argument"); return WT_ERR_INVALID;
+    }
+    const int64_t ks = (int64_t)k_views * slots;
+    const bool lds = fuse_slots_use_lds(ks);
+    const int64_t n_groups = n_frames * n_categories;
+    size_t need = 0;
+    const FuseSlotsWs ws = fuse_slots_ws_layout((char*)workspace, n_groups, (size_t)ks, lds, &need);
+    if (workspace_bytes < need) {
+        wt::set_error("slot fusion workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
+        return WT_ERR_CAPACITY;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)(n_groups < (1 << 20) ? n_groups : (1 << 20));
+    if (lds)
+        hipLaunchKernelGGL(fuse_slots_kernel<true>, dim3(grid), dim3(kWave), group_mem_bytes((size_t)ks), st, xywhs, category,
+                           n_frames, (int)slots, k_views, weights, n_categories, method, iou_thresh, min_score, ws);
+    else
+        hipLaunchKernelGGL(fuse_slots_kernel<false>, dim3(grid), dim3(kWave), 0, st, xywhs, category, n_frames, (int)slots,
+                           k_views, weights, n_categories, method, iou_thresh, min_score, ws);
+    WT_HIP(hipGetLastError());
+    const unsigned fgrid = (unsigned)(n_frames < (1 << 20) ? n_frames : (1 << 20));
+    hipLaunchKernelGGL(fuse_slots_compact_kernel, dim3(fgrid), dim3(kWave), 0, st, n_frames, (int)slots, k_views, n_categories, ws,
+                       out_xywhs, out_category, out_counts);
+    WT_HIP(hipGetLastError());
+    return WT_OK;
+}
 
 int64_t wt_fuse_groups_lds_rows(void) { return (int64_t)lds_capacity_rows(); }
 

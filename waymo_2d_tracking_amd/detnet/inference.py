@@ -6,6 +6,7 @@
         [--tta x1.5,hflip] [--auto-contrast=1] [-j 8] [-o OUT_DIR] [--resume OUT_DIR/detections.pkl] [--eval --annotations GT.json]
     python -m waymo_2d_tracking_amd.detnet.inference -m MODEL_FILE -i IMAGES_DIR --export merged.json \
         --views 'orig;x1.5,hflip' --views-method soft_nms [--views-weights 1,0.8] [--export-views VIEWS_DIR]
+        (--views-method weighted_fusion_b | nmw: the merge rules of detnet.ensemble_b, float boxes)
     torchrun --nproc-per-node 8 -m waymo_2d_tracking_amd.detnet.inference ...     # the same, started by torchrun
 
 MODEL_FILE is a `{args, kwargs, state_dict}` file of the reference or of this package (nn/__init__.py); the string
@@ -30,6 +31,7 @@ import torch
 from .. import _lib
 
 IMG_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
+FUSE_VIEW_METHODS = ('weighted_fusion_b', 'nmw')        # --views-method: the merge rules of detnet.ensemble_b (devpath.FUSE_METHODS)
 
 
 def arg2bool(v):
@@ -82,8 +84,9 @@ def build_parser():
     parser.add_argument('--data-bgr', action='store_true')
     # several TTA views of one model, merged per (image, category) on the GPU (= --tta V --export per view + detnet.ensemble)
     parser.add_argument('--views', type=str, help="';'-separated --tta specs merged per image, e.g. 'orig;x1.2;x1.5,hflip' (needs --export)")
-    parser.add_argument('--views-method', choices=('weighted_fusion', 'nms', 'soft_nms'), default='weighted_fusion',
-                        help='how the views are merged (detnet.ensemble -m)')
+    parser.add_argument('--views-method', choices=('weighted_fusion', 'nms', 'soft_nms') + FUSE_VIEW_METHODS, default='weighted_fusion',
+                        help='how the views are merged (detnet.ensemble -m; weighted_fusion_b and nmw: detnet.ensemble_b '
+                             '-m weighted_fusion / nmw, float boxes)')
     parser.add_argument('--views-iou-thresh', type=float, default=0.5, help='IOU threshold for merging bboxes')
     parser.add_argument('--views-soft-nms-cut', type=float, default=1.0, help='cutout IoU threshold for soft nms')
     parser.add_argument('--views-min-score', type=float, default=0, help='minimal score to keep')
@@ -129,10 +132,16 @@ def merge_view_rows(image_ids, view_rows, weights, method, iou_thresh, soft_nms_
 
     Every view's rows of an image fill that image's wire slots in file order (S = the most rows any view has for one image);
     devpath.SlotEnsemble merges batch_frames images per launch.  Images come out in the ensemble CLI's order: first appearance
-    over the views' kept rows, view by view (merge_inputs); inside an image categories ascend."""
+    over the views' kept rows, view by view (merge_inputs); inside an image categories ascend.
+
+    method 'weighted_fusion_b' / 'nmw' gives the rows of `python -m detnet.ensemble_b ... -m weighted_fusion / nmw` between the two
+    min_score filters (soft_nms_cut is ignored): the boxes stay float64 and an image's rows are ordered by descending score like
+    that file's (equal 5-decimal scores: ascending category, then the group's order); the scores are numpy-rounded."""
     from ..devpath import SlotEnsemble
     F, K = len(image_ids), len(view_rows)
-    empty = dict(image=np.zeros(0, np.int32), category=np.zeros(0, np.int32), bbox=np.zeros((0, 4), np.int64), score=np.zeros(0))
+    fuse = method in FUSE_VIEW_METHODS
+    box_dtype = np.float64 if fuse else np.int64
+    empty = dict(image=np.zeros(0, np.int32), category=np.zeros(0, np.int32), bbox=np.zeros((0, 4), box_dtype), score=np.zeros(0))
     counts = [np.bincount(r['image'], minlength=F) if len(r['image']) else np.zeros(F, np.int64) for r in view_rows]
     S = int(max([1] + [int(c.max()) for c in counts if len(c)]))
     C = int(max([1] + [int(r['category'].max()) for r in view_rows if len(r['category'])]))
@@ -163,7 +172,7 @@ def merge_view_rows(image_ids, view_rows, weights, method, iou_thresh, soft_nms_
         n = on[:min(B, F - b0)]
         slot = np.concatenate([f * K * S + np.arange(c) for f, c in enumerate(n.tolist())]) if n.sum() else np.zeros(0, np.int64)
         parts.append(dict(image=(b0 + slot // (K * S)).astype(np.int32), category=oc[slot].astype(np.int32),
-                          bbox=ox[0:4, slot].T.astype(np.int64), score=ox[4, slot].copy()))
+                          bbox=ox[0:4, slot].T.astype(box_dtype), score=ox[4, slot].copy()))
     rows = {k: np.concatenate([p[k] for p in parts]) if parts else empty[k] for k in empty}
     # image order of merge_inputs: first appearance over the kept rows (w > 0, h > 0, score * weight >= min_score), view by view
     seen = np.concatenate([np.asarray(r['image'], np.int64)[(r['bbox'][:, 2] > 0) & (r['bbox'][:, 3] > 0) & (r['score'] * w >= min_score)]
@@ -172,6 +181,8 @@ def merge_view_rows(image_ids, view_rows, weights, method, iou_thresh, soft_nms_
     rank = np.full(F, F, np.int64)
     rank[present[np.argsort(first, kind='stable')]] = np.arange(len(present))
     order = np.argsort(rank[rows['image']], kind='stable')
+    if fuse:
+        order = order[np.lexsort((-rows['score'][order], rank[rows['image'][order]]))]          # ensemble_b.output_rows
     return {k: v[order] for k, v in rows.items()}
 
 
@@ -227,7 +238,11 @@ def run_views(args, views_spec):
             write_detections_json(Path(args.export_views) / ('view%d.json' % k), image_ids, r)
     rows = merge_view_rows(image_ids, view_rows, weights, args.views_method, args.views_iou_thresh, args.views_soft_nms_cut,
                            args.views_min_score)
-    write_detections_json(Path(args.export).with_suffix('.json'), image_ids, rows)
+    if args.views_method in FUSE_VIEW_METHODS:
+        from .ensemble_b import write_detections_json as write_float_detections_json
+        write_float_detections_json(Path(args.export).with_suffix('.json'), image_ids, rows)          # float boxes, like ensemble_b
+    else:
+        write_detections_json(Path(args.export).with_suffix('.json'), image_ids, rows)
     print(f'inference done in {time.time() - start:.1f}s, {len(image_ids)} images, views {specs} weights {weights}, '
           f'{sum(len(r["image"]) for r in view_rows)} view rows -> {len(rows["image"])} merged rows')
     return rows

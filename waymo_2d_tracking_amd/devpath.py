@@ -133,8 +133,13 @@ class DeviceEnsemble(object):
         _lib.check(rc, 'wt_ensemble_groups_dev')
 
 
+FUSE_METHODS = {'weighted_fusion_b': 0, 'nmw': 1}        # SlotEnsemble method -> wt_fuse_slots_dev code (detnet/ensemble_b.py's rules)
+
+
 class SlotEnsemble(object):
     """wt_ensemble_slots_dev: K views' wire slots of the same frames -> merged wire slots, on the caller's stream.
+    method 'weighted_fusion_b' / 'nmw' runs wt_fuse_slots_dev instead (weighted boxes fusion / NMW: float boxes, soft_nms_cut
+    ignored); shapes and conventions are the same.
 
     Inputs are xywhs (K, 5, n_frames * slots) float64 and category (K, n_frames * slots) int32 device tensors (the layout
     DetectTrackPipeline fills per view); outputs are (5, n_frames * K * slots), (n_frames * K * slots) and per-frame row
@@ -149,14 +154,18 @@ class SlotEnsemble(object):
         self.lib = _lib.lib()
         self.dev = torch.device(device)
         self.n_frames, self.slots, self.k, self.n_categories = int(n_frames), int(slots), len(weights), int(n_categories)
-        self.method = METHODS[method] if isinstance(method, str) else int(method)
+        # 'weighted_fusion_b' / 'nmw' (the names of detnet/evaluate.py's B_METHODS): wt_fuse_slots_dev, no soft_nms_cut
+        self.fuse = isinstance(method, str) and method in FUSE_METHODS
+        self.method = FUSE_METHODS[method] if self.fuse else (METHODS[method] if isinstance(method, str) else int(method))
         self.thr, self.cut, self.min_score = float(iou_thresh), float(soft_nms_cut), float(min_score)
         self.weights = torch.tensor([float(w) for w in weights], dtype=torch.float64, device=self.dev)
-        ws = int(self.lib.wt_ensemble_slots_workspace(C.c_int64(self.n_frames), C.c_int64(self.slots), C.c_int(self.k),
-                                                      C.c_int(self.n_categories), C.c_int(self.method)))
+        sizer = self.lib.wt_fuse_slots_workspace if self.fuse else self.lib.wt_ensemble_slots_workspace
+        ws = int(sizer(C.c_int64(self.n_frames), C.c_int64(self.slots), C.c_int(self.k), C.c_int(self.n_categories),
+                       C.c_int(self.method)))
         if ws == 0:
-            raise ValueError('wt_ensemble_slots_workspace: bad shape (%d frames, %d slots, %d views, %d categories, method %d)'
-                             % (self.n_frames, self.slots, self.k, self.n_categories, self.method))
+            raise ValueError('%s: bad shape (%d frames, %d slots, %d views, %d categories, method %d)'
+                             % ('wt_fuse_slots_workspace' if self.fuse else 'wt_ensemble_slots_workspace', self.n_frames,
+                                self.slots, self.k, self.n_categories, self.method))
         self.ws_bytes = ws
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.dev)
         self.out_slots = self.n_frames * self.k * self.slots
@@ -178,6 +187,13 @@ class SlotEnsemble(object):
         ox, oc, on = out if out is not None else self.outputs()
         if tuple(ox.shape) != (5, self.out_slots) or tuple(oc.shape) != (self.out_slots,) or on.numel() < self.n_frames:
             raise ValueError('output tensors have the wrong shape')
+        if self.fuse:
+            rc = self.lib.wt_fuse_slots_dev(
+                _dp(xywhs), _dp(category), C.c_int64(self.n_frames), C.c_int64(self.slots), C.c_int(self.k), _dp(self.weights),
+                C.c_int(self.n_categories), C.c_int(self.method), C.c_double(self.thr), C.c_double(self.min_score), _dp(ox),
+                _dp(oc), _dp(on), _dp(self.workspace), C.c_size_t(self.ws_bytes), _stream())
+            _lib.check(rc, 'wt_fuse_slots_dev')
+            return ox, oc, on
         rc = self.lib.wt_ensemble_slots_dev(
             _dp(xywhs), _dp(category), C.c_int64(self.n_frames), C.c_int64(self.slots), C.c_int(self.k), _dp(self.weights),
             C.c_int(self.n_categories), C.c_int(self.method), C.c_double(self.thr), C.c_double(self.cut),
