@@ -903,6 +903,51 @@ int wt_det_eval_host(int64_t n_gt, const double* gx1, const double* gy1, const d
                      double* ap, double* ar, int64_t* npos, int64_t* tp, int64_t* fp,
                      uint8_t* tp_flag, int64_t* match_gt, int64_t* order, int64_t* class_offsets, int64_t* ctp, int64_t* cfp);
 
+/* =================================================================================================
+ * COCO detection evaluation (AP@[.5:.95], AP50, AP75, by area, AR@1/10/100; the definition is DESIGN.md section 28)
+ * ================================================================================================= */
+
+/* Scores K >= 1 detection results against one ground truth with the COCO rule: per (image, category) the detections by
+ * descending score (equal scores in input order), the first max_dets[last] of them; per area range and IoU threshold a greedy
+ * one-to-one match to the best ground-truth box that is still free (ties to the later box), not-ignored boxes before ignored
+ * ones, crowd boxes never used up; precision read at n_rec recall thresholds from the curve made non-increasing from the right.
+ *
+ * Ground truth: SoA rows in image order - gx, gy, gw, gh pixel [x, y, w, h] and g_area float64, g_cat int32 category index in
+ * 0..n_cats-1, g_crowd uint8 - with the CSR offsets image_gt_offsets (n_images + 1).
+ * Results: the K sets concatenated; set k owns rows set_row_offsets[k] .. set_row_offsets[k + 1], in image order (input order
+ * inside an image), image_det_offsets[k * (n_images + 1) + i] = offsets of image i inside the set.  score, x, y, w, h float64
+ * pixels, category int32 index in 0..n_cats-1.  image_mask: NULL, or (K, n_images) uint8 - 0 takes the image out of result k
+ * (its rows and its ground truth).
+ * Host arrays, read before the call returns (they travel as kernel arguments, so the device form can be captured in a graph):
+ * thr (n_thr <= 16) IoU thresholds, rec (n_rec <= 128) ascending recall thresholds, area_rng (n_area <= 4, 2) inclusive
+ * [lo, hi] pairs with n_area * n_thr <= 64, max_dets (n_maxdet <= 4) ascending, at most 128.  No limit on the rows of one
+ * image or problem; K x n_images x n_cats below 2^26 and K x n_cats x n_area x n_maxdet x n_thr below 2^24 (one workgroup
+ * each; more is WT_ERR_CAPACITY).
+ * Outputs: precision (K, n_thr, n_rec, n_cats, n_area, n_maxdet) and recall (K, n_thr, n_cats, n_area, n_maxdet) float64, -1
+ *          where the category has no not-ignored ground truth; npig (K, n_cats, n_area) int64, that count;
+ *          per row, each may be NULL: rank (n_det) int32 position in its problem, -1 = beyond max_dets[last] or took no part;
+ *          match_gt (n_det, n_area, n_thr) int64 ground-truth row, -1 none; ignore (n_det, n_area, n_thr) uint8 (together).
+ * The device form takes device pointers (except the four host arrays), never synchronises or allocates and reports 0 or a
+ * WT_ERR_* in status_dev (device int32); it does not check the layout or the numbers and only stays in bounds on non-finite
+ * rows; the host form checks both (WT_ERR_INVALID names the set / image / row).  Every refusal comes before any launch. */
+size_t wt_det_coco_workspace(int32_t k_sets, int64_t n_images, int32_t n_cats, int32_t n_thr, int32_t n_rec, int32_t n_area, int32_t n_maxdet,
+                             int64_t n_gt, int64_t n_det);
+int wt_det_coco_dev(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh, const double* g_area,
+                    const int32_t* g_cat, const uint8_t* g_crowd, int64_t n_images, const int64_t* image_gt_offsets,
+                    int32_t k_sets, int64_t n_det, const int64_t* set_row_offsets, const int64_t* image_det_offsets,
+                    const double* score, const double* x, const double* y, const double* w, const double* h, const int32_t* category,
+                    const uint8_t* image_mask, int32_t n_cats, int32_t n_thr, const double* thr, int32_t n_rec, const double* rec,
+                    int32_t n_area, const double* area_rng, int32_t n_maxdet, const int32_t* max_dets,
+                    double* precision, double* recall, int64_t* npig, int32_t* rank, int64_t* match_gt, uint8_t* ignore,
+                    int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_det_coco_host(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh, const double* g_area,
+                     const int32_t* g_cat, const uint8_t* g_crowd, int64_t n_images, const int64_t* image_gt_offsets,
+                     int32_t k_sets, const int64_t* set_row_offsets, const int64_t* image_det_offsets,
+                     const double* score, const double* x, const double* y, const double* w, const double* h, const int32_t* category,
+                     const uint8_t* image_mask, int32_t n_cats, int32_t n_thr, const double* thr, int32_t n_rec, const double* rec,
+                     int32_t n_area, const double* area_rng, int32_t n_maxdet, const int32_t* max_dets,
+                     double* precision, double* recall, int64_t* npig, int32_t* rank, int64_t* match_gt, uint8_t* ignore);
+
 /* --- Waymo Open Dataset protobuf emit (csrc/waymo_proto.hip; host code) -----------------------------------
  * metrics.Objects - and with submission != 0 the Submission envelope around it - written straight from columns: replaces
  * the per-object message building of /root/reference/coco_to_waymo.py:16-82 (create_pd_object / create_pb_submission) and

@@ -40,6 +40,7 @@ UNITS = {
     'track_xclass.hip': ['-ffp-contract=off'],         # cross-class suppression: the IoU terms in their order, frac * n_weak one multiplication
     'track_split.hip': ['-ffp-contract=off'],          # track splitting: the extrapolations x + ((x - xo) / slots) * n unfused, the same float64 IoU
     'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation
+    'det_coco_eval.hip': ['-ffp-contract=off'],      # COCO AP / AR: float64 IoU, precision and recall rounded operation by operation
     'det_roialign.hip': [],
     'det_nms.hip': [],
     'det_deform.hip': [],
