@@ -948,6 +948,84 @@ int wt_det_coco_host(int64_t n_gt, const double* gx, const double* gy, const dou
                      int32_t n_area, const double* area_rng, int32_t n_maxdet, const int32_t* max_dets,
                      double* precision, double* recall, int64_t* npig, int32_t* rank, int64_t* match_gt, uint8_t* ignore);
 
+/* =================================================================================================
+ * Track layouts (the two steps between the tracker, the post-passes and the metrics; the definitions are DESIGN.md section 29)
+ * ================================================================================================= */
+
+/* wt_tracks_layout_*: R >= 1 tracker outputs, each in buffers of its own, -> the shared layout of the post-passes ("Track
+ * refinement" above: "Results: the R sets concatenated, SoA ...") without the rows leaving the device.
+ *
+ * Input of the device form: in_tables, device int64 (R, 7) - per result the addresses of out_frame int64 (the global frame slot),
+ * out_category int32, out_bbox (n, 4) float64, out_score float64, out_object_id int64 and of the row count, a device int64, as
+ * wt_track_streams_dev / wt_track_streams_byte_dev leave them, and the row capacity of those buffers.  A negative count is the
+ * tracker's error status and becomes the call's status; a count above its capacity, or more rows in all than out_cap, is
+ * WT_ERR_CAPACITY.  The rows of a result must ascend by frame slot (the tracker's do); the kernels check that they do, that the
+ * slots lie in 0..n_frames-1 and the categories in 1..n_classes, and that stream_frame_offsets (n_streams + 1, device) cover
+ * the slots: WT_ERR_INVALID otherwise.  On any status the outputs are unspecified, and nothing is written out of bounds.  The
+ * same trajectory twice in one slot is not checked, as in the other device forms.
+ * Output, every array sized by the caller: x, y, w, h, score float64 and category int32 (out_cap), bit-copies of the input;
+ * local int32 (out_cap) = the row's trajectory - the rows of one (result, stream) with one object id - numbered from 0 by first
+ * appearance in row order; set_row_offsets (R + 1); frame_row_offsets (R, n_frames + 1); n_traj (R, n_streams) int32 and its
+ * running sum traj_offsets (R * n_streams + 1) int64; totals (3) int64 = the rows of all results, n_traj_total, max_traj;
+ * traj_object_id (out_cap) int64, indexed like traj_offsets = the object id of the trajectory's first row.
+ * Integers and bit-copies only: the answer is exact and the same for every launch.
+ *
+ * One workgroup per (result, stream) keeps an open-addressing table of the stream's ids: in LDS (lds_slots slots) while the
+ * stream has at most lds_rows rows, in the workspace (2 x its rows) above; wt_tracks_layout_limits reports both and scan_rows,
+ * the rows a workgroup scans per step.  wt_tracks_layout_probe is the first slot the table tries for `id` at `capacity` slots
+ * (-1 for a capacity below 1), the later ones following linearly: host code, for tests that need ids which collide.
+ * The device form takes device pointers, is stream-ordered, never allocates or synchronises, and reports 0 or a WT_ERR_* in
+ * status_dev (device int32).  Bad arguments are WT_ERR_INVALID, a workspace below wt_tracks_layout_workspace() bytes, more than
+ * 65535 results or 2^31 (result, stream) pairs WT_ERR_CAPACITY, all before any launch; the sizer returns 0 for a bad shape.
+ * The host form takes the R results back to back - in_row_offsets (R + 1), then the five columns - checks them (WT_ERR_INVALID
+ * names the result and the row), stages, calls the device form and copies back; its outputs hold in_row_offsets[R] rows. */
+void wt_tracks_layout_limits(int32_t* lds_rows, int32_t* lds_slots, int32_t* scan_rows);
+int32_t wt_tracks_layout_probe(int64_t id, int32_t capacity);
+size_t wt_tracks_layout_workspace(int32_t r_sets, int32_t n_streams, int64_t out_cap);
+int wt_tracks_layout_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets, int32_t r_sets, const int64_t* in_tables,
+                         int32_t n_classes, int64_t out_cap,
+                         double* x, double* y, double* w, double* h, double* score, int32_t* category, int32_t* local,
+                         int64_t* set_row_offsets, int64_t* frame_row_offsets, int32_t* n_traj, int64_t* traj_offsets, int64_t* totals,
+                         int64_t* traj_object_id, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_tracks_layout_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets, int32_t r_sets, const int64_t* in_row_offsets,
+                          const int64_t* in_frame, const int32_t* in_category, const double* in_bbox, const double* in_score, const int64_t* in_object_id,
+                          int32_t n_classes,
+                          double* x, double* y, double* w, double* h, double* score, int32_t* category, int32_t* local,
+                          int64_t* set_row_offsets, int64_t* frame_row_offsets, int32_t* n_traj, int64_t* traj_offsets, int64_t* totals,
+                          int64_t* traj_object_id);
+
+/* wt_tracks_to_eval_*: K >= 1 results in the shared layout -> the rows in the order wt_mot_*_dev take them ("MOT evaluation"
+ * above: "Results: the K sets concatenated ...").
+ *
+ * Input: set_row_offsets (K + 1, the first 0), frame_row_offsets (K, n_frames + 1) - rows behind a set's last offset take no
+ * part -, category and local int32, and the boxes x, y, w, h float64 with row i at [i * box_stride]: 1 for the columns
+ * wt_tracks_layout_* writes, 4 for out_bbox, out_bbox + 1, ... of wt_refine_tracks_emit_dev, whose job_row_offsets and
+ * out_frame_row_offsets are the two offset arrays.  slot_map (n_frames) int64: per frame slot the ground truth's frame slot, or
+ * -1 where the ground truth has no such frame or stream; no ground-truth slot is named twice.
+ * Output, per result in its input rows' place: first the rows on a known slot with a category in 1..n_classes, by ground-truth
+ * slot and in input order inside a slot, then the others in input order.  out_x, out_y, out_w, out_h float64 (bit-copies),
+ * out_category, out_h_id int32 (= local: equal inside a (result, stream) <=> one trajectory, all wt_mot_eval_* asks of it),
+ * out_order int64 = the output row's input row inside its result (n_rows each); out_set_row_offsets (K + 1);
+ * frame_hyp_offsets (K, n_gt_frames + 1); max_frame_boxes, one int64 = the most rows of one class on one known slot.
+ * The device form takes device pointers and n_rows = an upper bound of set_row_offsets[K] that the outputs hold, is
+ * stream-ordered, never allocates or synchronises, and reports 0 or WT_ERR_INVALID (offsets that do not fit the rows, a map
+ * entry outside -1..n_gt_frames-1 or named twice, a negative local index) in status_dev; the outputs are then unspecified and
+ * nothing is written out of bounds.  Bad arguments are WT_ERR_INVALID and a workspace below wt_tracks_to_eval_workspace() bytes
+ * WT_ERR_CAPACITY before any launch.  The host form checks the layout and the map (WT_ERR_INVALID names the result or the
+ * slots), stages, calls the device form and copies back. */
+size_t wt_tracks_to_eval_workspace(int32_t k_sets, int64_t n_rows);
+int wt_tracks_to_eval_dev(int64_t n_frames, int32_t k_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                          const double* x, const double* y, const double* w, const double* h, int64_t box_stride,
+                          const int32_t* category, const int32_t* local, const int64_t* slot_map, int64_t n_gt_frames, int32_t n_classes,
+                          double* out_x, double* out_y, double* out_w, double* out_h, int32_t* out_category, int32_t* out_h_id,
+                          int64_t* out_set_row_offsets, int64_t* frame_hyp_offsets, int64_t* out_order, int64_t* max_frame_boxes,
+                          int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_tracks_to_eval_host(int64_t n_frames, int32_t k_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                           const double* x, const double* y, const double* w, const double* h, int64_t box_stride,
+                           const int32_t* category, const int32_t* local, const int64_t* slot_map, int64_t n_gt_frames, int32_t n_classes,
+                           double* out_x, double* out_y, double* out_w, double* out_h, int32_t* out_category, int32_t* out_h_id,
+                           int64_t* out_set_row_offsets, int64_t* frame_hyp_offsets, int64_t* out_order, int64_t* max_frame_boxes);
+
 /* --- Waymo Open Dataset protobuf emit (csrc/waymo_proto.hip; host code) -----------------------------------
  * metrics.Objects - and with submission != 0 the Submission envelope around it - written straight from columns: replaces
  * the per-object message building of /root/reference/coco_to_waymo.py:16-82 (create_pd_object / create_pb_submission) and

@@ -39,6 +39,7 @@ UNITS = {
     'track_dedup.hip': ['-ffp-contract=off'],          # track deduplication: the same float64 IoU, dup_frac * min(n) one multiplication
     'track_xclass.hip': ['-ffp-contract=off'],         # cross-class suppression: the IoU terms in their order, frac * n_weak one multiplication
     'track_split.hip': ['-ffp-contract=off'],          # track splitting: the extrapolations x + ((x - xo) / slots) * n unfused, the same float64 IoU
+    'tracks_layout.hip': ['-ffp-contract=off'],        # track layouts: integers and bit-copies only; the flag matches the units whose headers it includes
     'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_coco_eval.hip': ['-ffp-contract=off'],      # COCO AP / AR: float64 IoU, precision and recall rounded operation by operation
     'det_roialign.hip': [],

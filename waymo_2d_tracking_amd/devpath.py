@@ -23,15 +23,22 @@ def _stream():
 class DeviceTracker(object):
     """wt_track_streams_dev on tensors already in HBM (layout: include/waymotrack.h, wt_track_streams_host)."""
 
-    def __init__(self, packed, iou_threshold, max_age, min_hits, score_threshold=None, device='cuda'):
+    _INPUTS = ('x', 'y', 'w', 'h', 'score', 'category', 'frame_off', 'stream_off', 'clip_w', 'clip_h')
+
+    def __init__(self, packed, iou_threshold, max_age, min_hits, score_threshold=None, device='cuda', share=None):
+        """share: a DeviceTracker of the same `packed` whose input tensors this one reads instead of uploading its own."""
         self.lib = _lib.lib()
         dev = torch.device(device)
-        f64 = lambda k: torch.from_numpy(np.ascontiguousarray(packed[k], dtype=np.float64)).to(dev)
-        self.x, self.y, self.w, self.h, self.score = f64('x'), f64('y'), f64('w'), f64('h'), f64('score')
-        self.category = torch.from_numpy(np.ascontiguousarray(packed['category'], dtype=np.int32)).to(dev)
-        self.frame_off = torch.from_numpy(np.ascontiguousarray(packed['frame_det_offsets'], dtype=np.int64)).to(dev)
-        self.stream_off = torch.from_numpy(np.ascontiguousarray(packed['stream_frame_offsets'], dtype=np.int64)).to(dev)
-        self.clip_w, self.clip_h = f64('clip_w'), f64('clip_h')
+        if share is not None:
+            for name in self._INPUTS:
+                setattr(self, name, getattr(share, name))
+        else:
+            f64 = lambda k: torch.from_numpy(np.ascontiguousarray(packed[k], dtype=np.float64)).to(dev)
+            self.x, self.y, self.w, self.h, self.score = f64('x'), f64('y'), f64('w'), f64('h'), f64('score')
+            self.category = torch.from_numpy(np.ascontiguousarray(packed['category'], dtype=np.int32)).to(dev)
+            self.frame_off = torch.from_numpy(np.ascontiguousarray(packed['frame_det_offsets'], dtype=np.int64)).to(dev)
+            self.stream_off = torch.from_numpy(np.ascontiguousarray(packed['stream_frame_offsets'], dtype=np.int64)).to(dev)
+            self.clip_w, self.clip_h = f64('clip_w'), f64('clip_h')
         self.n_dets = int(packed['x'].size)
         self.n_frames = int(packed['frame_det_offsets'].size - 1)
         self.n_streams = int(packed['stream_frame_offsets'].size - 1)
@@ -78,8 +85,8 @@ class DeviceTrackerByte(DeviceTracker):
     """wt_track_streams_byte_dev (second association with low-score detections) on tensors already in HBM; `score_threshold` is
     the high threshold, and `packed` holds the detections down to `low_score_threshold`."""
 
-    def __init__(self, packed, iou_threshold, max_age, min_hits, score_threshold, low_score_threshold, low_iou_threshold, device='cuda'):
-        DeviceTracker.__init__(self, packed, iou_threshold, max_age, min_hits, score_threshold, device)
+    def __init__(self, packed, iou_threshold, max_age, min_hits, score_threshold, low_score_threshold, low_iou_threshold, device='cuda', share=None):
+        DeviceTracker.__init__(self, packed, iou_threshold, max_age, min_hits, score_threshold, device, share)
         from .tracking.utils import per_class
         self.low_score = _lib.as_f64(per_class(low_score_threshold, self.params.n_classes, 'low_score_threshold'))
         self.low_iou = _lib.as_f64(per_class(low_iou_threshold, self.params.n_classes, 'low_iou_threshold'))

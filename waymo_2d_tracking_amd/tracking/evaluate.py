@@ -3,7 +3,7 @@
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json TRACKS.json [TRACKS2.json ...]
         [--iou-threshold 0.7,0.5,0.5,0.5] [--json OUT] [--identity] [--hota] [--coverage]
     python -m waymo_2d_tracking_amd.tracking.evaluate --annotations GT.json --sweep DETECTIONS.json
-        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--low-score-grid 0.2,0.4 --low-iou-grid 0.3,0.5] [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--coverage] [--rank-by idf1|hota|mt]
+        --score-grid 0.5:1.0:0.05 --iou-grid 0.0,0.01,0.1,0.3 --max-age 1,2,3 --min-hits 0,1 [--low-score-grid 0.2,0.4 --low-iou-grid 0.3,0.5] [--link-gap-grid 0,2,4 --link-iou-grid 0.3,0.5] [--dedup-frames-grid 0,3,5 --dedup-iou-grid 0.5,0.7] [--gap-grid 0,1,2 --min-len-grid 1,2,3] [--identity] [--hota] [--coverage] [--rank-by idf1|hota|mt] [--device-chain]
 
 The metric is CLEAR-MOT (Bernardin & Stiefelhagen 2008) per class and Waymo difficulty level; DESIGN.md ("Tracking metric")
 has the exact definition.  Every (result, segment, camera, class) is an independent problem and one wavefront of the HIP
@@ -13,7 +13,8 @@ section 18) through ``wt_mot_identity_host``: per problem one trajectory-by-traj
 --hota adds HOTA / DetA / AssA / LocA (Luiten et al. 2021) through ``wt_mot_hota_host``: one wavefront per
 problem and difficulty level, one assignment per frame scored at 19 localisation thresholds.  --coverage adds what became of every
 ground-truth trajectory (mostly tracked / partially tracked / mostly lost, fragmentations) through
-``wt_mot_coverage_host``, which reads the matches of the CLEAR-MOT kernel where they lie in device memory.  No arithmetic of the metric runs on the host; without a GPU the calls fail.
+``wt_mot_coverage_host``, which reads the matches of the CLEAR-MOT kernel where they lie in device memory.  --device-chain runs a sweep
+of the tracker, refinement and MOTA with the rows resident in HBM from the detections to the count tables (tracking/chain.py).  No arithmetic of the metric runs on the host; without a GPU the calls fail.
 """
 import argparse
 import collections
@@ -420,8 +421,8 @@ class _DeviceForm(object):
 class DeviceEvaluation(_DeviceForm):
     """The same evaluation with everything resident in HBM (torch tensors own the memory): ``launch()`` enqueues one
     wt_mot_eval_dev on the current torch stream and returns at once, ``results()`` synchronises and reads the outputs back.
-    This is the form a device-resident sweep (tracker output scored without leaving the GPU) builds on; the layout checks of
-    the host form are done here when the inputs are packed."""
+    This is the form a device-resident sweep (tracker output scored without leaving the GPU) builds on - tracking/chain.py, through
+    ``from_device()``; the layout checks of the host form are done here when the inputs are packed."""
     name = 'wt_mot_eval_dev'
 
     def __init__(self, gt, tracks_list, iou_threshold=DEFAULT_IOU_THRESHOLD):
@@ -429,13 +430,39 @@ class DeviceEvaluation(_DeviceForm):
         torch = self.torch
         self.max_boxes = max_frame_boxes(gt, self.p, self.n_classes)
         self.g['gt_id'], self.h['h_id'] = self.up(gt['gt_id']), self.up(self.p['h_id'])
-        self.counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 5), torch.int64)
-        self.iou_sum = self.zeros((self.K, self.n_streams, self.n_classes, 2), torch.float64)
         self.hyp_match = self.zeros(max(1, self.n_hyp), torch.int64)
         self.hyp_switch = self.zeros(max(1, self.n_hyp), torch.uint8)
+        self._outputs()
+
+    @classmethod
+    def from_device(cls, gt, columns, n_hyp, hyp_max_boxes, iou_threshold=DEFAULT_IOU_THRESHOLD, g=None):
+        """The same form over result columns that are in HBM already: `columns` holds the output tensors of wt_tracks_to_eval_dev by
+        the names x, y, w, h, category, h_id, set_row_offsets and frame_hyp_offsets (K, frames + 1), n_hyp is their row count and
+        hyp_max_boxes the scalar that call left (the result side of max_frame_boxes; the ground-truth side is computed as in the
+        other form).  g: the ground-truth tensors ``self.g`` of an earlier form over the same `gt`, to be used again instead of
+        uploaded.  No per-row output is kept: results() gives the tables and ignored_rows, read off the offsets."""
+        import torch
+        self = cls.__new__(cls)
+        self.torch, self.lib, self.gt, self.p = torch, _lib.lib(), gt, None
+        self.thr = _lib.as_f64(iou_threshold)
+        self.n_classes = int(self.thr.size)
+        self.K, self.n_streams, self.n_hyp = int(columns['frame_hyp_offsets'].shape[0]), len(gt['stream_keys']), int(n_hyp)
+        self.device = torch.device('cuda', torch.cuda.current_device())
+        self.g = g if g is not None else dict((n, self.up(gt[n])) for n in _BOX + ('category', 'level', 'frame_gt_offsets', 'stream_frame_offsets', 'gt_id'))
+        self.h = dict(columns)
+        self.status = self.zeros(1, torch.int32)
+        self.max_boxes = max(int(hyp_max_boxes), max_frame_boxes(gt, {'frame_hyp_offsets': np.zeros((0, 1), np.int64)}, self.n_classes))
+        self.hyp_match = self.hyp_switch = None
+        self._outputs()
+        return self
+
+    def _outputs(self):
+        torch = self.torch
+        self.counts = self.zeros((self.K, self.n_streams, self.n_classes, 2, 5), torch.int64)
+        self.iou_sum = self.zeros((self.K, self.n_streams, self.n_classes, 2), torch.float64)
         self.lib.wt_mot_eval_workspace.restype = C.c_size_t
         self.ws_bytes = int(self.lib.wt_mot_eval_workspace(C.c_int32(self.K), C.c_int32(self.n_streams), C.c_int32(self.n_classes),
-                                                           C.c_int64(self.max_boxes), C.c_int32(int(gt['max_gt_ids']))))
+                                                           C.c_int64(self.max_boxes), C.c_int32(int(self.gt['max_gt_ids']))))
         if not self.ws_bytes:
             _lib.check(4, 'wt_mot_eval_workspace')
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
@@ -445,12 +472,20 @@ class DeviceEvaluation(_DeviceForm):
         rc = self.lib.wt_mot_eval_dev(
             *self.leading_args(self.g['gt_id'], self.h['h_id']),
             C.c_int32(self.n_classes), _lib.ptr(self.thr), C.c_int64(self.max_boxes), C.c_int32(int(self.gt['max_gt_ids'])),
-            d(self.counts), d(self.iou_sum), d(self.hyp_match), d(self.hyp_switch), d(self.status),
+            d(self.counts), d(self.iou_sum), d(self.hyp_match) if self.hyp_match is not None else None,
+            d(self.hyp_switch) if self.hyp_switch is not None else None, d(self.status),
             d(self.ws), C.c_size_t(self.ws_bytes), C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, self.name)
 
     def results(self, per_row=False):
         self.wait()
+        if self.p is None:                               # from_device: the rows stayed in HBM, so there is nothing per row to give
+            if per_row:
+                raise ValueError('a DeviceEvaluation over device-resident columns keeps no per-row output')
+            rows = np.diff(self.h['set_row_offsets'].cpu().numpy()[:self.K + 1])
+            on = self.h['frame_hyp_offsets'][:, -1].cpu().numpy()
+            counts, iou_sum = self.counts.cpu().numpy(), self.iou_sum.cpu().numpy()
+            return [MotResult(counts[k], iou_sum[k], int(rows[k] - on[k]), self.gt['stream_keys']) for k in range(self.K)]
         return _results(self.gt, self.p, self.counts.cpu().numpy(), self.iou_sum.cpu().numpy(),
                         self.hyp_match.cpu().numpy()[:self.n_hyp], self.hyp_switch.cpu().numpy()[:self.n_hyp], per_row)
 
@@ -1260,7 +1295,18 @@ def _detections(path):
     return entries
 
 
-def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False, coverage=False):
+def _chain_scores(packed, gt, grid, plans, live, iou_threshold, n_classes):
+    """The MotResults of every setting through tracking/chain.py, in the order of sweep_settings(); ValueError for what it does not carry."""
+    beyond = ['the %s pass (--%s-grid)' % (p.name, p.axes[0].key.replace('_', '-')) for p in PASSES if plans[p.name].on and p.name != 'refine']
+    beyond += ['the %s metric (--%s)' % (m.name, m.option) for m in live if m.option is not None]
+    if beyond:
+        raise ValueError('the device chain carries the tracker, refinement and MOTA, not ' + ', '.join(beyond))
+    chain = importlib.import_module('.chain', __package__).DeviceChain(packed, gt, n_classes, iou_threshold)
+    return chain.run([args for _, args in _tracked_points(grid, plans['second'])], plans['refine'].jobs if plans['refine'].on else None)
+
+
+def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_classes=4, identity=False, rank_by='mota', hota=False, coverage=False,
+          device_chain=False):
     """Track `detections_path` under every setting of `grid`, score all results in ONE call per metric and rank the settings.
 
     grid: lists 'score' and 'iou' (the tracker's thresholds, one grid point for all classes), 'max_age' and 'min_hits', and
@@ -1273,6 +1319,9 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
     MOTA is always scored; identity / hota / coverage (and the rank_by that needs them: 'idf1', 'hota', 'mt') add their metric's
     keys to every ranked row (METRICS).  Ranking by anything but 'mota' is not the argmax of the ALL score over one shared grid
     point: per-class flags can only be tuned per class (DESIGN.md sections 18, 19 and 27).
+    device_chain: run and score through tracking/chain.py - the rows of a result stay in HBM from the tracker to the count tables
+    (DESIGN.md section 29).  The chain carries the tracker, its second association, refinement and MOTA; a grid that switches on
+    another pass or metric is a ValueError that names it.  Settings, results, ranked and best equal the other route's.
     Returns {'settings': [...], 'results': [MotResult...], 'ranked': {level: [...]}, 'best': {level: {...}}} and, per further
     metric, its results under 'id_results', 'hota_results', 'coverage_results'."""
     if rank_by not in [m.name for m in METRICS]:
@@ -1281,11 +1330,14 @@ def sweep(detections_path, gt, grid, iou_threshold=DEFAULT_IOU_THRESHOLD, n_clas
         gt = load_ground_truth(gt)
     packed = T.pack_streams(_detections(detections_path))
     settings, plans = sweep_settings(grid)
-    tracks = run_settings(packed, grid, plans, n_classes)
     asked = {'identity': identity, 'hota': hota, 'coverage': coverage}
     live = [m for m in METRICS if m.option is None or asked[m.option] or rank_by == m.name]
-    packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for all metrics
-    scored = dict((m.name, globals()[m.evaluate](gt, tracks, iou_threshold, packed=packed_results)) for m in live)
+    if device_chain:
+        scored = {'mota': _chain_scores(packed, gt, grid, plans, live, iou_threshold, n_classes)}
+    else:
+        tracks = run_settings(packed, grid, plans, n_classes)
+        packed_results = pack_results(gt, tracks, len(iou_threshold))       # once, for all metrics
+        scored = dict((m.name, globals()[m.evaluate](gt, tracks, iou_threshold, packed=packed_results)) for m in live)
     group = len(grid['score']) * len(grid['iou']) * math.prod(len(plan.points) for plan in plans.values())
     ranked, best = rank_settings(settings, plans, scored, rank_by, group, n_classes)
     out = {'settings': settings, 'results': scored['mota'], 'ranked': ranked, 'best': best}
@@ -1329,6 +1381,7 @@ def build_parser():
     parser.add_argument('--identity', action='store_true', help='also score identity preservation: IDF1 / IDP / IDR / IDTP / IDFP / IDFN')
     parser.add_argument('--hota', action='store_true', help='also score HOTA / DetA / AssA / LocA over the 19 localisation thresholds')
     parser.add_argument('--coverage', action='store_true', help='also score trajectory coverage: mostly tracked / partially tracked / mostly lost, fragmentations')
+    parser.add_argument('--device-chain', action='store_true', help='sweep: keep the rows in HBM from the tracker to the count tables (tracker, refinement and MOTA only)')
     parser.add_argument('--rank-by', choices=tuple(m.name for m in METRICS), default='mota',
                         help='what the sweep ranks by (idf1 implies --identity, hota implies --hota, mt implies --coverage)')
     return parser
@@ -1344,7 +1397,8 @@ def main(argv=None):
         for p in (SECOND,) + PASSES:
             grid.update((a.key, a.parse(getattr(args, a.key + '_grid'))) for a in p.axes)
             grid.update((s.key, getattr(args, s.key)) for s in p.singles)
-        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), rank_by=args.rank_by, **dict((m.option, True) for m in live[1:]))
+        res = sweep(args.sweep, gt, grid, args.iou_threshold, len(args.iou_threshold), rank_by=args.rank_by, device_chain=args.device_chain,
+                    **dict((m.option, True) for m in live[1:]))
         for lv in LEVELS:
             print('LEVEL_%d: %d settings tracked, best per class combined for each (max_age, min_hits)' % (lv, len(res['settings'])))
             for r in res['ranked'][lv][:args.top]:

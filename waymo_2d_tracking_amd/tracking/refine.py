@@ -27,7 +27,11 @@ def _per_class(value, n_classes):
 
 def _prepare(packed, outs, jobs, n_classes):
     """Everything wt_refine_tracks_* takes, as numpy arrays (include/waymotrack.h), after the checks that need names."""
-    p = TS.prepare(packed, outs, jobs, n_classes, 'refine')
+    return _job_columns(TS.prepare(packed, outs, jobs, n_classes, 'refine'), jobs, n_classes)
+
+
+def _job_columns(p, jobs, n_classes):
+    """the job parameters of wt_refine_tracks_*, checked, added to the layout `p`"""
     J = p['J']
     p['job_max_gap'] = np.asarray([_per_class(j.get('max_gap', 0), n_classes) for j in jobs], dtype=np.int32).reshape(J, n_classes)
     p['job_min_len'] = np.asarray([_per_class(j.get('min_len', 1), n_classes) for j in jobs], dtype=np.int32).reshape(J, n_classes)
@@ -88,7 +92,11 @@ class DeviceRefine(TS.DeviceStage):
     name = 'wt_refine_tracks_plan_dev'
 
     def __init__(self, packed, outs, jobs, n_classes=4):
-        TS.DeviceStage.__init__(self, _prepare(packed, outs, jobs, n_classes), _COLUMNS + _JOB)
+        """outs: the results as dicts, or a _trackset.DeviceTrackSet of results that are in HBM already (its rows are not copied)."""
+        if isinstance(outs, TS.DeviceTrackSet):
+            TS.DeviceStage.__init__(self, _job_columns(outs.job_params(jobs), jobs, n_classes), _COLUMNS + _JOB, trackset=outs)
+        else:
+            TS.DeviceStage.__init__(self, _prepare(packed, outs, jobs, n_classes), _COLUMNS + _JOB)
         self.job_row_offsets = self.zeros(self.p['J'] + 1, self.torch.int64)
         self.out = None
 
@@ -120,7 +128,8 @@ class DeviceRefine(TS.DeviceStage):
             self.emit()
         self.wait('wt_refine_tracks_emit_dev')
         o = dict((k, v.cpu().numpy()) for k, v in self.out.items())
-        return _job_dicts(self.p, self.job_row_offsets.cpu().numpy(), o['frame'], o['category'], o['bbox'], o['score'], o['local'], o['source'],
+        p = self.p if self.trackset is None else dict(self.p, **self.trackset.host_rows())
+        return _job_dicts(p, self.job_row_offsets.cpu().numpy(), o['frame'], o['category'], o['bbox'], o['score'], o['local'], o['source'],
                           o['frame_row_offsets'])
 
 
