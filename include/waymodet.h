@@ -337,6 +337,27 @@ int wd_jpeg_decode_rgb_u8(const uint8_t* data, int64_t n, uint8_t* rgb, int64_t 
  * one launch, subsequence decodes in total over all launches, subsequences} (host-only). */
 int wd_jpeg_last_stats(int32_t* out4);
 
+/* PIL's Image.resize((ow, oh), Image.BILINEAR) on an (h, w, 3) uint8 image - the reference's Resize transform behind --resize
+ * (detnet/inference.py:170-178, trainer/transforms/vision.py:137) - bit-exact with PIL: 22-bit fixed-point weights, int32 sums, the
+ * horizontal pass first and rounded to 8 bits, then the vertical pass; a pass whose sizes are equal is skipped.  Sizes 1 .. 16384 per
+ * axis; anything else is WT_ERR_INVALID with the argument's name and value in wt_last_error().
+ *   wd_resize_ksize                : coefficient slots per output index of one axis (host-only; 0 for sizes outside the limits)
+ *   wd_resize_tables_host          : the tables of one axis, built on the HOST in float64 (no GPU needed): bounds (out_size, 2) =
+ *                                    (first source index, count), coeffs (out_size, ksize), zero behind count
+ *   wd_resize_bilinear_u8_host     : the whole resize on the CPU, HOST pointers (test infrastructure; the product never calls it)
+ *   wd_resize_bilinear_u8_workspace: bytes of the 8-bit intermediate (h, ow, 3); 0 when at most one pass runs
+ *   wd_resize_bilinear_u8          : DEVICE pointers; xbounds / xcoeffs = the tables of (w -> ow), ybounds / ycoeffs of (h -> oh), NULL for
+ *                                    a skipped pass.  Stream-ordered: it neither allocates nor synchronises.  No alignment is required of
+ *                                    any pointer.  A workspace smaller than wd_resize_bilinear_u8_workspace is WT_ERR_CAPACITY before any
+ *                                    launch.  The kernels cut every table window to the source extent and to ksize: a wrong table gives
+ *                                    wrong pixels, never an access outside the buffers. */
+int wd_resize_ksize(int in_size, int out_size);
+int wd_resize_tables_host(int in_size, int out_size, int32_t* bounds, int32_t* coeffs);
+int wd_resize_bilinear_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, int oh, int ow);
+size_t wd_resize_bilinear_u8_workspace(int h, int w, int oh, int ow);
+int wd_resize_bilinear_u8(const uint8_t* src, int h, int w, uint8_t* dst, int oh, int ow, const int32_t* xbounds, const int32_t* xcoeffs,
+                          const int32_t* ybounds, const int32_t* ycoeffs, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

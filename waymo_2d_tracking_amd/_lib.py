@@ -80,7 +80,8 @@ def lib():
                      'wt_fuse_slots_workspace', 'wt_det_coco_workspace'):
             getattr(_lib, name).restype = C.c_size_t
         for name in ('wd_nms_workspace', 'wd_rpn_topk_workspace', 'wd_gemm_nt_workspace', 'wd_deform_table_bytes',
-                     'wd_deform_dw_scratch_floats', 'wd_deform_bwd_tables_bytes', 'wd_gemm_split_packed_bytes', 'wd_gemm_split_workspace', 'wd_split_planes_bytes'):
+                     'wd_deform_dw_scratch_floats', 'wd_deform_bwd_tables_bytes', 'wd_gemm_split_packed_bytes', 'wd_gemm_split_workspace', 'wd_split_planes_bytes',
+                     'wd_resize_bilinear_u8_workspace'):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_size_t
     return _lib

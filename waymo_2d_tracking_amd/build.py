@@ -53,6 +53,7 @@ UNITS = {
     'det_misc.hip': [],
     'det_preprocess.hip': ['-ffp-contract=off'],
     'jpeg_decode.hip': [],
+    'det_resize.hip': ['-ffp-contract=off'],           # PIL's bilinear resize: the coefficient tables are float64 on the host, one rounding per operation
     'det_tail.hip': ['-ffp-contract=off'],
     'det_backward.hip': ['-munsafe-fp-atomics'],
     'det_deform_bwd.hip': ['-munsafe-fp-atomics'],     # fused deformable backward: global float atomics for the dW / dX / dOffset partial sums

@@ -3,7 +3,8 @@
 `-j N`, `--resume`, `-o`) and the JSON export (/root/reference/detnet/export.py:159-165 -> detnet/data/coco.py:229-252).
 
     python -m waymo_2d_tracking_amd.detnet.inference -m MODEL_FILE -i IMAGES_DIR --export submission.json \
-        [--tta x1.5,hflip] [--auto-contrast=1] [-j 8] [-o OUT_DIR] [--resume OUT_DIR/detections.pkl] [--eval --annotations GT.json]
+        [--tta x1.5,hflip] [--auto-contrast=1] [-j 8] [-o OUT_DIR] [--resume OUT_DIR/detections.pkl] [--eval --annotations GT.json] \
+        [--resize 800 | --resize 1200x800] [--resize-device gpu]
     python -m waymo_2d_tracking_amd.detnet.inference -m MODEL_FILE -i IMAGES_DIR --export merged.json \
         --views 'orig;x1.5,hflip' --views-method soft_nms [--views-weights 1,0.8] [--export-views VIEWS_DIR]
         (--views-method weighted_fusion_b | nmw: the merge rules of detnet.ensemble_b, float boxes)
@@ -55,6 +56,9 @@ def add_test_argument(parser):
     parser.add_argument("--batch-size", type=int, default=0)
     parser.add_argument("--resize", type=str)
     parser.add_argument("--max-image-size", type=int)
+    parser.add_argument("--resize-device", type=str, default='host', choices=('host', 'gpu'),
+                        help="(extension) where --resize runs: 'host' = PIL on the loader threads like the reference, 'gpu' = decode, auto-contrast "
+                             "and resize in HIP kernels (bit-exact with PIL); 'gpu' also takes --resize WxH")
     parser.add_argument("--inflight", type=int, default=2,
                         help="(extension) detector passes in flight: each image size is captured once per lane as a hipGraph and replayed on its own "
                              "stream, results are collected one image behind; 0 = one eager call per image")
@@ -210,7 +214,8 @@ def run_views(args, views_spec):
     sizes = np.zeros((len(image_ids), 2), np.int32)
     K = len(views)
     with torch.no_grad():
-        loader = ImageLoader(images, args.resize, args.max_image_size, auto_contrast=args.auto_contrast, decoder=args.decoder)
+        loader = ImageLoader(images, parse_resize(args), args.max_image_size, auto_contrast=args.auto_contrast, decoder=args.decoder,
+                             resize_on=args.resize_device)
         lanes = [p.stream(args.inflight) for p in predicts] if args.inflight > 0 else None
         if lanes is not None and any(l is None for l in lanes):
             lanes = None                                              # no static-shape pass: one eager call per view and image
@@ -353,53 +358,95 @@ def resize_size(w, h, size, max_size=None):
     return oh, ow
 
 
+def parse_resize(args):
+    """--resize as the reference parses it (detnet/inference.py:40): None, the length of the shorter edge (int), or for 'WxH' the
+    pair (h, w) = reversed(s.split('x')), the exact output size.  A pair needs --resize-device gpu, and excludes --max-image-size as
+    the reference's Resize asserts (vision.py:151-152)."""
+    if args.resize is None:
+        return None
+    text = str(args.resize)
+    if 'x' not in text:
+        return int(text)
+    if getattr(args, 'resize_device', 'host') != 'gpu':
+        raise NotImplementedError('--resize WxH needs --resize-device gpu; on the host route --resize takes the length of the shorter edge (int)')
+    try:
+        size = tuple(int(item) for item in reversed(text.split('x')))
+    except ValueError:
+        size = ()
+    if len(size) != 2:
+        raise ValueError('--resize %r: WxH takes two integers' % text)
+    if args.max_image_size:
+        raise ValueError('--max-image-size only works with --resize <int>, not with a fixed WxH size')
+    return size
+
+
 class ImageLoader(object):
     """Decode ahead of the detector in a thread pool.  JPEG files: the file bytes go to the GPU and are decoded there
     (ops.jpeg_decode: Huffman, IDCT, upsampling, colour conversion in HIP kernels; bit-exact with PIL's decode, ~1 MB
-    instead of 7.4 MB over PCIe per 1920x1280 frame).  With --resize, or for other formats: PIL decode + ToRGB (+ Resize,
-    PIL bilinear like the reference), pinned staging buffer, asynchronous H2D of the uint8 HWC image.  Yields
-    (image_id, device uint8 (H, W, 3), (width, height) of the ORIGINAL decoded image): the detector's boxes are normalised,
-    and the reference's export scales them by the untransformed data set's image size (export.py:159-165 ->
-    coco.py:243-246 with `dataset.dataset`), not by the resized one.
+    instead of 7.4 MB over PCIe per 1920x1280 frame).  Other formats: PIL decode + ToRGB, pinned staging buffer, asynchronous H2D
+    of the uint8 HWC image.  Yields (image_id, device uint8 (H, W, 3), (width, height) of the ORIGINAL decoded image): the
+    detector's boxes are normalised, and the reference's export scales them by the untransformed data set's image size
+    (export.py:159-165 -> coco.py:243-246 with `dataset.dataset`), not by the resized one.
 
     Transform order of the reference (detnet/inference.py:170-178): ToRGB, AutoContrast, [CLAHE], Resize.  Without --resize
-    AutoContrast runs on the GPU (autocontrast_, bit-exact with PIL); with --resize it has to precede the resize, so the
-    loader thread applies PIL's own ImageOps.autocontrast before resizing (`auto_contrast_in_loader`)."""
+    AutoContrast runs on the GPU (autocontrast_, bit-exact with PIL); with --resize it has to precede the resize, so the loader
+    applies it (`auto_contrast_in_loader`).  `resize` is the length of the shorter edge or an (h, w) pair; `resize_on` says where:
+      'host' (default, the reference's way): every file is decoded by PIL, PIL's ImageOps.autocontrast and Image.resize(BILINEAR)
+             run on the loader thread, the resized image is uploaded;
+      'gpu':  the caller's `decoder` is kept - JPEG through ops.jpeg_decode, other files and the JPEG flavours the HIP decoder
+             refuses through PIL and uploaded unresized - then ops.autocontrast_ and ops.resize_bilinear_u8 on the loader thread's
+             stream (both bit-exact with PIL), and the thread synchronises that stream before it hands the frame over."""
     _warned = False                 # the PIL hand-over of an unsupported JPEG flavour is announced once
 
 
-    def __init__(self, items, resize=None, max_image_size=None, workers=4, depth=4, auto_contrast=False, decoder='gpu'):
+    def __init__(self, items, resize=None, max_image_size=None, workers=4, depth=4, auto_contrast=False, decoder='gpu', resize_on='host'):
         self.items, self.resize, self.max_size = items, resize, max_image_size
         self.workers, self.depth = workers, depth
         self.auto_contrast_in_loader = bool(auto_contrast and resize)
-        assert decoder in ('gpu', 'pil')
+        assert decoder in ('gpu', 'pil') and resize_on in ('host', 'gpu')
+        self.resize_on_gpu = bool(resize) and resize_on == 'gpu'
+        if isinstance(resize, (tuple, list)):
+            if not self.resize_on_gpu:
+                raise NotImplementedError("an (h, w) resize needs resize_on='gpu'")
+            if max_image_size:
+                raise ValueError('max_image_size only works with an int resize')
         # JPEG files are decoded by the HIP decoder (csrc/jpeg_decode.hip, bit-exact with PIL) unless the image has to pass
-        # through PIL's own resampling filter first (--resize: the reference resizes the PIL image, vision.py:137) or the
-        # caller asks for the host decoder; other formats (PNG ...) are read by PIL as in the reference
-        self.decoder = 'pil' if resize else decoder
+        # through PIL's own resampling filter first (--resize on the host route: the reference resizes the PIL image, vision.py:137)
+        # or the caller asks for the host decoder; other formats (PNG ...) are read by PIL as in the reference
+        self.decoder = 'pil' if (resize and not self.resize_on_gpu) else decoder
         self._local = threading.local()
+
+    def _out_size(self, w, h):
+        if isinstance(self.resize, (tuple, list)):
+            return int(self.resize[0]), int(self.resize[1])
+        return resize_size(w, h, int(self.resize), self.max_size)
+
+    def _stream(self):
+        if getattr(self._local, 'stream', None) is None:
+            self._local.stream = torch.cuda.Stream()                                # one stream per loader thread
+        return self._local.stream
 
     def _decode_pil(self, path):
         from PIL import Image, ImageOps
         img = Image.open(path).convert('RGB')                                       # ToRGB (vision.py:954)
         size = img.size
+        if self.resize_on_gpu:
+            return np.asarray(img, dtype=np.uint8), size                            # AutoContrast and Resize follow on the device
         if self.auto_contrast_in_loader:
             img = ImageOps.autocontrast(img)                                        # AutoContrast precedes Resize
         if self.resize:
-            oh, ow = resize_size(img.width, img.height, int(self.resize), self.max_size)
+            oh, ow = self._out_size(img.width, img.height)
             img = img.resize((ow, oh), Image.BILINEAR)
         return np.asarray(img, dtype=np.uint8), size
 
-    def _decode(self, path):
+    def _decode_file(self, path):
         if self.decoder == 'gpu':
             with open(path, 'rb') as f:
                 data = f.read()
             if data[:2] == b'\xff\xd8':
                 from .nn import ops
-                if getattr(self._local, 'stream', None) is None:
-                    self._local.stream = torch.cuda.Stream()                        # one decode stream per loader thread
                 try:
-                    with torch.cuda.stream(self._local.stream):
+                    with torch.cuda.stream(self._stream()):
                         t = ops.jpeg_decode(data)                                   # returns with the image complete
                     return t, (t.shape[1], t.shape[0])
                 except _lib.WaymoTrackError as e:
@@ -411,6 +458,24 @@ class ImageLoader(object):
                         ImageLoader._warned = True
                         print('ImageLoader: %s: %s -> such files are decoded by PIL on the host' % (path, e), flush=True)
         return self._decode_pil(path)
+
+    def _decode(self, path):
+        t, size = self._decode_file(path)
+        if not self.resize_on_gpu:
+            return t, size
+        from .nn import ops
+        stream = self._stream()
+        with torch.cuda.stream(stream):
+            if isinstance(t, np.ndarray):
+                t = torch.from_numpy(np.array(t, copy=True)).pin_memory().cuda(non_blocking=True)
+            if self.auto_contrast_in_loader:
+                t = ops.autocontrast_(t)                                            # in place: the decoded frame is the loader's own
+            oh, ow = self._out_size(size[0], size[1])
+            out = ops.resize_bilinear_u8(t, oh, ow)
+        # the kernels above are asynchronous and the consumer only calls record_stream: the frame is complete before it leaves this
+        # thread (which also keeps the pinned buffer and the decoded frame alive for as long as the stream reads them)
+        stream.synchronize()
+        return out, size
 
     def __iter__(self):
         from concurrent.futures import ThreadPoolExecutor
@@ -442,11 +507,7 @@ def check_supported(args):
         raise NotImplementedError('--device %s: the detector runs in fp32 on the GPU only (HIP kernels, no CPU fallback)' % args.device)
     if args.soft_nms or args.bbox_voting:
         raise NotImplementedError('--soft-nms / --bbox-voting belong to the SSD detect layer of the reference, not to Cascade R-CNN')
-    if args.resize is not None:
-        try:
-            int(args.resize)
-        except ValueError:
-            raise NotImplementedError('--resize takes the length of the shorter edge (int); (h, w) pairs are not supported')
+    parse_resize(args)
     if args.eval and not args.annotations:
         raise ValueError('--eval needs --annotations GT.json (COCO-format ground truth; the reference reads it from --data-root)')
     if getattr(args, 'eval_gpu', False) and not args.eval:
@@ -485,7 +546,8 @@ def run_rank(args, world, rank):
     sizes = np.zeros((len(image_ids), 2), np.int32)
     index = {k: i for i, k in enumerate(image_ids)}
     with torch.no_grad():
-        loader = ImageLoader(images[lo:hi], args.resize, args.max_image_size, auto_contrast=args.auto_contrast, decoder=args.decoder)
+        loader = ImageLoader(images[lo:hi], parse_resize(args), args.max_image_size, auto_contrast=args.auto_contrast, decoder=args.decoder,
+                             resize_on=args.resize_device)
         # round 6: `--inflight` detector passes in flight, each a captured hipGraph per image size (the Waymo cameras have two); results are collected
         # one image behind.  --inflight 0: the per-image eager call of the earlier rounds (and the only form for TTA plans / models without a
         # static-shape pass)

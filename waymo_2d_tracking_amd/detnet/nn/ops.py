@@ -806,6 +806,47 @@ def autocontrast_(img_u8):
     return img_u8
 
 
+_RESIZE_TABLES = {}         # (in_size, out_size, device index) -> (bounds, coeffs) int32 device tensors, uploaded once
+
+
+def resize_tables(in_size, out_size, device):
+    """The coefficient tables of one axis of resize_bilinear_u8 on `device`: built on the host in float64 (wd_resize_tables_host) and
+    uploaded once per (in_size, out_size, device).  Loader threads may race here: they build equal tables and one of them stays."""
+    key = (int(in_size), int(out_size), torch.device(device).index)
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        import numpy as np
+        lib = _lib.lib()
+        ksize = lib.wd_resize_ksize(C.c_int(key[0]), C.c_int(key[1]))
+        bounds = np.zeros((key[1], 2), np.int32)
+        coeffs = np.zeros((key[1], max(ksize, 1)), np.int32)
+        _lib.check(lib.wd_resize_tables_host(C.c_int(key[0]), C.c_int(key[1]), _lib.ptr(bounds), _lib.ptr(coeffs)), 'wd_resize_tables_host')
+        hit = _RESIZE_TABLES.setdefault(key, (torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device)))
+    return hit
+
+
+def resize_bilinear_u8(img_u8, out_h, out_w, out=None):
+    """PIL's `Image.resize((out_w, out_h), Image.BILINEAR)` on an (H, W, 3) uint8 GPU image -> a new (out_h, out_w, 3) tensor, bit-exact
+    with PIL (csrc/det_resize.hip: wd_resize_bilinear_u8; integer kernels, the horizontal pass rounded to 8 bits, then the vertical
+    one).  Asynchronous on the current stream."""
+    assert img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3 and img_u8.is_contiguous()
+    h, w = int(img_u8.shape[0]), int(img_u8.shape[1])
+    out_h, out_w = int(out_h), int(out_w)
+    lib = _lib.lib()
+    dev = img_u8.device
+    xb, xc = resize_tables(w, out_w, dev) if w != out_w else (None, None)          # a size outside 1..16384 is refused here, by name
+    yb, yc = resize_tables(h, out_h, dev) if h != out_h else (None, None)
+    if out is None:
+        out = torch.empty((out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    else:
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (out_h, out_w, 3)
+    need = lib.wd_resize_bilinear_u8_workspace(C.c_int(h), C.c_int(w), C.c_int(out_h), C.c_int(out_w))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    _lib.check(lib.wd_resize_bilinear_u8(_p(img_u8), C.c_int(h), C.c_int(w), _p(out), C.c_int(out_h), C.c_int(out_w), _p(xb), _p(xc), _p(yb),
+                                         _p(yc), _p(ws), C.c_size_t(need), _stream()), 'wd_resize_bilinear_u8')
+    return out
+
+
 def jpeg_info(data):
     """(width, height, components, h_samp, v_samp, restart_interval) of a baseline JPEG (host-only header parse)."""
     buf = bytes(data)
