@@ -1,7 +1,9 @@
 """Detector custom ops (HIP, through the C ABI) against the PyTorch restatement in oracle/detops_ref.py.
 float32 kernels vs float64 references; every test states its tolerance in its assertion (north_star: 1e-4 on boxes/scores).  One or two
 convenient shapes per kernel: the edge and multi-tile shapes of the forward kernels are in tests/test_gpu_forward_ops.py, those of the backward
-kernels in tests/test_gpu_backward_ops.py, the exact-answer edge cases of the NMS sweeps and the kept-row compaction in tests/test_gpu_nms_edges.py."""
+kernels in tests/test_gpu_backward_ops.py, the exact-answer edge cases of the NMS sweeps and the kept-row compaction in tests/test_gpu_nms_edges.py,
+those of forward ROIAlign (every route and per-ROI path) in tests/test_gpu_roi_edges.py, those of the f32 MFMA GEMM (every kernel, split and
+refusal) in tests/test_gpu_gemm_f32.py."""
 import os
 
 import numpy as np
@@ -108,6 +110,8 @@ def test_nms_vs_reference(n):
 @pytest.mark.parametrize('M,N,K,relu', [(1000, 1024, 12544, True), (130, 70, 36, False), (2400, 2048, 1024, True),
                                         (64, 64, 4, False), (38400, 256, 512, False)])
 def test_gemm_vs_reference(M, N, K, relu):
+    """Convenient shapes against a flat tolerance; the exact-answer and edge shapes of every kernel, split-K branch and refusal of
+    csrc/det_gemm.hip are in tests/test_gpu_gemm_f32.py."""
     from waymo_2d_tracking_amd.detnet.nn import ops
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn((M, K), generator=g)
