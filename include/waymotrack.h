@@ -861,6 +861,51 @@ int wt_xclass_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                           int32_t* out_keep, int32_t* out_by, int32_t* out_match, int32_t* out_row_keep, int64_t* out_dropped);
 
 /* =================================================================================================
+ * Cross-class track linking (class flicker: tracklets linked across classes and relabelled; the definition is DESIGN.md section 31)
+ * ================================================================================================= */
+
+/* Links the trajectories of R >= 1 tracking results across gaps AND classes under J jobs, and gives every chain one class.
+ * Results, slots, streams, trajectories, local indices (by first appearance), a trajectory's class, the affinity a of a tail and a
+ * head, and the walk of the candidates in the strict order (-a, n, i, j) are those of the track stitching above.  What differs is
+ * rule 1: tail i of class ci and head j != i of the same stream and class cj are a candidate when n lies in
+ * 1..pair_max_link[ci][cj], a >= pair_link_iou[ci][cj] and a > 0.  A job carries pair_max_link int32 >= 0 (0: the pair is off)
+ * and pair_link_iou float64 not NaN - two (n_classes, n_classes) tables that must be symmetric, the doubles bit for bit; the
+ * diagonal means pairs inside a class - class_prio[c] int32 and motion (0 = hold, 1 = linear); n_classes <= 16.
+ * A chain is a root and everything linked behind it.  Its class is the class c that maximises (rows of the chain's trajectories
+ * whose class is c, class_prio[c], 1 if c is the root's class else 0, -c) among the classes with at least one row: integers only.
+ *
+ * Outputs, sized up front: out_pred, out_root (J, n_traj_total) int32 and out_affinity (J, n_traj_total) float64 as in the
+ * stitching; out_cls (J, n_traj_total) int32 = the chain's class at every member; out_row_root, out_row_category (J, n_rows)
+ * int32 = per row of the job's result the root's local index and the chain's class; out_links, out_relabelled (J, n_streams)
+ * int64 = the links made and the rows whose category changed.  Entries of results the job does not name are -1 (-1.0).
+ *
+ * The entry points are the twins of wt_stitch_tracks_*: the device form takes device pointers, is stream-ordered, never allocates
+ * or waits, reports 0 or WT_ERR_CAPACITY in status_dev, answers a workspace smaller than wt_xlink_tracks_workspace() with
+ * WT_ERR_CAPACITY and more than 16 classes with WT_ERR_INVALID before any launch, and does not check the layout; the host form
+ * checks (WT_ERR_INVALID names the result and the row or frame slot, or the job and the pair), stages and launches.
+ * wt_xlink_tracks_limits: the trajectory count of one (result, stream) up to which the tables of the matching stay in LDS.
+ * wt_xlink_tracks_rounds: after a finished call on `workspace`, the rounds that accepted a link, (J, n_streams); it synchronises. */
+void wt_xlink_tracks_limits(int32_t* lds_trajectories);
+size_t wt_xlink_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj);
+int wt_xlink_tracks_rounds(const void* workspace, int32_t n_jobs, int32_t n_streams, int32_t* out_rounds);
+int wt_xlink_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                        int32_t r_sets, int64_t n_rows, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                        const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                        const int64_t* traj_offsets, int64_t n_traj_total, int64_t max_traj,
+                        int32_t n_jobs, const int32_t* job_result, const int32_t* job_pair_max_link, const double* job_pair_link_iou,
+                        const int32_t* job_class_prio, const int32_t* job_motion, int32_t n_classes,
+                        int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_cls, int32_t* out_row_root,
+                        int32_t* out_row_category, int64_t* out_links, int64_t* out_relabelled,
+                        int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+int wt_xlink_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
+                         int32_t r_sets, const int64_t* set_row_offsets, const int64_t* frame_row_offsets,
+                         const double* x, const double* y, const double* w, const double* h, const int32_t* category, const int32_t* local,
+                         const int32_t* n_traj, int32_t n_jobs, const int32_t* job_result, const int32_t* job_pair_max_link,
+                         const double* job_pair_link_iou, const int32_t* job_class_prio, const int32_t* job_motion, int32_t n_classes,
+                         int32_t* out_pred, int32_t* out_root, double* out_affinity, int32_t* out_cls, int32_t* out_row_root,
+                         int32_t* out_row_category, int64_t* out_links, int64_t* out_relabelled);
+
+/* =================================================================================================
  * Detection evaluation (VOC-style AP / AR per class, IoU threshold and box-size bucket; the definition is DESIGN.md section 16)
  * ================================================================================================= */
 

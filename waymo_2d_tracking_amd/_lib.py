@@ -76,7 +76,7 @@ def lib():
         _lib.wt_sort_num_tracks.argtypes = [C.c_void_p]
         for name in ('wt_track_streams_workspace', 'wt_ensemble_groups_workspace', 'wt_ensemble_slots_workspace', 'wt_track_state_bytes',
                      'wt_track_chunk_workspace', 'wt_det_eval_workspace', 'wt_refine_tracks_workspace', 'wt_stitch_tracks_workspace',
-                     'wt_smooth_tracks_workspace', 'wt_dedup_tracks_workspace', 'wt_xclass_tracks_workspace', 'wt_split_tracks_workspace', 'wt_track_streams_byte_workspace',
+                     'wt_smooth_tracks_workspace', 'wt_dedup_tracks_workspace', 'wt_xclass_tracks_workspace', 'wt_xlink_tracks_workspace', 'wt_split_tracks_workspace', 'wt_track_streams_byte_workspace',
                      'wt_fuse_slots_workspace', 'wt_det_coco_workspace'):
             getattr(_lib, name).restype = C.c_size_t
         for name in ('wd_nms_workspace', 'wd_rpn_topk_workspace', 'wd_gemm_nt_workspace', 'wd_deform_table_bytes',

@@ -38,6 +38,7 @@ UNITS = {
     'track_smooth.hip': ['-ffp-contract=off'],         # track smoothing: acc + k[d] * (v(f - d) + v(f + d)) and the quotient, every operation rounded on its own
     'track_dedup.hip': ['-ffp-contract=off'],          # track deduplication: the same float64 IoU, dup_frac * min(n) one multiplication
     'track_xclass.hip': ['-ffp-contract=off'],         # cross-class suppression: the IoU terms in their order, frac * n_weak one multiplication
+    'track_xlink.hip': ['-ffp-contract=off'],          # cross-class linking: stitching's extrapolation and IoU, unfused; the vote is integers only
     'track_split.hip': ['-ffp-contract=off'],          # track splitting: the extrapolations x + ((x - xo) / slots) * n unfused, the same float64 IoU
     'tracks_layout.hip': ['-ffp-contract=off'],        # track layouts: integers and bit-copies only; the flag matches the units whose headers it includes
     'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation

@@ -1,4 +1,4 @@
-"""What the six track post-passes (refine.py, stitch.py, smooth.py, dedup.py, split.py, xclass.py) share: the layout every ``wt_<stage>_tracks_*`` call
+"""What the seven track post-passes (refine.py, stitch.py, smooth.py, dedup.py, split.py, xclass.py, xlink.py) share: the layout every ``wt_<stage>_tracks_*`` call
 takes - R results over the frame slots of `packed`, CSR offsets, the box / score / category columns, a dense per-stream trajectory
 index per row, J jobs that each name a result (include/waymotrack.h; DESIGN.md section 20, "The shared layer") - the argument
 lists built from it, and the device-resident form of a stage.  The layout is built on the host by prepare(), or on the GPU, for

@@ -9,8 +9,8 @@ is not required to exist).
 
 Beyond the reference: `--low-score-threshold=0.3,0.3,1.0,0.3 [--low-iou-threshold 0.5]` lets detections between the two score
 thresholds continue tracks that no detection above `--score-threshold` matched (second association; one
-process only), and the post-passes of split.py, stitch.py, dedup.py, xclass.py, refine.py and smooth.py follow when their flags ask
-for them.
+process only), and the post-passes of split.py, stitch.py, xlink.py, dedup.py, xclass.py, refine.py and smooth.py follow when their
+flags ask for them.
 """
 import argparse
 import importlib
@@ -86,6 +86,17 @@ def build_parser():
                         help='the overlap of two boxes: intersection over union, or over the smaller area (a rider box inside a cyclist box)')
     parser.add_argument("--xclass-prio", type=_ints, default=[0],
                         help='class priority, one int per class: of two overlapping tracks the one of the higher priority stays, whatever their lengths')
+    parser.add_argument("--xlink-pairs", type=_pairs, default=None,
+                        help='repair class flicker: the class pairs across which a track that ends is linked to one that starts, as 2:4,1:2 '
+                             '(a:a = inside a class; absent = off); the linked rows take one id and the class most of them have')
+    parser.add_argument("--xlink-gap", type=_ints, default=[1],
+                        help='link up to this many frames later (one value, or one per listed pair; 0 = the pair is off)')
+    parser.add_argument("--xlink-iou", type=_floats, default=[0.3],
+                        help='lowest IoU of the ended track\'s extrapolated box and the new track\'s first box (one value, or one per listed pair)')
+    parser.add_argument("--xlink-motion", choices=('hold', 'linear'), default='hold',
+                        help='how the ended track is extrapolated over the gap: its last box, or moved on by its last step')
+    parser.add_argument("--xlink-prio", type=_ints, default=[0],
+                        help='class priority, one int per class: decides the class of linked rows when two classes have equally many')
     parser.add_argument("--smooth-window", type=_ints, default=[0],
                         help='smooth tracks: every box becomes the weighted mean of its track\'s boxes up to this many frames to either side, '
                              'both sides or neither (one value, or one per class)')
@@ -125,6 +136,12 @@ def dedups(args):
     return max(args.dedup_frames) > 0
 
 
+def _per_pair(values, flag, n):
+    if len(values) not in (1, n):
+        raise SystemExit('%s needs one value, or one per listed pair (%d)' % (flag, n))
+    return list(values) * n if len(values) == 1 else list(values)
+
+
 def xclass_pairs(args):
     """The pairs of tracking/xclass.py that the flags switch on: {(a, b): {'frames', 'overlap', 'frac'}}; empty = the pass is off."""
     if not args.xclass_pairs:
@@ -132,11 +149,7 @@ def xclass_pairs(args):
     n = len(args.xclass_pairs)
     if any(len(pair) != 2 for pair in args.xclass_pairs):
         raise SystemExit('--xclass-pairs takes pairs of classes, as 2:4,1:4')
-
-    def per_pair(values, flag):
-        if len(values) not in (1, n):
-            raise SystemExit('%s needs one value, or one per listed pair (%d)' % (flag, n))
-        return list(values) * n if len(values) == 1 else list(values)
+    per_pair = lambda values, flag: _per_pair(values, flag, n)
     frames, overlap, frac = per_pair(args.xclass_frames, '--xclass-frames'), per_pair(args.xclass_overlap, '--xclass-overlap'), per_pair(args.xclass_frac, '--xclass-frac')
     return dict((pair, {'frames': f, 'overlap': o, 'frac': q}) for pair, f, o, q in zip(args.xclass_pairs, frames, overlap, frac) if f > 0)
 
@@ -144,6 +157,22 @@ def xclass_pairs(args):
 def xclasses(args):
     """Whether the flags ask for the suppression of duplicate tracks across classes (tracking/xclass.py)."""
     return bool(xclass_pairs(args))
+
+
+def xlink_pairs(args):
+    """The pairs of tracking/xlink.py that the flags switch on: {(a, b): {'max_link', 'link_iou'}}; empty = the pass is off."""
+    if not args.xlink_pairs:
+        return {}
+    n = len(args.xlink_pairs)
+    if any(len(pair) != 2 for pair in args.xlink_pairs):
+        raise SystemExit('--xlink-pairs takes pairs of classes, as 2:4,1:2')
+    gaps, ious = _per_pair(args.xlink_gap, '--xlink-gap', n), _per_pair(args.xlink_iou, '--xlink-iou', n)
+    return dict((pair, {'max_link': g, 'link_iou': v}) for pair, g, v in zip(args.xlink_pairs, gaps, ious) if g > 0)
+
+
+def xlinks(args):
+    """Whether the flags ask for linking across classes (tracking/xlink.py)."""
+    return bool(xlink_pairs(args))
 
 
 def smooths(args):
@@ -177,9 +206,17 @@ PASSES = (
     (smooths, lambda args, packed, out, n: _stage('smooth').smooth_one(packed, out, args.smooth_window, args.smooth_sigma, args.smooth_kernel, n)))
 
 
+# The chain that runs: PASSES with the linking across classes between stitching and deduplication - after the stitching, so that
+# a piece is first joined to its own class where it can be and the vote sees whole tracks, and before the suppression of
+# duplicates, which then judges a repaired track at its full length and in its voted class.  Off unless --xlink-pairs is given.
+CHAIN = PASSES[:2] + (
+    (xlinks, lambda args, packed, out, n: _stage('xlink').xlink_one(packed, out, xlink_pairs(args), args.xlink_prio, args.xlink_motion, n)),
+) + PASSES[2:]
+
+
 def refined(args, packed, out):
-    """The tracker's rows after the post-passes the flags ask for, in the order of PASSES."""
-    for asked, run in PASSES:
+    """The tracker's rows after the post-passes the flags ask for, in the order of CHAIN."""
+    for asked, run in CHAIN:
         if asked(args):
             out = run(args, packed, out, len(args.iou_threshold))
     return out
@@ -291,7 +328,7 @@ def main(argv=None):
         from . import utils as T
         packed = T.pack_streams(predictions)
         tracked_predictions = T.format_tracks(packed, refined(args, packed, tracked_byte(args, packed)))
-    elif any(asked(args) for asked, _ in PASSES):
+    elif any(asked(args) for asked, _ in CHAIN):
         from . import utils as T
         packed = T.pack_streams(predictions)
         out, births = T.track_packed(packed, args.iou_threshold, args.max_age, args.min_hits, None, T._GLOBAL_IDS['next'])
