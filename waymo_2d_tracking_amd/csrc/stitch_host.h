@@ -21,7 +21,7 @@ inline int check_stitch_layout(const StitchInput& in, int64_t* max_traj, int64_t
                                  in.n_jobs >= 0 && (!in.n_jobs || (in.job_result && in.job_max_link && in.job_link_iou && in.job_motion)),
                                  max_traj, n_traj_total));
     return check_job_results(in.job_result, in.n_jobs, in.r_sets, [&](int32_t j) {
-        if (in.job_motion[j] != 0 && in.job_motion[j] != 1) { set_error("job %d: motion must be 0 (hold) or 1 (linear)", (int)j); return WT_ERR_INVALID; }
+        WT_TRY(check_link_motion(in.job_motion, j));
         for (int32_t c = 0; c < in.n_classes; ++c) {
             if (in.job_max_link[(size_t)j * in.n_classes + c] < 0) { set_error("job %d: max_link of class %d is negative", (int)j, (int)c + 1); return WT_ERR_INVALID; }
             const double v = in.job_link_iou[(size_t)j * in.n_classes + c];

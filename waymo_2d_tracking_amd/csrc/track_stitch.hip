@@ -3,290 +3,59 @@
 // later (head) when the tail's extrapolated box overlaps the head's first box; the linked pieces take the id of the earliest one.
 // R tracking results come in once; J jobs each name a result and their parameters.  No row is added, removed or moved.
 //
-// Two launches, one 64-lane wavefront per independent problem:
-//   1. summary: per (result, stream), walk the slots once: per trajectory the first slot and row, the last slot and row, the slot
-//               and row before the last, and the class.  Shared by all jobs of the result.
-//   2. match:   per (job, stream).  The answer is the greedy walk of all candidate pairs in the strict order (-a, n, i, j); it is
-//               computed in rounds of locally dominant pairs, without a table of pairs: a lane owns a free tail and scans its heads -
-//               local indices are by first appearance, so the heads whose first slot lies in [e + 1, e + max_link] are a contiguous
-//               range found by two binary searches.  Scan A gives every head the highest affinity any free tail offers it (64-bit
-//               atomic max on the bits of a positive double) and every tail its best head; scan B gives every head the smallest
-//               (n, i) among the tails that offer exactly that affinity; a pair that is its tail's best and its head's best is
-//               accepted.  The smallest free pair always is one, so a round without an acceptance ends the matching.  The same
-//               wavefront then resolves the roots, counts the links and labels its rows.
-// The tables of the match (36 bytes per trajectory) live in LDS up to kLdsTraj trajectories, in the workspace beyond.
+// The summary, the match in rounds, the roots and the launches are those of link_match_device.h, shared with track_xlink.hip; this
+// unit gives them the rules of section 21 as a compile-time policy - its match kernel reads no flag on account of the sharing - and
+// labels the rows with their roots.
 // Compile with -ffp-contract=off: the extrapolation is x + ((x - xp) / (e - p)) * n with every operation rounded on its own, and
 // iou_dd is the IoU the metrics use.
 #include "eval_device.h"
 #include "tracks_device.h"
+#include "link_match_device.h"
 #include "stitch_host.h"
 
 using namespace wtdev;
+using link::kLdsTraj;
 
 namespace {
 
-constexpr int kLdsTraj = 1024;                // trajectories of one (result, stream) up to which the match tables stay in LDS
-constexpr int kTableBytes = 36;               // per trajectory: two uint64, one double, three int32
-
-struct Layout : TrackLayout {                 // device pointers
-    const int32_t *job_max_link, *job_motion;
+struct Layout : link::Layout {                // device pointers
+    const int32_t* job_max_link;
     const double* job_link_iou;
 };
 
-struct Summary {                              // [n_traj_total] each; slots relative to the stream's first, rows to the stream's first row; -1 none
-    int32_t *first_slot, *first_row, *last_slot, *last_row, *prev_slot, *prev_row, *cls;
+// Section 21: pairs inside a class, with the class's gap and threshold.
+struct StitchPolicy {
+    static constexpr bool kRowCounts = false, kRounds = false;
+    const int32_t* max_link;
+    const double* link_iou;
+    struct Row {
+        int cls, gap;
+        double thr;
+        __device__ __forceinline__ int reach() const { return gap; }
+        __device__ __forceinline__ bool meets(int cj) const { return cj == cls; }
+        __device__ __forceinline__ int max_link(int) const { return gap; }
+        __device__ __forceinline__ double threshold(int) const { return thr; }
+    };
+    __device__ __forceinline__ static StitchPolicy make(const Layout& L, int job) {
+        const size_t o = (size_t)job * L.n_classes;
+        return {L.job_max_link + o, L.job_link_iou + o};
+    }
+    __device__ __forceinline__ Row row(int c) const { return {c, max_link[c - 1], link_iou[c - 1]}; }
 };
 
-struct Workspace {
-    Summary sum;
-    unsigned long long *head_a, *head_k;      // [J * n_traj_total] the tables of the problems above kLdsTraj (all five)
-    double* tail_a;
-    int32_t *tail_j, *succ, *pred;
-    size_t bytes;
-};
-
-Workspace carve(void* base, size_t n_jobs, size_t n_traj_total, size_t max_traj) {
-    wt::Carver cv(base);
-    Workspace w;
-    const size_t big = max_traj > (size_t)kLdsTraj ? n_jobs * n_traj_total : 0;
-    int32_t** cols[7] = {&w.sum.first_slot, &w.sum.first_row, &w.sum.last_slot, &w.sum.last_row, &w.sum.prev_slot, &w.sum.prev_row, &w.sum.cls};
-    for (auto c : cols) *c = cv.take<int32_t>(n_traj_total + 1);
-    w.head_a = cv.take<unsigned long long>(big + 1);
-    w.head_k = cv.take<unsigned long long>(big + 1);
-    w.tail_a = cv.take<double>(big + 1);
-    w.tail_j = cv.take<int32_t>(big + 1);
-    w.succ = cv.take<int32_t>(big + 1);
-    w.pred = cv.take<int32_t>(big + 1);
-    w.bytes = cv.off;
-    return w;
-}
-
-__global__ __launch_bounds__(kWave) void stitch_summary_kernel(Layout L, Summary S, int* __restrict__ status) {
-    const int lane = threadIdx.x & 63;
-    const int r = (int)(blockIdx.x / (unsigned)L.n_streams), s = (int)(blockIdx.x % (unsigned)L.n_streams);
-    const Span q = span_of(L, r, s);
-    if (!q.ok) {
-        if (lane == 0) atomicMax(status, kErrCapacity);
-        return;
-    }
-    const int T = q.T;
-    for (int t = lane; t < T; t += kWave) {
-        const size_t g = (size_t)q.t0 + t;
-        S.first_slot[g] = -1; S.first_row[g] = -1; S.last_slot[g] = -1; S.last_row[g] = -1; S.prev_slot[g] = -1; S.prev_row[g] = -1; S.cls[g] = 0;
-    }
-    wsync();
-    int err = 0;
-    for_stream_rows(q, L.local, &err, [&](long long d, int t, int fo) {
-        const size_t g = (size_t)q.t0 + t;
-        const int row = (int)(d - q.rs0);
-        if (S.first_slot[g] < 0) { S.first_slot[g] = fo; S.first_row[g] = row; S.cls[g] = L.category[d]; }
-        S.prev_slot[g] = S.last_slot[g];
-        S.prev_row[g] = S.last_row[g];
-        S.last_slot[g] = fo;
-        S.last_row[g] = row;
-    });
-    if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
-}
-
-struct Outputs {
-    int32_t *pred, *root;                     // [J * n_traj_total]
-    double* affinity;                         // [J * n_traj_total]
-    int32_t* row_root;                        // [J * n_rows]
-    int64_t* links;                           // [J * n_streams]
-};
-
-// every entry: no link, no root; the match kernel fills those of its job's result
-__global__ void stitch_init_kernel(Outputs O, long long n_traj, long long n_row) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_traj) { O.pred[i] = -1; O.root[i] = -1; O.affinity[i] = -1.0; }
-    if (i < n_row) O.row_root[i] = -1;
-}
-
-// first t in [0, T) with slot[t] >= v (slot is non-decreasing where the local indices are by first appearance); always inside [0, T]
-__device__ __forceinline__ int lower_bound_slot(const int32_t* __restrict__ slot, int T, int v) {
-    int lo = 0, hi = T;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (slot[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// The candidate heads of one free tail, in ascending index: visit(j, n, a) for every free head j of the tail's class, n = its gap,
-// a = the affinity, when the pair is a candidate (rule 1 of the definition).
-struct Tail {
-    int e, lo, hi, cls, max_link;
-    double px0, py0, vx, vy, w, h, thr;
-    bool linear;
-};
-
-template <class Visit>
-__device__ __forceinline__ void scan_heads(const Tail& t, const Summary& S, size_t g0, const Boxes& B, long long rs0, long long n_stream_rows,
-                                           const int32_t* pred, Visit visit) {
-    for (int j = t.lo; j < t.hi; ++j) {
-        if (pred[j] >= 0 || S.cls[g0 + j] != t.cls) continue;
-        const int n = S.first_slot[g0 + j] - t.e, fr = S.first_row[g0 + j];
-        if (n < 1 || n > t.max_link || fr < 0 || fr >= n_stream_rows) continue;
-        double px = t.px0, py = t.py0;
-        if (t.linear) { px = t.px0 + t.vx * (double)n; py = t.py0 + t.vy * (double)n; }
-        const double pb[4] = {px, py, px + t.w, py + t.h};
-        double hb[4];
-        B.get(rs0 + fr, hb);
-        const double a = iou_dd(pb, hb);
-        if (a >= t.thr && a > 0.) visit(j, n, a);
-    }
-}
-
-__global__ __launch_bounds__(kWave) void stitch_match_kernel(Layout L, Boxes B, Workspace ws, Outputs O, int* __restrict__ status) {
+__global__ __launch_bounds__(kWave) void stitch_match_kernel(Layout L, Boxes B, link::Workspace ws, link::Outputs O, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
-    const size_t p = blockIdx.x;
-    int j_, s_;
-    decode_job_stream(p, L.n_streams, &j_, &s_);
-    const int job = j_, s = s_;
-    const Span q = span_of(L, L.job_result[job], s);
-    if (!q.ok) {
-        if (lane == 0) { atomicMax(status, kErrCapacity); O.links[p] = 0; }
-        return;
-    }
-    const int T = q.T, C = L.n_classes;
-    const Summary S = ws.sum;
-    const size_t g0 = (size_t)q.t0;
-    const size_t tbase = (size_t)job * (size_t)L.n_traj_total + g0;
-    const size_t lbase = (size_t)job * (size_t)L.n_rows;
-    const bool in_lds = T <= L.lds_traj;
-    const size_t stride = (size_t)L.lds_traj;
-    unsigned long long* head_a = in_lds ? reinterpret_cast<unsigned long long*>(smem) : ws.head_a + tbase;
-    unsigned long long* head_k = in_lds ? head_a + stride : ws.head_k + tbase;
-    double* tail_a = in_lds ? reinterpret_cast<double*>(head_k + stride) : ws.tail_a + tbase;
-    int32_t* tail_j = in_lds ? reinterpret_cast<int32_t*>(tail_a + stride) : ws.tail_j + tbase;   // after the matching: the root
-    int32_t* succ = in_lds ? tail_j + stride : ws.succ + tbase;                                      // the head linked to this tail, -1 free, -2 no candidate left
-    int32_t* pred = in_lds ? succ + stride : ws.pred + tbase;                                        // the tail linked to this head, -1 free
-    const int32_t* links = L.job_max_link + (size_t)job * C;
-    const double* thrs = L.job_link_iou + (size_t)job * C;
-    const bool linear = L.job_motion[job] == 1;
-    int err = 0;
-    const long long end = stream_end(q, &err);
-    const long long n_stream_rows = end - q.rs0;
-    for (int t = lane; t < T; t += kWave) { succ[t] = -1; pred[t] = -1; }
-    wsync();
-
-    // what a free tail needs for its scans; valid = false: it can never link
-    auto make_tail = [&](int i, Tail* t) {
-        const int c = S.cls[g0 + i];
-        if (c < 1 || c > C) return false;
-        const int max_link = links[c - 1];
-        const int e = S.last_slot[g0 + i], row = S.last_row[g0 + i];
-        if (max_link < 1 || e < 0 || row < 0 || row >= n_stream_rows) return false;
-        t->e = e; t->cls = c; t->max_link = max_link; t->thr = thrs[c - 1];
-        const long long hi_slot = (long long)e + max_link + 1;
-        t->lo = lower_bound_slot(S.first_slot + g0, T, e + 1);
-        t->hi = lower_bound_slot(S.first_slot + g0, T, hi_slot > 0x7fffffffll ? 0x7fffffff : (int)hi_slot);
-        const long long d = q.rs0 + row;
-        t->px0 = B.x[d]; t->py0 = B.y[d]; t->w = B.w[d]; t->h = B.h[d];
-        const int ps = S.prev_slot[g0 + i], prow = S.prev_row[g0 + i];
-        t->linear = linear && ps >= 0 && prow >= 0 && prow < n_stream_rows && e > ps;
-        t->vx = 0.; t->vy = 0.;
-        if (t->linear) {
-            const long long dp = q.rs0 + prow;
-            t->vx = (t->px0 - B.x[dp]) / (double)(e - ps);
-            t->vy = (t->py0 - B.y[dp]) / (double)(e - ps);
-        }
-        return t->lo < t->hi;
-    };
-
-    for (int round = 0; round <= T; ++round) {                         // every round but the last accepts a pair: at most T rounds
-        for (int t = lane; t < T; t += kWave) { head_a[t] = 0ull; head_k[t] = ~0ull; }
-        wsync();
-        // ---- scan A: per head the highest affinity offered, per tail its best head ----
-        for (int ib = 0; ib < T; ib += kWave) {
-            const int i = ib + lane;
-            if (i >= T || succ[i] != -1) continue;
-            Tail t;
-            int bj = -1;
-            double ba = 0.;
-            if (make_tail(i, &t))
-                scan_heads(t, S, g0, B, q.rs0, n_stream_rows, pred, [&](int j, int n, double a) {
-                    atomicMax(&head_a[j], (unsigned long long)__double_as_longlong(a));
-                    if (a > ba) { ba = a; bj = j; }                    // ascending j is ascending n: the first of equal affinities is the best
-                });
-            tail_a[i] = ba;
-            tail_j[i] = bj;
-            if (bj < 0) succ[i] = -2;                                  // the free heads only get fewer
-        }
-        wsync();
-        // ---- scan B: per head the smallest (n, i) among the tails that offer exactly its highest affinity ----
-        for (int ib = 0; ib < T; ib += kWave) {
-            const int i = ib + lane;
-            if (i >= T || succ[i] != -1) continue;
-            Tail t;
-            if (make_tail(i, &t))
-                scan_heads(t, S, g0, B, q.rs0, n_stream_rows, pred, [&](int j, int n, double a) {
-                    if ((unsigned long long)__double_as_longlong(a) == head_a[j])
-                        atomicMin(&head_k[j], ((unsigned long long)(unsigned)n << 32) | (unsigned)i);
-                });
-        }
-        wsync();
-        // ---- accept the pairs that are best on both sides ----
-        bool any = false;
-        for (int ib = 0; ib < T; ib += kWave) {
-            const int i = ib + lane;
-            bool mine = false;
-            if (i < T && succ[i] == -1) {
-                const int j = tail_j[i];
-                const int n = S.first_slot[g0 + j] - S.last_slot[g0 + i];
-                mine = (unsigned long long)__double_as_longlong(tail_a[i]) == head_a[j] &&
-                       head_k[j] == (((unsigned long long)(unsigned)n << 32) | (unsigned)i);
-                if (mine) { succ[i] = j; pred[j] = i; O.affinity[tbase + j] = tail_a[i]; }
-            }
-            any = any || __ballot(mine) != 0ull;
-        }
-        wsync();
-        if (!any) break;
-        if (round == T) err = kErrCapacity;                            // cannot happen: a round that accepts uses up a tail
-    }
-
-    // ---- roots, link count, row labels ----
-    int32_t* root = tail_j;
-    long long n_links = 0;
-    for (int t = lane; t < T; t += kWave) {
-        int r = t, steps = 0;
-        while (pred[r] >= 0 && steps < T) { r = pred[r]; ++steps; }
-        if (pred[r] >= 0) err = kErrCapacity;                          // a cycle: links go forward in time, so there is none
-        root[t] = r;
-        O.pred[tbase + t] = pred[t];
-        O.root[tbase + t] = r;
-        n_links += pred[t] >= 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) n_links += __shfl_xor(n_links, o, kWave);
-    wsync();
-    for (long long d = q.rs0 + lane; d < end; d += kWave) {
+    const link::Matched M = link::match_problem<StitchPolicy>(L, B, ws, O, status, smem);
+    if (!M.ok) return;
+    int err = M.err;
+    for (long long d = M.q.rs0 + lane; d < M.end; d += kWave) {
         const int t = L.local[d];
-        if (t < 0 || t >= T) { err = kErrCapacity; continue; }
-        O.row_root[lbase + d] = root[t];
+        if (t < 0 || t >= M.q.T) { err = kErrCapacity; continue; }
+        O.row_root[M.lbase + d] = M.root[t];
     }
     if (__ballot(err != 0) != 0ull && lane == 0) atomicMax(status, kErrCapacity);
-    if (lane == 0) O.links[p] = n_links;
-}
-
-constexpr const char* kGridText = "%s: %d jobs, %d results x %d streams in one call";
-
-int launch(const char* entry, const Layout& L, const Boxes& B, const Outputs& O, int32_t* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    WT_TRY(wt::ensure_device());
-    const Workspace ws = carve(wt::align_ptr(workspace), (size_t)L.n_jobs, (size_t)L.n_traj_total, (size_t)L.max_traj);
-    WT_TRY(wt::check_workspace_fits(entry, workspace, workspace_bytes, ws.bytes, WT_ERR_CAPACITY));
-    WT_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
-    const size_t P = (size_t)L.n_jobs * (size_t)L.n_streams, RS = (size_t)L.r_sets * (size_t)L.n_streams;
-    const long long n_traj = (long long)L.n_jobs * L.n_traj_total, n_row = (long long)L.n_jobs * L.n_rows;
-    const long long n_init = n_traj > n_row ? n_traj : n_row;
-    if (n_init > 0x7fffffffll * 256) { wt::set_error("%s: %d jobs over %lld rows in one call", entry, (int)L.n_jobs, (long long)L.n_rows); return WT_ERR_CAPACITY; }
-    if (n_init) hipLaunchKernelGGL(stitch_init_kernel, dim3((unsigned)((n_init + 255) / 256)), dim3(256), 0, stream, O, n_traj, n_row);
-    if (P) {
-        hipLaunchKernelGGL(stitch_summary_kernel, dim3((unsigned)RS), dim3(kWave), 0, stream, L, ws.sum, (int*)status_dev);
-        hipLaunchKernelGGL(stitch_match_kernel, dim3((unsigned)P), dim3(kWave), (size_t)L.lds_traj * kTableBytes, stream, L, B, ws, O, (int*)status_dev);
-    }
-    WT_HIP(hipGetLastError());
-    return WT_OK;
+    if (lane == 0) O.links[blockIdx.x] = M.n_links;
 }
 
 }  // namespace
@@ -298,8 +67,7 @@ void wt_stitch_tracks_limits(int32_t* lds_trajectories) {
 }
 
 size_t wt_stitch_tracks_workspace(int32_t n_jobs, int32_t n_streams, int64_t n_rows, int64_t n_traj_total, int64_t max_traj) {
-    if (n_jobs < 0 || n_streams < 0 || n_rows < 0 || n_traj_total < 0 || max_traj < 0) return 0;
-    return carve(nullptr, (size_t)n_jobs, (size_t)n_traj_total, (size_t)(max_traj > 0 ? max_traj : 1)).bytes + 256;
+    return link::workspace_bytes<StitchPolicy>(n_jobs, n_streams, n_rows, n_traj_total, max_traj);
 }
 
 int wt_stitch_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
@@ -314,15 +82,15 @@ int wt_stitch_tracks_dev(int64_t n_frames, int32_t n_streams, const int64_t* str
                                 stream_frame_offsets && set_row_offsets && frame_row_offsets && x && y && w && h && category && local && traj_offsets &&
                                     job_result && job_max_link && job_link_iou && job_motion && out_pred && out_root && out_affinity && out_row_root &&
                                     out_links && status_dev,
-                                wt::grid_fits(n_jobs, n_streams) && wt::grid_fits(r_sets, n_streams), kGridText, (int)n_jobs, (int)r_sets, (int)n_streams));
+                                wt::grid_fits(n_jobs, n_streams) && wt::grid_fits(r_sets, n_streams), link::kGridText, (int)n_jobs, (int)r_sets, (int)n_streams));
     const wt::TrackSet dev = {n_frames, n_streams, stream_frame_offsets, r_sets, set_row_offsets, frame_row_offsets, x, y, w, h, nullptr,
                               category, local, nullptr, n_classes};
     Layout L;
     wt::fill_track_layout(&L, dev, n_rows, traj_offsets, n_traj_total, max_traj, n_jobs, job_result, kLdsTraj);
     L.job_max_link = job_max_link; L.job_motion = job_motion; L.job_link_iou = job_link_iou;
     const Boxes B = {x, y, w, h};
-    const Outputs O = {out_pred, out_root, out_affinity, out_row_root, out_links};
-    return launch("wt_stitch_tracks_dev", L, B, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    const link::Outputs O = {out_pred, out_root, out_affinity, out_row_root, out_links};
+    return link::launch<StitchPolicy>("wt_stitch_tracks_dev", stitch_match_kernel, L, B, O, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int wt_stitch_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* stream_frame_offsets,
@@ -335,37 +103,14 @@ int wt_stitch_tracks_host(int64_t n_frames, int32_t n_streams, const int64_t* st
                                  category, local, n_traj, n_classes}, n_jobs, job_result, job_max_link, job_link_iou, job_motion};
     int64_t max_traj = 0, n_traj_total = 0;
     WT_TRY(wt::check_stitch_layout(in, &max_traj, &n_traj_total));
-    const size_t nr = (size_t)set_row_offsets[r_sets], J = (size_t)n_jobs, nt = (size_t)n_traj_total;
-    if ((J * nt && !(out_pred && out_root && out_affinity)) || (J * nr && !out_row_root) || (J * (size_t)n_streams && !out_links)) {
-        wt::set_error("wt_stitch_tracks_host: bad argument");
-        return WT_ERR_INVALID;
-    }
-    WT_TRY(wt::check_track_args("wt_stitch_tracks_host", n_frames, n_streams, r_sets, (int64_t)nr, n_traj_total, max_traj, n_jobs, n_classes, true,
-                                wt::grid_fits(n_jobs, n_streams) && wt::grid_fits(r_sets, n_streams), kGridText, (int)n_jobs, (int)r_sets, (int)n_streams));
-    WT_TRY(wt::ensure_device());
-    wt::StagedTrackSet st;
-    wt::DevBuf jl, ji, jm, op, oo, oa, orr, ol, dws;
-    WT_TRY(st.upload(in, n_jobs, job_result));
-    WT_TRY(jl.upload(job_max_link, 4 * J * (size_t)n_classes));
-    WT_TRY(ji.upload(job_link_iou, 8 * J * (size_t)n_classes)); WT_TRY(jm.upload(job_motion, 4 * J));
-    WT_TRY(op.alloc(4 * J * nt)); WT_TRY(oo.alloc(4 * J * nt)); WT_TRY(oa.alloc(8 * J * nt)); WT_TRY(orr.alloc(4 * J * nr));
-    WT_TRY(ol.alloc(8 * J * (size_t)n_streams));
-    const size_t wsb = wt_stitch_tracks_workspace(n_jobs, n_streams, (int64_t)nr, n_traj_total, max_traj);
-    WT_TRY(dws.alloc(wsb));
-    Layout L;
-    st.fill(&L, n_traj_total, max_traj, n_jobs, kLdsTraj);
-    L.job_max_link = jl.as<int32_t>(); L.job_motion = jm.as<int32_t>(); L.job_link_iou = ji.as<double>();
-    const Boxes B = {st.dev.x, st.dev.y, st.dev.w, st.dev.h};
-    const Outputs O = {op.as<int32_t>(), oo.as<int32_t>(), oa.as<double>(), orr.as<int32_t>(), ol.as<int64_t>()};
-    WT_TRY(launch("wt_stitch_tracks_host", L, B, O, st.status.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_TRY(st.finish("stitch", "counts or offsets"));
-    if (J * nt) {
-        WT_HIP(hipMemcpy(out_pred, op.p, 4 * J * nt, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(out_root, oo.p, 4 * J * nt, hipMemcpyDeviceToHost));
-        WT_HIP(hipMemcpy(out_affinity, oa.p, 8 * J * nt, hipMemcpyDeviceToHost));
-    }
-    if (J * nr) WT_HIP(hipMemcpy(out_row_root, orr.p, 4 * J * nr, hipMemcpyDeviceToHost));
-    if (J * (size_t)n_streams) WT_HIP(hipMemcpy(out_links, ol.p, 8 * J * (size_t)n_streams, hipMemcpyDeviceToHost));
-    return WT_OK;
+    const size_t jc = (size_t)n_jobs * (size_t)n_classes;
+    wt::DevBuf jl, ji, jm;
+    return link::run_host<StitchPolicy, Layout, link::Outputs>("wt_stitch_tracks_host", "stitch", stitch_match_kernel, in, n_jobs, job_result, n_traj_total,
+                                                               max_traj, [&](Layout* L, link::Outputs*) {
+        WT_TRY(jl.upload(job_max_link, 4 * jc)); WT_TRY(ji.upload(job_link_iou, 8 * jc)); WT_TRY(jm.upload(job_motion, 4 * (size_t)n_jobs));
+        L->job_max_link = jl.as<int32_t>(); L->job_link_iou = ji.as<double>(); L->job_motion = jm.as<int32_t>();
+        return (int)WT_OK;
+    }, {out_pred, out_root, out_affinity, out_row_root, out_links});
 }
 
 }  // extern "C"

@@ -125,6 +125,12 @@ int check_job_results(const int32_t* job_result, int32_t n_jobs, int32_t r_sets,
     return WT_OK;
 }
 
+// the motion of job j of a linking pass (stitch_host.h, xlink_host.h)
+inline int check_link_motion(const int32_t* job_motion, int32_t j) {
+    if (job_motion[j] != 0 && job_motion[j] != 1) { set_error("job %d: motion must be 0 (hold) or 1 (linear)", (int)j); return WT_ERR_INVALID; }
+    return WT_OK;
+}
+
 // a * b blocks fit one grid dimension
 inline bool grid_fits(uint64_t a, uint64_t b) { return a * b <= 0x7fffffffull; }
 

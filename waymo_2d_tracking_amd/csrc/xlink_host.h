@@ -44,7 +44,7 @@ inline int check_xlink_layout(const XLinkInput& in, int64_t* max_traj, int64_t* 
                                  max_traj, n_traj_total));
     if (in.n_classes > kXLinkMaxClasses) { set_error("wt_xlink_tracks_host: %d classes, at most %d", (int)in.n_classes, (int)kXLinkMaxClasses); return WT_ERR_INVALID; }
     return check_job_results(in.job_result, in.n_jobs, in.r_sets, [&](int32_t j) {
-        if (in.job_motion[j] != 0 && in.job_motion[j] != 1) { set_error("job %d: motion must be 0 (hold) or 1 (linear)", (int)j); return WT_ERR_INVALID; }
+        WT_TRY(check_link_motion(in.job_motion, j));
         return check_xlink_pair_tables(in.job_pair_max_link, in.job_pair_link_iou, j, in.n_classes);
     });
 }
