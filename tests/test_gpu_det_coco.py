@@ -78,6 +78,31 @@ def test_three_hundred_categories():
     assert (got['precision'][:, :, :, 298] == -1).all() and (got['precision'][:, 0, :, 299, 0, 2] > 0.99).all()
 
 
+def test_two_sets_without_rows():
+    """n_det = 0 with K = 2: only the offsets and curve kernels run."""
+    gt, p, got = run_case('two_empty_sets', lambda: (CC.hand_cases()['j_three_step_curve'][0], [[], []], False))
+    assert p['set_row_offsets'].tolist() == [0, 0, 0] and got['npig'][:, 0, 0].tolist() == [3, 3]
+    assert (got['precision'][:, :, :, 0, 0] == 0).all() and (got['recall'][:, :, 0, 0] == 0).all()
+
+
+def test_every_row_takes_no_part():
+    """Category indices outside 0..n_cats - 1, which only the device form lets through: all rows sort into the last segment, the
+    one no curve reads, and the tables are those of a result without rows."""
+    E = evaluate()
+    annotations, sets, _ = CC.random_case(2, 2)
+    gt = E.pack_coco_ground_truth(annotations)
+    p = E.pack_coco_detections(gt, sets)
+    p['cat'][:] = np.where(np.arange(len(p['cat'])) % 2, gt['n_cats'], -1).astype(np.int32)
+    dev = E.DeviceCocoEvaluation(gt, p)
+    dev.launch()
+    res = dev.results()
+    exp = R.call_from_packed(gt, p)
+    assert (exp['rank'] == -1).all() and (exp['npig'] > 0).any() and exp['precision'].max() == 0
+    got = dict(precision=np.stack([r.precision for r in res]), recall=np.stack([r.recall for r in res]), npig=np.stack([r.npig for r in res]),
+               rank=np.concatenate([r.rank for r in res]), match_gt=np.concatenate([r.match_gt for r in res]), ignore=np.concatenate([r.ignore for r in res]))
+    assert_equal(got, exp)
+
+
 def half_case():
     annotations, sets, _ = CC.random_case(2, 2)
     return annotations, [[r for r in sets[0] if r['image_id'] < 'img020'], [r for r in sets[1] if r['image_id'] >= 'img030']], True

@@ -41,11 +41,11 @@ def reference(annotations, detections, metric, min_conf=0.01):
     return g, d, R.evaluate(g, d, 4, [R.THRESHOLDS[metric](n) for n in names[1:]], min_conf)
 
 
-def assert_equals_restatement(got, ref, d, n_thr):
+def assert_equals_restatement(got, ref, d, n_thr, labels=LABELS):
     """DetResult (per_row=True) against det_ap_ref.evaluate() on the same rows, by the three rules."""
     assert np.array_equal(got.tp_flag, ref['tp_flag'])
     assert np.array_equal(got.match_gt, ref['match_gt'])
-    for c in LABELS:
+    for c in labels:
         assert np.array_equal(got.order[c], ref['order'][c]), c
         for t in range(n_thr):
             for bi, b in enumerate(('', 'S', 'M', 'L')):
@@ -206,6 +206,25 @@ def test_edge_problems():
     # no detection anywhere
     empty = E.evaluate_detection_sets(annotations, [{}], per_row=True)[0]
     assert empty.tp.sum() == 0 and empty.fp.sum() == 0 and np.isnan(empty.ar).all() and (empty.ap == 0).all() and empty.npos[1, 0, 0] == 2
+
+
+def test_two_sets_without_rows_and_two_whose_rows_all_take_no_part():
+    """n_det = 0 with K = 2: only the offsets and curve kernels run.  Every confidence at or under min_conf: all rows sort into the
+    last segment, the one no curve reads."""
+    from waymo_2d_tracking_amd.detnet import evaluate as E
+    f = lambda rows: np.asarray(rows, np.float32).reshape(-1, 5)
+    annotations = _ann(['a', 'b'], [('a', 1, [100, 100, 200, 200]), ('a', 2, [500, 500, 50, 100]), ('b', 2, [10, 10, 20, 20])])
+    detections = {'a': [f([[0.9, 0.2, 0.2, 0.2, 0.2], [0.9, 0.2, 0.2, 0.2, 0.2]]), f([[0.5, 0.5, 0.5, 0.1, 0.1]]), f([]), f([])],
+                  'b': [f([]), f([[0.7, 0.5, 0.5, 0.1, 0.1]]), f([[0.9, 0.5, 0.5, 0.1, 0.1]]), f([])]}
+    for sets, min_conf in (([{}, {}], [0.01, 0.01]), ([detections, detections], [0.9, 2.0])):
+        got = E.evaluate_detection_sets(annotations, sets, min_conf=min_conf, per_row=True)
+        assert len(got) == 2
+        for k in range(2):
+            g, d, ref = reference(annotations, sets[k], 'waymo', min_conf[k])
+            assert_equals_restatement(got[k], ref, d, 1)
+            assert got[k].tp.sum() == 0 and got[k].fp.sum() == 0 and (got[k].tp_flag == 2).all() and len(got[k].tp_flag) == len(d['conf'])
+            assert np.isnan(got[k].ar).all() and (got[k].ap == 0).all() and got[k].npos[1, 0, 0] == 2
+            assert all(len(got[k].order[c]) == 0 for c in LABELS)
 
 
 def test_shuffled_input_rows_give_the_sorted_result(g8):

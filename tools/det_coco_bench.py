@@ -171,7 +171,7 @@ def main():
 
 
 STAGES = (('prep + npig', ('coco_prep_kernel', 'coco_npig_kernel', 'coco_npig_fill_kernel')), ('select + match', ('coco_match_kernel',)),
-          ('order (rocPRIM sorts, gathers, offsets)', ('rocprim', 'coco_gather_seg_kernel', 'coco_gather_rows_kernel', 'coco_offsets_kernel')),
+          ('order (rocPRIM sorts, gathers, offsets)', ('rocprim', 'det_gather_seg_kernel', 'coco_gather_rows_kernel', 'det_offsets_kernel')),
           ('curve', ('coco_curve_kernel',)))
 TRACE_CALLS = 8                                     # --trace-run: 3 warm-up + 5 launches
 

@@ -43,6 +43,7 @@ UNITS = {
     'tracks_layout.hip': ['-ffp-contract=off'],        # track layouts: integers and bit-copies only; the flag matches the units whose headers it includes
     'det_eval.hip': ['-ffp-contract=off'],           # detection AP: float64 IoU / precision / recall rounded operation by operation
     'det_coco_eval.hip': ['-ffp-contract=off'],      # COCO AP / AR: float64 IoU, precision and recall rounded operation by operation
+    'det_order.hip': ['-ffp-contract=off'],          # the ordering step of both: integers only; the flag matches the units whose headers it includes
     'det_roialign.hip': [],
     'det_nms.hip': [],
     'det_deform.hip': [],

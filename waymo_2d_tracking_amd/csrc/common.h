@@ -58,6 +58,10 @@ struct DevBuf {
         if (n) WT_HIP(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
         return WT_OK;
     }
+    int download(void* dst) const {              // device -> host, all of it, when there is anything to copy
+        if (bytes) WT_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+        return WT_OK;
+    }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 

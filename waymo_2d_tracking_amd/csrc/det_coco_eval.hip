@@ -10,17 +10,15 @@
 //           tile for ITS (area range, threshold) chain: best free not-ignored box (ties to the last), else best ignored one.  The
 //           "taken" sets are one 64-bit word per ground-truth row (bit = chain) in LDS, in the workspace for images with more
 //           than kTakenLds rows;
-//   order   a stable sort of the rows by (set, category, score descending): rocPRIM's device radix sort twice, LSD fashion;
+//   order   a stable sort of the rows by (set, category, score descending), equal scores in input order (det_order.h);
 //   gather  rank and the matched / ignored bit words of every row, in sorted order;
 //   curve   one workgroup per (set, category, area range, max_dets, threshold): prefix sums of TP / FP, precision and recall per
 //           TP row, the best precision per recall bucket with LDS atomics, a suffix maximum over the buckets = the 101 samples.
 // No kernel waits for another workgroup, every loop bound is an input size, and there is no per-problem capacity.
 // Compile with -ffp-contract=off: IoU, precision and recall are rounded operation by operation like numpy's.
-#include "common.h"
-#include "sort_device.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <algorithm>
-#include <mutex>
+#include "det_metric_device.h"
+#include "det_metric_host.h"
+#include "det_order.h"
 
 using namespace wtdev;
 
@@ -48,56 +46,21 @@ struct Params {
 };
 
 struct Workspace {
-    unsigned long long *key_in, *key_out;     // [n_det] score keys before / after the first sort
-    long long *row_in, *row_mid, *order;      // [n_det] row indices: iota, after the first sort, after the second
-    unsigned int *seg, *seg_in, *seg_out;     // [n_det] (set, category) segment of a row; gathered; sorted
+    wt::OrderBufs o;                          // keys = score keys, segments = (set, category)
     int32_t* rank;                            // [n_det] rank in the problem, -1 = takes no part
     unsigned long long *mbits, *ibits;        // [n_det] bit a * T + t: matched / ignored
     uint8_t* srank;                           // [n_det] rank by sorted position, 255 = takes no part
     unsigned long long *smbits, *sibits;      // [n_det] the bit words by sorted position
     unsigned long long* taken;                // [K * n_gt] taken words of the images with more than kTakenLds rows
     long long* npig;                          // [K * C * A]
-    long long* class_offsets;                 // [K * (C + 1)]
-    void* sort_tmp;
-    size_t sort_tmp_bytes;
     size_t bytes;
 };
 
-int seg_bits(size_t n_segments) {
-    int b = 1;
-    while (((size_t)1 << b) <= n_segments) ++b;
-    return b;
-}
-
-int sort_tmp_bytes(size_t n_det, int bits, size_t* out) {
-    static std::mutex mu;
-    static size_t last_n = ~(size_t)0, last_bytes = 0;
-    static int last_bits = -1;
-    std::lock_guard<std::mutex> lock(mu);
-    if (n_det == last_n && bits == last_bits) { *out = last_bytes; return WT_OK; }
-    size_t a = 0, b = 0;
-    unsigned long long* k64 = nullptr;
-    unsigned int* k32 = nullptr;
-    long long* v = nullptr;
-    WT_HIP(rocprim::radix_sort_pairs(nullptr, a, k64, k64, v, v, n_det, 0u, 64u, (hipStream_t) nullptr));
-    WT_HIP(rocprim::radix_sort_pairs(nullptr, b, k32, k32, v, v, n_det, 0u, (unsigned)bits, (hipStream_t) nullptr));
-    *out = std::max(a, b) + 256;
-    last_n = n_det; last_bits = bits; last_bytes = *out;
-    return WT_OK;
-}
-
-Workspace carve(void* base, size_t K, size_t C, size_t A, size_t n_gt, size_t n_det, size_t sort_tmp) {
+int carve(void* base, size_t K, size_t C, size_t A, size_t n_gt, size_t n_det, Workspace* ws) {
     wt::Carver cv(base);
-    Workspace w;
+    Workspace& w = *ws;
     const size_t nd = n_det ? n_det : 1, slots = K * n_gt ? K * n_gt : 1;
-    w.key_in = cv.take<unsigned long long>(nd);
-    w.key_out = cv.take<unsigned long long>(nd);
-    w.row_in = cv.take<long long>(nd);
-    w.row_mid = cv.take<long long>(nd);
-    w.order = cv.take<long long>(nd);
-    w.seg = cv.take<unsigned int>(nd);
-    w.seg_in = cv.take<unsigned int>(nd);
-    w.seg_out = cv.take<unsigned int>(nd);
+    WT_TRY(wt::carve_order(cv, n_det, K, C, &w.o));
     w.rank = cv.take<int32_t>(nd);
     w.mbits = cv.take<unsigned long long>(nd);
     w.ibits = cv.take<unsigned long long>(nd);
@@ -106,27 +69,11 @@ Workspace carve(void* base, size_t K, size_t C, size_t A, size_t n_gt, size_t n_
     w.sibits = cv.take<unsigned long long>(nd);
     w.taken = cv.take<unsigned long long>(slots);
     w.npig = cv.take<long long>(K * C * A);
-    w.class_offsets = cv.take<long long>(K * (C + 1));
-    w.sort_tmp = cv.take<char>(sort_tmp);
-    w.sort_tmp_bytes = sort_tmp;
     w.bytes = cv.off;
-    return w;
+    return WT_OK;
 }
 
-// ---- device helpers ----------------------------------------------------------------------------------------------------
-// Larger key = higher score; -0.0 == 0.0; never 0 for a number (0 marks "not a row of this category" in a tile).
-__device__ __forceinline__ unsigned long long score_key(double v) {
-    if (v == 0.0) v = 0.0;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-// the wave reads taken words that its own atomics wrote: every access of a word in the workspace goes to L2
-__device__ __forceinline__ void gsync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-    __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ unsigned long long word_load(unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void word_store(unsigned long long* p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// desc_key of a score: larger key = higher score; 0 marks "not a row of this category" in a tile
 
 // ---- prep ----------------------------------------------------------------------------------------------------------------
 __global__ void coco_prep_kernel(long long n_det, int K, int C, int AT, const int64_t* __restrict__ set_row_offsets, const double* __restrict__ score,
@@ -134,16 +81,12 @@ __global__ void coco_prep_kernel(long long n_det, int K, int C, int AT, const in
                                  uint8_t* __restrict__ ign_out) {
     const long long d = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= n_det) return;
-    int lo = 0, hi = K;                                 // set of the row: last k with set_row_offsets[k] <= d
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (set_row_offsets[mid] <= d) lo = mid; else hi = mid;
-    }
+    const int lo = set_of_row(set_row_offsets, K, d);
     const int c = category[d];
     const bool part = c >= 0 && c < C;
-    ws.key_in[d] = ~score_key(score[d]);
-    ws.row_in[d] = d;
-    ws.seg[d] = part ? (unsigned)(lo * C + c) : (unsigned)(K * C);
+    ws.o.key_in[d] = ~desc_key(score[d]);
+    ws.o.row_in[d] = d;
+    ws.o.seg[d] = part ? (unsigned)(lo * C + c) : (unsigned)(K * C);
     rank[d] = -1;
     if (match_out)
         for (int q = 0; q < AT; ++q) { match_out[(size_t)d * AT + q] = -1; ign_out[(size_t)d * AT + q] = 0; }
@@ -165,14 +108,7 @@ __global__ void coco_npig_kernel(long long n_gt, long long n_images, int C, int 
     const long long k = blockIdx.y;
     const int c = r < n_gt ? g_cat[r] : -1;
     bool counts = c >= 0 && c < C && !g_crowd[r];
-    if (counts && image_mask) {
-        long long lo = 0, hi = n_images;                // image of the row: last i with image_gt_offsets[i] <= r
-        while (hi - lo > 1) {
-            const long long mid = (lo + hi) >> 1;
-            if (image_gt_offsets[mid] <= r) lo = mid; else hi = mid;
-        }
-        counts = image_mask[k * n_images + lo] != 0;
-    }
+    if (counts && image_mask) counts = image_mask[k * n_images + image_of_row(image_gt_offsets, n_images, r)] != 0;
     if (counts) {
         const double area = g_area[r];
         for (int a = 0; a < A; ++a)
@@ -208,13 +144,12 @@ __global__ __launch_bounds__(kWave) void coco_match_kernel(
     __shared__ int sel[kCap];
     __shared__ unsigned long long taken_lds[kTakenLds];
     const int lane = threadIdx.x & 63;
-    const size_t p = blockIdx.x;
-    const int c = (int)(p % (size_t)C);
-    const long long img = (long long)((p / (size_t)C) % (size_t)n_images);
-    const long long k = (long long)(p / ((size_t)C * (size_t)n_images));
+    const DetProblem prob(blockIdx.x, n_images, C);
+    const int c = prob.c;
+    const long long img = prob.img, k = prob.k;
     if (image_mask && !image_mask[k * n_images + img]) return;
-    const long long d0 = set_row_offsets[k] + image_det_offsets[k * (n_images + 1) + img];
-    const long long d1 = set_row_offsets[k] + image_det_offsets[k * (n_images + 1) + img + 1];
+    long long d0, d1;
+    prob.rows(set_row_offsets, image_det_offsets, n_images, &d0, &d1);
     if (d0 >= d1) return;
 
     // ---- select: rank of every row of the category among them by (score key descending, input index) ----
@@ -225,12 +160,12 @@ __global__ __launch_bounds__(kWave) void coco_match_kernel(
         const unsigned long long mm = __ballot(mine);
         if (mm == 0ull) continue;
         n_c += __popcll(mm);
-        const unsigned long long key = mine ? score_key(D.score[d]) : 0ull;
+        const unsigned long long key = mine ? desc_key(D.score[d]) : 0ull;
         int before = 0;
         for (long long tb = d0; tb < d1; tb += kWave) {
             const long long e = tb + lane;
             wsync();                                     // the previous tile has been read
-            tkey[lane] = ((e < d1) && D.cat[e] == c) ? score_key(D.score[e]) : 0ull;
+            tkey[lane] = ((e < d1) && D.cat[e] == c) ? desc_key(D.score[e]) : 0ull;
             wsync();
             if (mine) {
                 const int nt = (int)((d1 - tb) < kWave ? (d1 - tb) : kWave);
@@ -253,7 +188,7 @@ __global__ __launch_bounds__(kWave) void coco_match_kernel(
     unsigned long long* taken_g = ws.taken + (size_t)k * (size_t)n_gt + (size_t)g0;
     for (long long i = lane; i < g1 - g0; i += kWave) {
         if (in_lds) taken_lds[i] = 0ull;
-        else if (G.cat[g0 + i] == c) word_store(&taken_g[i], 0ull);      // the other rows belong to the waves of their categories
+        else if (G.cat[g0 + i] == c) slot_store(&taken_g[i], 0ull);      // the other rows belong to the waves of their categories
     }
     if (in_lds) wsync(); else gsync();
 
@@ -314,7 +249,7 @@ __global__ __launch_bounds__(kWave) void coco_match_kernel(
                 const int j = __builtin_ctzll(mm);
                 mm &= mm - 1ull;
                 const long long r = gb + j;
-                const unsigned long long tk = in_lds ? taken_lds[r - g0] : word_load(&taken_g[r - g0]);
+                const unsigned long long tk = in_lds ? taken_lds[r - g0] : slot_load(&taken_g[r - g0]);
                 const double v = tiou[j];
                 const unsigned f = tflag[j];
                 if (act && !((tk & my_bit) && !(f & 0x80u)) && !(v < bound)) {
@@ -342,24 +277,7 @@ __global__ __launch_bounds__(kWave) void coco_match_kernel(
     }
 }
 
-// ---- ordering helpers ------------------------------------------------------------------------------------------------------
-__global__ void coco_gather_seg_kernel(long long n, const long long* __restrict__ rows, const unsigned int* __restrict__ seg, unsigned int* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = seg[rows[i]];
-}
-
-__global__ void coco_offsets_kernel(long long n, int K, int C, const unsigned int* __restrict__ seg_sorted, long long* __restrict__ class_offsets) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)K * (C + 1)) return;
-    const unsigned int s = (unsigned int)((i / (C + 1)) * C + i % (C + 1));
-    long long lo = 0, hi = n;                            // lower bound of s
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (seg_sorted[mid] < s) lo = mid + 1; else hi = mid;
-    }
-    class_offsets[i] = lo;
-}
-
+// ---- rank and bit words in sorted order ------------------------------------------------------------------------------------
 __global__ void coco_gather_rows_kernel(long long n, const long long* __restrict__ order, const int32_t* __restrict__ rank, Workspace ws) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -371,29 +289,6 @@ __global__ void coco_gather_rows_kernel(long long n, const long long* __restrict
 }
 
 // ---- curve -----------------------------------------------------------------------------------------------------------------
-// exclusive prefix sum over the workgroup's threads; *total = the sum.  lds: kCurveWaves ints.
-__device__ __forceinline__ int block_excl_sum(int v, int* total, int* lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int u = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();                                     // the previous use of lds is over
-    if (lane == kWave - 1) lds[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kCurveWaves; ++w) {
-        const int s = lds[w];
-        if (w < wave) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(kCurveThreads) void coco_curve_kernel(int C, int T, int A, int M, int R, Params P, Workspace ws,
                                                                    double* __restrict__ precision, double* __restrict__ recall) {
     __shared__ int lds_i[kCurveWaves];
@@ -416,7 +311,7 @@ __global__ __launch_bounds__(kCurveThreads) void coco_curve_kernel(int C, int T,
     }
     for (int ri = tid; ri < kMaxRec; ri += kCurveThreads) { bucket[ri] = 0ull; rec[ri] = ri < R ? P.rec[ri] : 0.; }
     __syncthreads();
-    const long long o0 = ws.class_offsets[k * (C + 1) + c], o1 = ws.class_offsets[k * (C + 1) + c + 1];
+    const long long o0 = ws.o.class_offsets[k * (C + 1) + c], o1 = ws.o.class_offsets[k * (C + 1) + c + 1];
     const int md = P.max_dets[m];
     const int chain = a * T + t;
     const double npig_d = (double)npig;
@@ -439,7 +334,7 @@ __global__ __launch_bounds__(kCurveThreads) void coco_curve_kernel(int C, int T,
             packed += (tpv[u] << 16) + fpv[u];
         }
         int tile_total;
-        const int before = block_excl_sum(packed, &tile_total, lds_i);
+        const int before = block_excl_sum<kCurveWaves>(packed, &tile_total, lds_i);
         long long ctp = run_tp + (before >> 16), cfp = run_fp + (before & 0xffff);
 #pragma unroll
         for (int u = 0; u < kCurveItems; ++u) {
@@ -512,9 +407,9 @@ extern "C" {
 size_t wt_det_coco_workspace(int32_t k_sets, int64_t n_images, int32_t n_cats, int32_t n_thr, int32_t n_rec, int32_t n_area, int32_t n_maxdet,
                              int64_t n_gt, int64_t n_det) {
     if (check_sizes(k_sets, n_images, n_cats, n_thr, n_rec, n_area, n_maxdet, n_gt, n_det) != WT_OK) return 0;
-    size_t tmp = 0;
-    if (sort_tmp_bytes((size_t)n_det, seg_bits((size_t)k_sets * n_cats), &tmp) != WT_OK) return 0;
-    return carve(nullptr, (size_t)k_sets, (size_t)n_cats, (size_t)n_area, (size_t)n_gt, (size_t)n_det, tmp).bytes + 256;
+    Workspace ws;
+    if (carve(nullptr, (size_t)k_sets, (size_t)n_cats, (size_t)n_area, (size_t)n_gt, (size_t)n_det, &ws) != WT_OK) return 0;
+    return ws.bytes + 256;
 }
 
 int wt_det_coco_dev(int64_t n_gt, const double* gx, const double* gy, const double* gw, const double* gh, const double* g_area,
@@ -540,10 +435,8 @@ int wt_det_coco_dev(int64_t n_gt, const double* gx, const double* gy, const doub
         return WT_ERR_INVALID;
     }
     const int K = k_sets, C = n_cats, T = n_thr, A = n_area, M = n_maxdet, R = n_rec;
-    const int bits = seg_bits((size_t)K * C);
-    size_t tmp = 0;
-    WT_TRY(sort_tmp_bytes((size_t)n_det, bits, &tmp));
-    Workspace ws = carve(wt::align_ptr(workspace), (size_t)K, (size_t)C, (size_t)A, (size_t)n_gt, (size_t)n_det, tmp);
+    Workspace ws;
+    WT_TRY(carve(wt::align_ptr(workspace), (size_t)K, (size_t)C, (size_t)A, (size_t)n_gt, (size_t)n_det, &ws));
     if (!workspace || workspace_bytes < ws.bytes + 256) {
         wt::set_error("COCO evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
         return WT_ERR_CAPACITY;
@@ -568,16 +461,9 @@ int wt_det_coco_dev(int64_t n_gt, const double* gx, const double* gy, const doub
         hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)n_problems), dim3(kWave), 0, stream, G, image_gt_offsets, (long long)n_images, (long long)n_gt,
                            C, T, A, (int)P.max_dets[M - 1], P, set_row_offsets, image_det_offsets, D, image_mask, ws, rk, match_gt, ignore);
     }
-    if (n_det > 0) {
-        size_t bytes = ws.sort_tmp_bytes;
-        WT_HIP(rocprim::radix_sort_pairs(ws.sort_tmp, bytes, ws.key_in, ws.key_out, ws.row_in, ws.row_mid, (size_t)n_det, 0u, 64u, stream));
-        hipLaunchKernelGGL(coco_gather_seg_kernel, dim3((unsigned)((n_det + 255) / 256)), dim3(256), 0, stream, (long long)n_det, ws.row_mid, ws.seg, ws.seg_in);
-        bytes = ws.sort_tmp_bytes;
-        WT_HIP(rocprim::radix_sort_pairs(ws.sort_tmp, bytes, ws.seg_in, ws.seg_out, ws.row_mid, ws.order, (size_t)n_det, 0u, (unsigned)bits, stream));
-        hipLaunchKernelGGL(coco_gather_rows_kernel, dim3((unsigned)((n_det + 255) / 256)), dim3(256), 0, stream, (long long)n_det, ws.order, rk, ws);
-    }
-    const long long n_off = (long long)K * (C + 1);
-    hipLaunchKernelGGL(coco_offsets_kernel, dim3((unsigned)((n_off + 255) / 256)), dim3(256), 0, stream, (long long)n_det, K, C, ws.seg_out, ws.class_offsets);
+    WT_TRY(wt::enqueue_order(ws.o, n_det, K, C, ws.o.order, nullptr, stream));
+    if (n_det > 0)
+        hipLaunchKernelGGL(coco_gather_rows_kernel, dim3((unsigned)((n_det + 255) / 256)), dim3(256), 0, stream, (long long)n_det, ws.o.order, rk, ws);
     hipLaunchKernelGGL(coco_curve_kernel, dim3((unsigned)((size_t)K * C * A * M * T)), dim3(kCurveThreads), 0, stream, C, T, A, M, R, P, ws, precision, recall);
     WT_HIP(hipGetLastError());
     return WT_OK;
@@ -604,47 +490,16 @@ int wt_det_coco_host(int64_t n_gt, const double* gx, const double* gy, const dou
         return WT_ERR_INVALID;
     }
     // ---- the layout must be what the kernels walk, and the numbers finite: checked here, the device form trusts its caller ----
-    if (image_gt_offsets[0] != 0 || image_gt_offsets[n_images] != n_gt || set_row_offsets[0] != 0) {
-        wt::set_error("wt_det_coco_host: CSR offsets do not cover the rows");
-        return WT_ERR_INVALID;
-    }
-    for (int64_t i = 0; i < n_images; ++i)
-        if (image_gt_offsets[i + 1] < image_gt_offsets[i]) { wt::set_error("image_gt_offsets must be non-decreasing (image %lld)", (long long)i); return WT_ERR_INVALID; }
-    auto finite = [](double v) { return (v == v) && (v - v == 0.0); };
-    for (int64_t r = 0; r < n_gt; ++r) {
-        if (g_cat[r] < 0 || g_cat[r] >= n_cats) {
-            wt::set_error("ground-truth row %lld: category index %d outside 0..%d", (long long)r, (int)g_cat[r], (int)n_cats - 1);
-            return WT_ERR_INVALID;
-        }
-        if (!finite(gx[r]) || !finite(gy[r]) || !finite(gw[r]) || !finite(gh[r]) || !finite(g_area[r])) {
-            wt::set_error("ground-truth row %lld: a coordinate or the area is not finite", (long long)r);
-            return WT_ERR_INVALID;
-        }
-    }
-    for (int32_t k = 0; k < k_sets; ++k) {
-        const int64_t* ido = image_det_offsets + (size_t)k * (size_t)(n_images + 1);
-        const int64_t rows = set_row_offsets[k + 1] - set_row_offsets[k];
-        if (rows < 0 || ido[0] != 0 || ido[n_images] != rows) { wt::set_error("result set %d: image_det_offsets do not cover its rows", (int)k); return WT_ERR_INVALID; }
-        for (int64_t i = 0; i < n_images; ++i)
-            if (ido[i + 1] < ido[i]) { wt::set_error("result set %d: image_det_offsets must be non-decreasing (image %lld)", (int)k, (long long)i); return WT_ERR_INVALID; }
-        for (int64_t r = set_row_offsets[k]; r < set_row_offsets[k + 1]; ++r) {
-            if (category[r] < 0 || category[r] >= n_cats) {
-                wt::set_error("result set %d, row %lld: category index %d outside 0..%d", (int)k, (long long)(r - set_row_offsets[k]), (int)category[r], (int)n_cats - 1);
-                return WT_ERR_INVALID;
-            }
-            if (!finite(score[r]) || !finite(x[r]) || !finite(y[r]) || !finite(w[r]) || !finite(h[r])) {
-                wt::set_error("result set %d, row %lld: the score or a coordinate is not finite", (int)k, (long long)(r - set_row_offsets[k]));
-                return WT_ERR_INVALID;
-            }
-        }
-    }
+    const wt::DetLayout layout = {n_gt, n_images, k_sets, image_gt_offsets, set_row_offsets, image_det_offsets};
+    const double* gsrc[5] = {gx, gy, gw, gh, g_area};
+    const double* dsrc[5] = {score, x, y, w, h};
+    WT_TRY(wt::check_det_layout(layout, "wt_det_coco_host"));
+    WT_TRY(wt::check_det_coco_rows(layout, gsrc, g_cat, dsrc, category, n_cats));
     WT_TRY(wt::ensure_device());
     const size_t ng = (size_t)n_gt, nd = (size_t)n_det, K = (size_t)k_sets, C = (size_t)n_cats, T = (size_t)n_thr, A = (size_t)n_area, M = (size_t)n_maxdet,
                  R = (size_t)n_rec, ni = (size_t)n_images;
     const size_t n_prec = K * T * R * C * A * M, n_rcl = K * T * C * A * M, n_np = K * C * A;
     wt::DevBuf dg[5], dgc, dgw, dio, dsr, dido, dd[5], dcat, dmask, dprec, drcl, dnp, drank, dmatch, dign, dstat, dws;
-    const double* gsrc[5] = {gx, gy, gw, gh, g_area};
-    const double* dsrc[5] = {score, x, y, w, h};
     for (int i = 0; i < 5; ++i) WT_TRY(dg[i].upload(gsrc[i], 8 * ng));
     for (int i = 0; i < 5; ++i) WT_TRY(dd[i].upload(dsrc[i], 8 * nd));
     WT_TRY(dgc.upload(g_cat, 4 * ng));
@@ -667,17 +522,10 @@ int wt_det_coco_host(int64_t n_gt, const double* gx, const double* gy, const dou
                            image_mask ? dmask.as<uint8_t>() : nullptr, n_cats, n_thr, thr, n_rec, rec, n_area, area_rng, n_maxdet, max_dets,
                            dprec.as<double>(), drcl.as<double>(), dnp.as<int64_t>(), rank ? drank.as<int32_t>() : nullptr,
                            match_gt ? dmatch.as<int64_t>() : nullptr, match_gt ? dign.as<uint8_t>() : nullptr, dstat.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_HIP(hipDeviceSynchronize());
-    int32_t st = 0;
-    WT_HIP(hipMemcpy(&st, dstat.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (st) { wt::set_error("COCO evaluation kernel reported status %d", (int)st); return (int)st; }
-    WT_HIP(hipMemcpy(precision, dprec.p, 8 * n_prec, hipMemcpyDeviceToHost));
-    WT_HIP(hipMemcpy(recall, drcl.p, 8 * n_rcl, hipMemcpyDeviceToHost));
-    WT_HIP(hipMemcpy(npig, dnp.p, 8 * n_np, hipMemcpyDeviceToHost));
-    if (nd) {
-        if (rank) WT_HIP(hipMemcpy(rank, drank.p, 4 * nd, hipMemcpyDeviceToHost));
-        if (match_gt) { WT_HIP(hipMemcpy(match_gt, dmatch.p, 8 * nd * A * T, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(ignore, dign.p, nd * A * T, hipMemcpyDeviceToHost)); }
-    }
+    WT_TRY(wt::finish_det_call(dstat, "COCO evaluation", ""));
+    WT_TRY(dprec.download(precision)); WT_TRY(drcl.download(recall)); WT_TRY(dnp.download(npig));
+    if (rank) WT_TRY(drank.download(rank));
+    if (match_gt) { WT_TRY(dmatch.download(match_gt)); WT_TRY(dign.download(ignore)); }
     return WT_OK;
 }
 

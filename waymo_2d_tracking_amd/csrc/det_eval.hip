@@ -7,19 +7,14 @@
 //   match   one wavefront per problem (set, image, class): float64 IoU of every participating row against the class's
 //           ground-truth rows in LDS tiles of 64, running first-argmax, then "the most confident row that claims a box" per
 //           threshold with two atomics per claim on the box's slot (max of the confidence key, then min of the row index);
-//   order   a stable sort of the rows by (set, class, confidence descending): rocPRIM's device radix sort twice, LSD fashion -
-//           64 key bits of confidence, then the segment bits; both passes are stable, so equal confidences keep the input
-//           order (image order, then file order).  Its temporary storage is part of the caller's workspace;
+//   order   a stable sort of the rows by (set, class, confidence descending), equal confidences in input order (det_order.h);
 //   curve   one workgroup per (set, class, threshold, size bucket): totals forward, then the tiles backwards with a prefix sum of
 //           TP / FP, the reverse running maximum of the precision and the AP terms.
 // No kernel waits for another workgroup, every loop bound is an input size, and there is no per-problem capacity.
 // Compile with -ffp-contract=off: IoU, precision, recall and the AP terms are rounded operation by operation like numpy's.
-#include "common.h"
-#include "sort_device.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <algorithm>
-#include <mutex>
-#include <vector>
+#include "det_metric_device.h"
+#include "det_metric_host.h"
+#include "det_order.h"
 
 using namespace wtdev;
 
@@ -38,58 +33,22 @@ constexpr double kEps = 2.220446049250313e-16;                   // np.finfo(np.
 struct Thresholds { double v[kMaxClasses * kMaxThr]; };
 
 struct Workspace {
-    unsigned long long *key_in, *key_out;     // [n_det] confidence keys before / after the first sort
-    long long *row_in, *row_mid, *order;      // [n_det] row indices: iota, after the first sort, after the second
-    unsigned int *seg, *seg_in, *seg_out;     // [n_det] (set, class) segment of a row; gathered; sorted
+    wt::OrderBufs o;                          // keys = confidence keys, segments = (set, class)
     uint8_t *flag, *bucket;                   // [n_det * n_thr], [n_det]
     long long* match;                         // [n_det]
     unsigned int* hits;                       // [n_det] bit t: IoU of the row's box exceeds threshold t
     unsigned long long* best_key;             // [K * n_gt * n_thr] slot of a ground-truth box: best confidence key that claims it
     long long* best_row;                      // [K * n_gt * n_thr] and the first row with that key
     long long* npos;                          // [n_classes * 4]
-    long long* class_offsets;                 // [K * (n_classes + 1)]
     double* min_conf;                         // [K]
-    void* sort_tmp;
-    size_t sort_tmp_bytes;
     size_t bytes;
 };
 
-int seg_bits(size_t n_segments) {             // segments 0 .. n_segments (the last one = rows that take no part)
-    int b = 1;
-    while (((size_t)1 << b) <= n_segments) ++b;
-    return b;
-}
-
-// Temporary storage of the two sorts.  The last answer is kept: a sweep launches the same size over and over.
-int sort_tmp_bytes(size_t n_det, int bits, size_t* out) {
-    static std::mutex mu;
-    static size_t last_n = ~(size_t)0, last_bytes = 0;
-    static int last_bits = -1;
-    std::lock_guard<std::mutex> lock(mu);
-    if (n_det == last_n && bits == last_bits) { *out = last_bytes; return WT_OK; }
-    size_t a = 0, b = 0;
-    unsigned long long* k64 = nullptr;
-    unsigned int* k32 = nullptr;
-    long long* v = nullptr;
-    WT_HIP(rocprim::radix_sort_pairs(nullptr, a, k64, k64, v, v, n_det, 0u, 64u, (hipStream_t) nullptr));
-    WT_HIP(rocprim::radix_sort_pairs(nullptr, b, k32, k32, v, v, n_det, 0u, (unsigned)bits, (hipStream_t) nullptr));
-    *out = std::max(a, b) + 256;
-    last_n = n_det; last_bits = bits; last_bytes = *out;
-    return WT_OK;
-}
-
-Workspace carve(void* base, size_t K, size_t C, size_t T, size_t n_gt, size_t n_det, size_t sort_tmp) {
+int carve(void* base, size_t K, size_t C, size_t T, size_t n_gt, size_t n_det, Workspace* ws) {
     wt::Carver cv(base);
-    Workspace w;
+    Workspace& w = *ws;
     const size_t nd = n_det ? n_det : 1, slots = K * n_gt * T ? K * n_gt * T : 1;
-    w.key_in = cv.take<unsigned long long>(nd);
-    w.key_out = cv.take<unsigned long long>(nd);
-    w.row_in = cv.take<long long>(nd);
-    w.row_mid = cv.take<long long>(nd);
-    w.order = cv.take<long long>(nd);
-    w.seg = cv.take<unsigned int>(nd);
-    w.seg_in = cv.take<unsigned int>(nd);
-    w.seg_out = cv.take<unsigned int>(nd);
+    WT_TRY(wt::carve_order(cv, n_det, K, C, &w.o));
     w.flag = cv.take<uint8_t>(nd * T);
     w.bucket = cv.take<uint8_t>(nd);
     w.match = cv.take<long long>(nd);
@@ -97,33 +56,17 @@ Workspace carve(void* base, size_t K, size_t C, size_t T, size_t n_gt, size_t n_
     w.best_key = cv.take<unsigned long long>(slots);
     w.best_row = cv.take<long long>(slots);
     w.npos = cv.take<long long>(C * kBuckets);
-    w.class_offsets = cv.take<long long>(K * (C + 1));
     w.min_conf = cv.take<double>(K);
-    w.sort_tmp = cv.take<char>(sort_tmp);
-    w.sort_tmp_bytes = sort_tmp;
     w.bytes = cv.off;
-    return w;
+    return WT_OK;
 }
 
 // ---- device helpers ----------------------------------------------------------------------------------------------------
-// Larger key = more confident; -0.0 == 0.0; never 0 for a number (0 marks "no claim" in a slot).
-__device__ __forceinline__ unsigned long long conf_key(double v) {
-    if (v == 0.0) v = 0.0;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// desc_key of a confidence: larger key = more confident; 0 marks "no claim" in a slot
 // np.minimum / np.maximum: a NaN operand is the result
 __device__ __forceinline__ double np_min(double a, double b) { return (a != a) ? a : ((b != b) ? b : (a < b ? a : b)); }
 __device__ __forceinline__ double np_max(double a, double b) { return (a != a) ? a : ((b != b) ? b : (a > b ? a : b)); }
 __device__ __forceinline__ int size_bucket(double px) { return px < kSmall ? 1 : ((px >= kSmall && px < kLarge) ? 2 : (px >= kLarge ? 3 : 0)); }
-
-// The match wave reads slots that its own atomics wrote: every access of a slot goes to L2.
-__device__ __forceinline__ void gsync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-    __builtin_amdgcn_wave_barrier();
-}
-template <class T> __device__ __forceinline__ T slot_load(T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <class T> __device__ __forceinline__ void slot_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- prep ----------------------------------------------------------------------------------------------------------------
 __global__ void det_prep_kernel(long long n_det, int K, int C, int T, const int64_t* __restrict__ set_row_offsets,
@@ -131,17 +74,13 @@ __global__ void det_prep_kernel(long long n_det, int K, int C, int T, const int6
                                 const double* __restrict__ min_conf, Workspace ws, uint8_t* __restrict__ flag, int64_t* __restrict__ match) {
     const long long d = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= n_det) return;
-    int lo = 0, hi = K;                                 // set of the row: last k with set_row_offsets[k] <= d
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (set_row_offsets[mid] <= d) lo = mid; else hi = mid;
-    }
+    const int lo = set_of_row(set_row_offsets, K, d);
     const int c = category[d];
     const double v = conf[d];
     const bool part = c >= 1 && c <= C && v > min_conf[lo];
-    ws.key_in[d] = part ? ~conf_key(v) : ~0ull;
-    ws.row_in[d] = d;
-    ws.seg[d] = part ? (unsigned)(lo * C + (c - 1)) : (unsigned)(K * C);
+    ws.o.key_in[d] = part ? ~desc_key(v) : ~0ull;
+    ws.o.row_in[d] = d;
+    ws.o.seg[d] = part ? (unsigned)(lo * C + (c - 1)) : (unsigned)(K * C);
     ws.hits[d] = 0u;
     match[d] = -1;
     for (int t = 0; t < T; ++t) flag[d * T + t] = 2;
@@ -158,13 +97,9 @@ __global__ void det_npos_kernel(long long n_gt, long long n_images, int C, const
     if (r < n_gt) {
         const int c = label[r];
         if (c >= 1 && c <= C) {
-            long long lo = 0, hi = n_images;            // image of the row: last i with image_gt_offsets[i] <= r
-            while (hi - lo > 1) {
-                const long long mid = (lo + hi) >> 1;
-                if (image_gt_offsets[mid] <= r) lo = mid; else hi = mid;
-            }
+            const long long img = image_of_row(image_gt_offsets, n_images, r);
             const double g_size = (x2[r] - x1[r]) * (y2[r] - y1[r]);
-            const int b = size_bucket(g_size * image_area[lo]);
+            const int b = size_bucket(g_size * image_area[img]);
             atomicAdd(&cnt[(c - 1) * kBuckets], 1u);
             if (b) atomicAdd(&cnt[(c - 1) * kBuckets + b], 1u);
         }
@@ -187,12 +122,11 @@ __global__ __launch_bounds__(kWave) void det_match_kernel(
     __shared__ long long trow[kWave];
     const int lane = threadIdx.x & 63;
     const unsigned long long lt = lanemask_lt();
-    const size_t p = blockIdx.x;
-    const int c = (int)(p % (size_t)C) + 1;
-    const long long img = (long long)((p / (size_t)C) % (size_t)n_images);
-    const long long k = (long long)(p / ((size_t)C * (size_t)n_images));
-    const long long d0 = set_row_offsets[k] + image_det_offsets[k * (n_images + 1) + img];
-    const long long d1 = set_row_offsets[k] + image_det_offsets[k * (n_images + 1) + img + 1];
+    const DetProblem prob(blockIdx.x, n_images, C);
+    const int c = prob.c + 1;
+    const long long img = prob.img, k = prob.k;
+    long long d0, d1;
+    prob.rows(set_row_offsets, image_det_offsets, n_images, &d0, &d1);
     if (d0 >= d1) return;
     const double minc = min_conf[k];
     bool any = false;
@@ -261,7 +195,7 @@ __global__ __launch_bounds__(kWave) void det_match_kernel(
             wsync();
         }
         if (mine) {
-            const unsigned long long key = conf_key(cf);
+            const unsigned long long key = desc_key(cf);
             unsigned int hm = 0u;
             if (jmax >= 0)
                 for (int t = 0; t < T; ++t)
@@ -282,7 +216,7 @@ __global__ __launch_bounds__(kWave) void det_match_kernel(
         if (!mine) continue;
         const unsigned int hm = ws.hits[d];
         if (!hm) continue;
-        const unsigned long long key = conf_key(D.conf[d]);
+        const unsigned long long key = desc_key(D.conf[d]);
         const long long j = match[d];
         for (int t = 0; t < T; ++t)
             if (((hm >> t) & 1u) && slot_load(&best_key[j * T + t]) == key) atomicMin(&best_row[j * T + t], d);
@@ -302,51 +236,7 @@ __global__ __launch_bounds__(kWave) void det_match_kernel(
     }
 }
 
-// ---- ordering helpers ------------------------------------------------------------------------------------------------------
-__global__ void det_gather_seg_kernel(long long n, const long long* __restrict__ rows, const unsigned int* __restrict__ seg, unsigned int* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = seg[rows[i]];
-}
-
-// class_offsets[k * (C + 1) + c] = first ordered position of segment k * C + c (c = C: the end of set k's last class)
-__global__ void det_offsets_kernel(long long n, int K, int C, const unsigned int* __restrict__ seg_sorted, long long* __restrict__ class_offsets,
-                                   int64_t* __restrict__ class_offsets_out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)K * (C + 1)) return;
-    const unsigned int s = (unsigned int)((i / (C + 1)) * C + i % (C + 1));
-    long long lo = 0, hi = n;                            // lower bound of s
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (seg_sorted[mid] < s) lo = mid + 1; else hi = mid;
-    }
-    class_offsets[i] = lo;
-    if (class_offsets_out) class_offsets_out[i] = lo;
-}
-
 // ---- curve -----------------------------------------------------------------------------------------------------------------
-// exclusive prefix sum over the workgroup's threads; *total = the sum.  lds: kCurveWaves + 1 ints.
-__device__ __forceinline__ int block_excl_sum(int v, int* total, int* lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int u = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();                                     // the previous use of lds is over
-    if (lane == kWave - 1) lds[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kCurveWaves; ++w) {
-        const int s = lds[w];
-        if (w < wave) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 // maximum over the threads AFTER this one (0 when there is none; the values are >= 0); *total = the maximum over all.
 __device__ __forceinline__ double block_excl_max_after(double v, double* total, double* lds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -434,7 +324,7 @@ __global__ __launch_bounds__(kCurveThreads) void det_curve_kernel(
             packed += (tpv[u] << 16) + fpv[u];
         }
         int tile_total;
-        const int before = block_excl_sum(packed, &tile_total, lds_i);
+        const int before = block_excl_sum<kCurveWaves>(packed, &tile_total, lds_i);
         const long long base_tp = rem_tp - (tile_total >> 16), base_fp = rem_fp - (tile_total & 0xffff);
         long long ctp = base_tp + (before >> 16), cfp = base_fp + (before & 0xffff);
         double prec[kCurveItems], step[kCurveItems];
@@ -505,9 +395,9 @@ extern "C" {
 
 size_t wt_det_eval_workspace(int32_t k_sets, int64_t n_images, int32_t n_classes, int32_t n_thr, int64_t n_gt, int64_t n_det) {
     if (check_sizes(k_sets, n_images, n_classes, n_thr, n_gt, n_det) != WT_OK) return 0;
-    size_t tmp = 0;
-    if (sort_tmp_bytes((size_t)n_det, seg_bits((size_t)k_sets * n_classes), &tmp) != WT_OK) return 0;
-    return carve(nullptr, (size_t)k_sets, (size_t)n_classes, (size_t)n_thr, (size_t)n_gt, (size_t)n_det, tmp).bytes + 256;
+    Workspace ws;
+    if (carve(nullptr, (size_t)k_sets, (size_t)n_classes, (size_t)n_thr, (size_t)n_gt, (size_t)n_det, &ws) != WT_OK) return 0;
+    return ws.bytes + 256;
 }
 
 int wt_det_eval_dev(int64_t n_gt, const double* gx1, const double* gy1, const double* gx2, const double* gy2, const int32_t* g_label,
@@ -526,17 +416,15 @@ int wt_det_eval_dev(int64_t n_gt, const double* gx1, const double* gy1, const do
         return WT_ERR_INVALID;
     }
     const int K = k_sets, C = n_classes, T = n_thr;
-    const int bits = seg_bits((size_t)K * C);
-    size_t tmp = 0;
-    WT_TRY(sort_tmp_bytes((size_t)n_det, bits, &tmp));
-    Workspace ws = carve(wt::align_ptr(workspace), (size_t)K, (size_t)C, (size_t)T, (size_t)n_gt, (size_t)n_det, tmp);
+    Workspace ws;
+    WT_TRY(carve(wt::align_ptr(workspace), (size_t)K, (size_t)C, (size_t)T, (size_t)n_gt, (size_t)n_det, &ws));
     if (!workspace || workspace_bytes < ws.bytes + 256) {
         wt::set_error("evaluation workspace too small: need %zu bytes, have %zu", ws.bytes + 256, workspace_bytes);
         return WT_ERR_CAPACITY;
     }
     uint8_t* flag = tp_flag ? tp_flag : ws.flag;
     int64_t* match = match_gt ? match_gt : (int64_t*)ws.match;
-    long long* ord = order ? (long long*)order : ws.order;
+    long long* ord = order ? (long long*)order : ws.o.order;
     Thresholds th;
     for (int c = 0; c < kMaxClasses; ++c)
         for (int t = 0; t < kMaxThr; ++t) th.v[c * kMaxThr + t] = (c < C && t < T) ? thr[c * T + t] : 2.0;
@@ -561,17 +449,8 @@ int wt_det_eval_dev(int64_t n_gt, const double* gx1, const double* gy1, const do
         hipLaunchKernelGGL(det_match_kernel, dim3((unsigned)n_problems), dim3(kWave), 0, stream, G, g_label, image_gt_offsets, image_area,
                            (long long)n_images, (long long)n_gt, C, T, set_row_offsets, image_det_offsets, D, category, ws.min_conf, th, ws, flag, match);
     }
-    if (n_det > 0) {
-        size_t bytes = ws.sort_tmp_bytes;
-        WT_HIP(rocprim::radix_sort_pairs(ws.sort_tmp, bytes, ws.key_in, ws.key_out, ws.row_in, ws.row_mid, (size_t)n_det, 0u, 64u, stream));
-        hipLaunchKernelGGL(det_gather_seg_kernel, dim3((unsigned)((n_det + 255) / 256)), dim3(256), 0, stream, (long long)n_det, ws.row_mid, ws.seg, ws.seg_in);
-        bytes = ws.sort_tmp_bytes;
-        WT_HIP(rocprim::radix_sort_pairs(ws.sort_tmp, bytes, ws.seg_in, ws.seg_out, ws.row_mid, ord, (size_t)n_det, 0u, (unsigned)bits, stream));
-    }
-    const long long n_off = (long long)K * (C + 1);
-    hipLaunchKernelGGL(det_offsets_kernel, dim3((unsigned)((n_off + 255) / 256)), dim3(256), 0, stream, (long long)n_det, K, C, ws.seg_out, ws.class_offsets,
-                       class_offsets);
-    hipLaunchKernelGGL(det_curve_kernel, dim3((unsigned)((size_t)K * C * T * kBuckets)), dim3(kCurveThreads), 0, stream, C, T, ord, ws.class_offsets, flag,
+    WT_TRY(wt::enqueue_order(ws.o, n_det, K, C, ord, class_offsets, stream));
+    hipLaunchKernelGGL(det_curve_kernel, dim3((unsigned)((size_t)K * C * T * kBuckets)), dim3(kCurveThreads), 0, stream, C, T, ord, ws.o.class_offsets, flag,
                        ws.bucket, ws.npos, ap, ar, npos, tp, fp, ctp, cfp);
     WT_HIP(hipGetLastError());
     return WT_OK;
@@ -592,29 +471,9 @@ int wt_det_eval_host(int64_t n_gt, const double* gx1, const double* gy1, const d
     WT_TRY(check_sizes(k_sets, n_images, n_classes, n_thr, n_gt, n_det));
     if ((ctp == nullptr) != (cfp == nullptr)) { wt::set_error("wt_det_eval_host: ctp and cfp come together"); return WT_ERR_INVALID; }
     // ---- the layout must be what the kernels walk: checked here, the device form trusts its caller ----
-    if (image_gt_offsets[0] != 0 || image_gt_offsets[n_images] != n_gt || set_row_offsets[0] != 0) {
-        wt::set_error("wt_det_eval_host: CSR offsets do not cover the rows");
-        return WT_ERR_INVALID;
-    }
-    for (int64_t i = 0; i < n_images; ++i)
-        if (image_gt_offsets[i + 1] < image_gt_offsets[i]) { wt::set_error("image_gt_offsets must be non-decreasing (image %lld)", (long long)i); return WT_ERR_INVALID; }
-    for (int64_t r = 0; r < n_gt; ++r)
-        if (g_label[r] < 1 || g_label[r] > n_classes) {
-            wt::set_error("ground-truth row %lld: label %d outside 1..%d", (long long)r, (int)g_label[r], (int)n_classes);
-            return WT_ERR_INVALID;
-        }
-    for (int32_t k = 0; k < k_sets; ++k) {
-        const int64_t* ido = image_det_offsets + (size_t)k * (size_t)(n_images + 1);
-        const int64_t rows = set_row_offsets[k + 1] - set_row_offsets[k];
-        if (rows < 0 || ido[0] != 0 || ido[n_images] != rows) { wt::set_error("result set %d: image_det_offsets do not cover its rows", (int)k); return WT_ERR_INVALID; }
-        for (int64_t i = 0; i < n_images; ++i)
-            if (ido[i + 1] < ido[i]) { wt::set_error("result set %d: image_det_offsets must be non-decreasing (image %lld)", (int)k, (long long)i); return WT_ERR_INVALID; }
-        for (int64_t r = set_row_offsets[k]; r < set_row_offsets[k + 1]; ++r)
-            if (category[r] < 1 || category[r] > n_classes) {
-                wt::set_error("result set %d, row %lld: category %d outside 1..%d", (int)k, (long long)(r - set_row_offsets[k]), (int)category[r], (int)n_classes);
-                return WT_ERR_INVALID;
-            }
-    }
+    const wt::DetLayout layout = {n_gt, n_images, k_sets, image_gt_offsets, set_row_offsets, image_det_offsets};
+    WT_TRY(wt::check_det_layout(layout, "wt_det_eval_host"));
+    WT_TRY(wt::check_det_eval_rows(layout, g_label, category, n_classes));
     WT_TRY(wt::ensure_device());
     const size_t ng = (size_t)n_gt, nd = (size_t)n_det, K = (size_t)k_sets, C = (size_t)n_classes, T = (size_t)n_thr, ni = (size_t)n_images;
     const size_t n_out = K * C * T * kBuckets;
@@ -646,20 +505,13 @@ int wt_det_eval_host(int64_t n_gt, const double* gx1, const double* gy1, const d
                            tp_flag ? dflag.as<uint8_t>() : nullptr, match_gt ? dmatch.as<int64_t>() : nullptr, order ? dorder.as<int64_t>() : nullptr,
                            class_offsets ? dco.as<int64_t>() : nullptr, ctp ? dctp.as<int64_t>() : nullptr, ctp ? dcfp.as<int64_t>() : nullptr,
                            dstat.as<int32_t>(), dws.p, wsb, nullptr));
-    WT_HIP(hipDeviceSynchronize());
-    int32_t st = 0;
-    WT_HIP(hipMemcpy(&st, dstat.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (st) { wt::set_error("evaluation kernel reported status %d (4 = capacity)", (int)st); return (int)st; }
-    WT_HIP(hipMemcpy(ap, dap.p, 8 * n_out, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(ar, dar.p, 8 * n_out, hipMemcpyDeviceToHost));
-    WT_HIP(hipMemcpy(npos, dnp.p, 8 * n_out, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(tp, dtp.p, 8 * n_out, hipMemcpyDeviceToHost));
-    WT_HIP(hipMemcpy(fp, dfp.p, 8 * n_out, hipMemcpyDeviceToHost));
-    if (class_offsets) WT_HIP(hipMemcpy(class_offsets, dco.p, 8 * K * (C + 1), hipMemcpyDeviceToHost));
-    if (nd) {
-        if (tp_flag) WT_HIP(hipMemcpy(tp_flag, dflag.p, nd * T, hipMemcpyDeviceToHost));
-        if (match_gt) WT_HIP(hipMemcpy(match_gt, dmatch.p, 8 * nd, hipMemcpyDeviceToHost));
-        if (order) WT_HIP(hipMemcpy(order, dorder.p, 8 * nd, hipMemcpyDeviceToHost));
-        if (ctp) { WT_HIP(hipMemcpy(ctp, dctp.p, 8 * nd * T, hipMemcpyDeviceToHost)); WT_HIP(hipMemcpy(cfp, dcfp.p, 8 * nd * T, hipMemcpyDeviceToHost)); }
-    }
+    WT_TRY(wt::finish_det_call(dstat, "evaluation", " (4 = capacity)"));
+    WT_TRY(dap.download(ap)); WT_TRY(dar.download(ar)); WT_TRY(dnp.download(npos)); WT_TRY(dtp.download(tp)); WT_TRY(dfp.download(fp));
+    if (class_offsets) WT_TRY(dco.download(class_offsets));
+    if (tp_flag) WT_TRY(dflag.download(tp_flag));
+    if (match_gt) WT_TRY(dmatch.download(match_gt));
+    if (order) WT_TRY(dorder.download(order));
+    if (ctp) { WT_TRY(dctp.download(ctp)); WT_TRY(dcfp.download(cfp)); }
     return WT_OK;
 }
 
